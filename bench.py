@@ -5,7 +5,7 @@ equivalent: H SpGraphAttentionLayers sharing inputs, outputs concatenated) forwa
 one batch of synthetic graphs, inputs resident in HBM.  Default workload = BASELINE.json configs[1]:
 512 graphs x 16 nodes x 64 edges, F = R = 200, 8 heads x D = 200, fp32.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU, every rank owns its own graphs (weak scaling) — BASELINE.json configs[3]: 8 192 graphs sharded over 8 GPUs,
@@ -21,6 +21,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -49,7 +50,36 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-extras", action="store_true", help="main step and roofline only (profiling runs): no exact_fp32 / uncached / secondary legs")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's out, g_x, g_edge_embed, g_a, g_a_2) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: bytes written in all, at most
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """Write every tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy: float64 stays float64, everything else becomes float32.
+    Each array gets an equal share of `budget`; one larger than its share is written as a fixed sample of its rows (leading dimension):
+    the sorted rows numpy.random.default_rng(0) draws without replacement — the same rows whenever the shape is the same, so that two
+    builds run with the same arguments can be compared file by file.  Returns {name: {"shape": full shape, "rows_written": k}}."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        shape = list(a.shape)
+        if a.nbytes > share and a.ndim >= 1:
+            k = max(1, share // max(1, a[0].nbytes))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = {"shape": shape, "rows_written": int(a.shape[0]) if a.ndim else 1}
+    return written
 
 
 def _free_port():
@@ -155,7 +185,6 @@ def main():
         # BASELINE.json configs[4]: power-law degree graphs of up to 256 nodes / 4 096 edges (SURVEY 8d's generator: n ~ U{16..256},
         # e = min(4096, 16 n), destinations ~ Zipf(1)); `--graphs` graphs per GPU, generated identically on every rank and dealt out by
         # edge count (longest-processing-time packing) so that the ranks' edge loads — what the step's time follows — are level
-        import numpy as np
         from recon_amd.dist import shard_by_edges
         rs = np.random.RandomState(0)
         sizes = [int(rs.randint(16, 257)) for _ in range(B * world)]
@@ -206,12 +235,15 @@ def main():
     # blocks the host at its start (measured with 2 processes on one GPU: 2.42 ms overlapped against 1.99 ms plain)
     want = os.environ.get("RECON_DP_OVERLAP", "1" if (backend == "nccl") else "0")
     overlap = sync.active() and want != "0"
+    last = {} if args.dump_outputs else None                                  # --dump-outputs: the latest step's output, kept for the dump
 
     def step():
         bucket.zero()
         xd.grad = None
         eed.grad = None
         out = model.heads_forward(xd, edged, eed, nohop, nohop)
+        if last is not None:
+            last["out"] = out
         if overlap:
             with sync.installed():
                 out.backward(Gd)
@@ -251,6 +283,13 @@ def main():
         step()
     dt = timed_region(step, args.steps, barrier_sync, reduce_max)
     edges_per_s = E_global * args.steps / dt
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # here, before the legs below run step() again (on other GEMM families) and overwrite the gradients
+        dumped = dump_outputs(args.dump_outputs, {
+            "out": last["out"], "g_x": xd.grad, "g_edge_embed": eed.grad,
+            "g_a": torch.stack([att.a.grad for att in model.attentions]),           # [H, D, 2F + R]
+            "g_a_2": torch.cat([att.a_2.grad for att in model.attentions])})        # [H, D]
 
     result = {
         "metric": "edges aggregated/sec (GAT fwd+bwd) on synthetic KG-context graphs",
@@ -265,6 +304,8 @@ def main():
                    "backend": ({"nccl": "nccl (RCCL)"}.get(backend, backend) + (", %d ranks on %d GPU(s): schedule exercised, nothing measured" % (world, ndev) if ndev < world else "")
                                + (", RECON_DIST_FORCE=1: every collective executed at world size 1" if (force and world == 1) else "")) if backend else None},
     }
+    if dumped is not None:
+        result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "of": "the last timed step, rank 0"}
 
     if dt_no_comm is not None:
         result.update(scaling_fields(E_global / world, args.steps, dt, dt_no_comm))

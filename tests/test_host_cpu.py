@@ -356,3 +356,29 @@ def test_trust_marks_carry_version_and_bound():
     assert trust_bounds(q) == (7, 3) and trust_bounds(torch.zeros(1)) == (None, None)
     k = trust(torch.arange(5))                                            # keys built for exactly the table they index: no bound
     assert trusted(k, 5) and trusted(k, 1)
+
+
+def test_bench_dump_outputs_is_bounded_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: float32 (float64 kept) .npy files, at most the budget in all; an array above its share is a fixed sample
+    of its rows, the same rows on every call with the same shapes, so that two builds' dumps compare file by file."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"out": torch.randn(4096, 64, generator=g), "g_x": torch.randn(100, 8, generator=g).double(),
+              "g_a": torch.randn(2, 3, 5, generator=g).half()}
+    budget = 3 * 64 * 1024
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays, budget=budget)
+    bench.dump_outputs(str(tmp_path / "b"), {k: v.clone() for k, v in arrays.items()}, budget=budget)
+    total = 0
+    for name, t in arrays.items():
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == (np.float64 if t.dtype == torch.float64 else np.float32)
+        np.testing.assert_array_equal(a, b)
+        assert info[name]["shape"] == list(t.shape) and info[name]["rows_written"] == a.shape[0]
+        total += a.nbytes
+    assert total <= budget
+    out = np.load(tmp_path / "a" / "out.npy")
+    assert out.shape == (budget // 3 // (64 * 4), 64)                              # sampled rows of the large array ...
+    full = arrays["out"].numpy()
+    assert all((full == r).all(axis=1).any() for r in out[:16])                    # ... taken unchanged from it
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "g_x.npy"), arrays["g_x"].numpy())   # small ones whole
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "g_a.npy"), arrays["g_a"].float().numpy())
