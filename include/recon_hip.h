@@ -794,6 +794,36 @@ int recon_rows_normalize_fwd(const float* ew, const float* skip, const float* ma
 int recon_rows_normalize_bwd(const float* g_y, const float* y, const float* norm, const float* mask, int64_t N, int32_t C, float eps, float* g_t,
                              float* g_skip, recon_stream_t stream);
 
+/* --------------------------------------------------------------------------------------------
+ * E1  link-prediction evaluation of the ConvKB scorer (csrc/kg_eval.hip): SpKBGATConvOnly.batch_test (GAT/models.py:300-304) ->
+ *     ConvKB.forward (GAT/layers.py:41-46) over every candidate of one slot of every test triple, as Corpus.get_validation_pred
+ *     (GAT/create_batch.py:905-1099) and get_validation_cnfmat (:1365-1420) run it.  fc1 is split along its concatenated input:
+ *     P_h = E W_h^T, P_r = Rel W_r^T, P_t = E W_t^T (W1 = [W_h | W_r | W_t], recon_sgemm_ex with ldb = 3 D), and
+ *         s(q, c) = b2 + sum_d w2[d] leaky(u[q, d] + P_slot[c, d]),   u[q] = (P_a[a] + P_b[b]) + b1,   leaky(x) = max(x, slope x)
+ *     with (a, b) the two other columns of the triple in column order.  slot = the column replaced: 0 head, 1 relation, 2 tail.
+ *     triples int64 [Q][3] = (head, relation, tail); P_h, P_t [n_ent][D], P_r [n_rel][D]; b1, w2 [D]; b2 [1] (device, read by the kernels);
+ *     0 <= slope <= 1 (RECON_ERR_UNSUPPORTED otherwise; the reference's nl1 = nn.LeakyReLU(): 0.01).  Every score comes from ONE routine with
+ *     one summation order, so a (query, candidate) scores bit-identically in both entry points.  Ids are range-checked by the caller
+ *     (recon_amd.kg_eval); the kernels never read outside a table: a query with an id outside its table gets rank 0 and a NaN score (a NaN
+ *     dense score), an excluded id outside the candidate table is ignored.
+ * ------------------------------------------------------------------------------------------*/
+enum { RECON_KGE_HEAD = 0, RECON_KGE_RELATION = 1, RECON_KGE_TAIL = 2 };
+/* Filtered rank without the Q x N score matrix (:934-1020): ranks int64 [Q] = 1 + #{c not excluded : s(q, c) > s*(q)}, true_scores [Q] = s*(q)
+ * = s(q, true id).  That is the position of the true triple in a stable descending sort with the true triple inserted at index 0 (:965-968,
+ * :1016-1020): ties count for the true triple.  The excluded ids of query q are filt_ids[filt_begin[q] .. filt_end[q]) (int64, no duplicates;
+ * may contain the true id; filt_ids NULL: raw ranks) — valid_triples_dict's members among the candidates (:947-963).  workspace:
+ * recon_convkb_rank_workspace_floats(Q, D) floats.  Two launches; the rank is an integer sum, deterministic. */
+size_t recon_convkb_rank_workspace_floats(int64_t Q, int32_t D);
+int recon_convkb_rank(int32_t slot, int64_t Q, const int64_t* triples, const float* P_h, const float* P_r, const float* P_t, int64_t n_ent,
+                      int64_t n_rel, int32_t D, const float* b1, const float* w2, const float* b2, float slope, const int64_t* filt_ids,
+                      const int64_t* filt_begin, const int64_t* filt_end, float* workspace, size_t workspace_floats, int64_t* ranks,
+                      float* true_scores, recon_stream_t stream);
+/* Dense scores S[q][j] = s(q, c0 + j), j < C, row stride ldS >= C: with slot = RECON_KGE_RELATION and [c0, c0 + C) = [0, n_rel) the `scores`
+ * tensor of get_validation_cnfmat (:1369-1420) laid out [Q][n_rel].  Q <= 65535 per call. */
+int recon_convkb_scores(int32_t slot, int64_t Q, const int64_t* triples, const float* P_h, const float* P_r, const float* P_t, int64_t n_ent,
+                        int64_t n_rel, int32_t D, const float* b1, const float* w2, const float* b2, float slope, int64_t c0, int64_t C, float* S,
+                        int64_t ldS, recon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

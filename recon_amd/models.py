@@ -9,7 +9,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .gat_layers import SpGraphAttentionLayer, gat_heads, cat_edge_embed, gather_rows, gather_rows_pair, small_mm, IndexedRows, set_weight_grad_destination
+from .gat_layers import ConvKB, SpGraphAttentionLayer, gat_heads, cat_edge_embed, gather_rows, gather_rows_pair, small_mm, IndexedRows, set_weight_grad_destination
 from .graph import prepare_graph, trust, trusted, trust_bounds
 from .sampler import prune_batch_launch
 
@@ -283,3 +283,53 @@ class SpKBGATModified(nn.Module):
     def batch_test(self, Corpus_, batch_entities, adj, train_indices_nhop, entity_embeddings):
         ent = F.normalize(entity_embeddings.data, p=2, dim=1).detach()
         return self._encode(Corpus_, ent, self.relation_embeddings.detach(), batch_entities, adj, train_indices_nhop)
+
+
+class SpKBGATConvOnly(nn.Module):
+    """The ConvKB scorer over frozen final embeddings (GAT/models.py:240-304): same constructor, state_dict keys (final_entity_embeddings,
+    final_relation_embeddings, convKB.*) and torch arithmetic in forward / batch_test, so `conv/trained_*.pth` loads with strict=True and
+    training stays as it is.  `evaluate` runs the link-prediction evaluation on the HIP kernels of recon_amd.kg_eval."""
+
+    def __init__(self, initial_entity_emb, initial_relation_emb, entity_out_dim, relation_out_dim, drop_GAT, drop_conv, alpha, alpha_conv,
+                 nheads_GAT, conv_out_channels):
+        super().__init__()
+        self.num_nodes = initial_entity_emb.shape[0]
+        self.entity_in_dim = initial_entity_emb.shape[1]
+        self.entity_out_dim_1 = entity_out_dim[0]
+        self.nheads_GAT_1 = nheads_GAT[0]
+        self.entity_out_dim_2 = entity_out_dim[1]
+        self.nheads_GAT_2 = nheads_GAT[1]
+        self.num_relation = initial_relation_emb.shape[0]
+        self.relation_dim = initial_relation_emb.shape[1]
+        self.relation_out_dim_1 = relation_out_dim[0]
+        self.drop_GAT = drop_GAT
+        self.drop_conv = drop_conv
+        self.alpha = alpha
+        self.alpha_conv = alpha_conv
+        self.conv_out_channels = conv_out_channels
+        D = self.entity_out_dim_1 * self.nheads_GAT_1
+        self.final_entity_embeddings = nn.Parameter(torch.randn(self.num_nodes, D))
+        self.final_relation_embeddings = nn.Parameter(torch.randn(self.num_relation, D))
+        self.convKB = ConvKB(D, 3, 1, self.conv_out_channels, self.drop_conv, self.alpha_conv)
+
+    def _score(self, batch_inputs):
+        if not self.final_entity_embeddings.is_cuda or not batch_inputs.is_cuda:
+            raise RuntimeError("recon_amd: SpKBGATConvOnly expects GPU tensors (this package has no CPU path)")
+        conv_input = torch.cat((self.final_entity_embeddings[batch_inputs[:, 0], :], self.final_relation_embeddings[batch_inputs[:, 1]],
+                                self.final_entity_embeddings[batch_inputs[:, 2], :]), dim=1)
+        return self.convKB(conv_input)
+
+    def forward(self, Corpus_, adj, batch_inputs):
+        return self._score(batch_inputs)
+
+    def batch_test(self, batch_inputs):
+        return self._score(batch_inputs)
+
+    def evaluate(self, test_triples, known_triples, unique_entities=None):
+        """Filtered head and tail ranking of test_triples against known_triples (train + valid + test: valid_triples_dict) and the metrics
+        Corpus.get_validation_pred prints (GAT/create_batch.py:905-1199): recon_amd.kg_eval.link_prediction_metrics' dict."""
+        from . import kg_eval
+        with torch.no_grad():
+            proj = kg_eval.convkb_projections(self.final_entity_embeddings, self.final_relation_embeddings, self.convKB)
+            rh, rt, _ = kg_eval.rank_entities(proj, test_triples, known_triples, unique_entities=unique_entities)
+        return kg_eval.link_prediction_metrics(rh, rt)
