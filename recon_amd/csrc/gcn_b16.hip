@@ -420,8 +420,8 @@ __global__ void __launch_bounds__(256 * NS, 1) k_gcn_b16_fused_fwd(const GcnFuse
 // (the A fragments of the next layer's x @ W are 16-byte LDS reads of exactly the bits the per-layer kernel would have written to and
 // re-read from HBM: results are bit-equal to L calls of it).  HBM traffic: x once, the last layer's result once, adj once; the W^T planes
 // of every layer through the LDS slab from L2 ("fused 3-hop, H resident in LDS, 19 KB per graph: 42 MB" at cfg 3a against
-// 125 MB layer by layer).  Workgroup = 4 graphs x NS column parts as above; between the K loop of a layer and the writes of its result into
-// the image, and again before the next layer reads it, a workgroup barrier.
+// 125 MB layer by layer).  Workgroup = 4 graphs x 4 column parts as above, one graph per wave; between the K loop of a layer and the writes
+// of its result into the image, and again before the next layer reads it, a workgroup barrier.
 constexpr int kMaxStack = 8;
 struct GcnStackK {
     const uint16_t* x; int64_t ldx;
@@ -437,21 +437,20 @@ struct GcnStackK {
 // Every operand arrives by range-checked LDS-DMA (buffer_load ... lds: no staging registers, rows / columns that do not exist come back as
 // zeros): the graphs' x tiles straight into the activation images at the start, the W^T slabs of ALL layers through a ring of three
 // 20-KiB slabs two K steps ahead (counted vmcnt, raw s_barrier: the copies stay in flight across the barriers; the first form of this
-// kernel staged W through registers one step ahead and waited for it at every step).  One K-loop body for every layer; NS = 4 column parts
-// = 16 waves per CU fit without spills because nothing but accumulators and fragments lives in registers.
-// GPW = graphs per wave: a wave that works on two graphs reads each W^T fragment ONCE for both — the K step of the 16-wave form is bound by
-// LDS reads (16 waves x (2 x-fragments + 5 W^T fragments) x 1 KiB = 112 KiB per step at 128 B per clock: ~900 of a step's ~1 800 cycles, in
-// lockstep with the barrier, against 640 cycles of matrix pipe); 8 waves x (2 x 2 + 5) KiB = 72 KiB.
-template <int NS, int GPW>
-__global__ void __launch_bounds__(256 * NS / GPW, 1) k_gcn_b16_stack_fwd(const GcnStackK p) {
+// kernel staged W through registers one step ahead and waited for it at every step).  One K-loop body for every layer; 4 column parts
+// = 16 waves per CU fit without spills because nothing but accumulators and fragments lives in registers.  The K step is bound by LDS reads
+// (16 waves x (2 x-fragments + 5 W^T fragments) x 1 KiB = 112 KiB per step at 128 B per clock: ~900 of a step's ~1 800 cycles, in lockstep
+// with the barrier, against 640 cycles of matrix pipe), yet lighter grids were both slower: two graphs per wave (each W^T fragment read once
+// for both: 8 waves, 72 KiB; 36 us against 34 at cfg 3a) and five column parts x two graph slots (10 waves, 80 KiB).
+__global__ void __launch_bounds__(1024, 1) k_gcn_b16_stack_fwd(const GcnStackK p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char st_sm[];      // W^T slabs [3][20 KiB] | activations [4 graphs][NKI][2 KiB] | scratch 1 KiB
-    constexpr int NTP = kFusedNT / NS, NGS = 4 / GPW, NW = NGS * NS, SLAB = kFusedNT * 16 * 64, NRING = 3;      // NGS = graph slots of waves
+    constexpr int NS = 4, NTP = kFusedNT / NS, NW = 4 * NS, SLAB = kFusedNT * 16 * 64, NRING = 3;
     constexpr int SP = kFusedNT;                                         // pieces (16 rows x 64 B) of a slab
     constexpr int NDW = (SP + NW - 1) / NW;                               // copy instructions per wave and slab (waves past the last piece: scratch)
     const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int li = lane & 15, lq = lane >> 4;
-    const int gw = (w % NGS) * GPW, g0 = blockIdx.x * 4 + gw;            // this wave's first graph (slot in the workgroup, index in the batch)
-    const int c_lo = (w / NGS) * NTP;
+    const int gw = w % 4, g = blockIdx.x * 4 + gw;                      // this wave's graph (slot in the workgroup, index in the batch)
+    const int c_lo = (w / 4) * NTP;
     const int n = p.n, nt = p.nt, D = p.D;
     const int nk0 = (p.I0 + 31) >> 5, nkh = (D + 31) >> 5, nki = nk0 > nkh ? nk0 : nkh;      // K steps of layer 0 / of the others / of an image
     unsigned char* Hg = st_sm + NRING * SLAB + gw * nki * 2048;
@@ -512,28 +511,23 @@ __global__ void __launch_bounds__(256 * NS / GPW, 1) k_gcn_b16_stack_fwd(const G
     issue();
     issue();
     // adj^T fragments (8-byte loads: n % 4 == 0, adj 8-byte aligned — checked by the host), kept for all layers
-    bf16x8 adjf[GPW][2];
+    bf16x8 adjf[2];
     {
         const auto ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.adj), 0,
                                                           sat_i32(static_cast<int64_t>(p.B) * n * n * 2), 0x00020000);
-        u32x2_g adjv[GPW][2][2];
+        u32x2_g adjv[2][2];
 #pragma unroll
-        for (int gi = 0; gi < GPW; ++gi)
+        for (int it = 0; it < 2; ++it) {
+            const int i = 16 * it + li;
 #pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const int i = 16 * it + li, g = g0 + gi;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int j0 = 16 * h + 4 * lq;
-                    const uint32_t base = static_cast<uint32_t>(((static_cast<int64_t>(g) * n + i) * n + j0) * 2);
-                    adjv[gi][it][h] = __builtin_amdgcn_raw_buffer_load_b64(ra, (g < p.B && i < n && j0 < n) ? base : 0xfffffff0u, 0, 0);
-                }
+            for (int h = 0; h < 2; ++h) {
+                const int j0 = 16 * h + 4 * lq;
+                const uint32_t base = static_cast<uint32_t>(((static_cast<int64_t>(g) * n + i) * n + j0) * 2);
+                adjv[it][h] = __builtin_amdgcn_raw_buffer_load_b64(ra, (g < p.B && i < n && j0 < n) ? base : 0xfffffff0u, 0, 0);
             }
+        }
 #pragma unroll
-        for (int gi = 0; gi < GPW; ++gi)
-#pragma unroll
-            for (int it = 0; it < 2; ++it)
-                adjf[gi][it] = __builtin_bit_cast(bf16x8, u32x4_g{adjv[gi][it][0].x, adjv[gi][it][0].y, adjv[gi][it][1].x, adjv[gi][it][1].y});
+        for (int it = 0; it < 2; ++it) adjf[it] = __builtin_bit_cast(bf16x8, u32x4_g{adjv[it][0].x, adjv[it][0].y, adjv[it][1].x, adjv[it][1].y});
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the x tiles, the first two slabs, adj
     if (p.xcopy) {
@@ -577,13 +571,11 @@ __global__ void __launch_bounds__(256 * NS / GPW, 1) k_gcn_b16_stack_fwd(const G
             for (int d = 0; d < 4; ++d) m[d] = (k0 + 2 * d < I ? 0x0000ffffu : 0u) | (k0 + 2 * d + 1 < I ? 0xffff0000u : 0u);
             tailmask = u32x4_g{m[0], m[1], m[2], m[3]};
         }
-        f32x4 acc[GPW][2][NTP];
+        f32x4 acc[2][NTP];
 #pragma unroll
-        for (int gi = 0; gi < GPW; ++gi)
+        for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                for (int c = 0; c < NTP; ++c) acc[gi][rt][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int c = 0; c < NTP; ++c) acc[rt][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int ks = 0; ks < nks; ++ks) {
             // this wave's copies of this step have landed (those of the next step may still travel) ...
@@ -602,13 +594,9 @@ __global__ void __launch_bounds__(256 * NS / GPW, 1) k_gcn_b16_stack_fwd(const G
 #endif
             const unsigned char* slab = st_sm + cb * SLAB;
             const u32x4_g km = ks == nks - 1 ? tailmask : allmask;
-            bf16x8 af[GPW][2];
-#pragma unroll
-            for (int gi = 0; gi < GPW; ++gi) {
-                const u32x4_g c0 = *reinterpret_cast<const u32x4_g*>(Hg + gi * nki * 2048 + ks * 2048 + a_rd0);
-                const u32x4_g c1 = *reinterpret_cast<const u32x4_g*>(Hg + gi * nki * 2048 + ks * 2048 + a_rd1);
-                af[gi][0] = __builtin_bit_cast(bf16x8, c0 & km); af[gi][1] = __builtin_bit_cast(bf16x8, c1 & km);
-            }
+            const u32x4_g c0 = *reinterpret_cast<const u32x4_g*>(Hg + ks * 2048 + a_rd0);
+            const u32x4_g c1 = *reinterpret_cast<const u32x4_g*>(Hg + ks * 2048 + a_rd1);
+            const bf16x8 af0 = __builtin_bit_cast(bf16x8, c0 & km), af1 = __builtin_bit_cast(bf16x8, c1 & km);
             bf16x8 bq[NTP];
 #pragma unroll
             for (int c = 0; c < NTP; ++c) bq[c] = *reinterpret_cast<const bf16x8*>(slab + b_rd + 1024 * c);
@@ -624,12 +612,10 @@ __global__ void __launch_bounds__(256 * NS / GPW, 1) k_gcn_b16_stack_fwd(const G
             if (ns_ < 46) stamp[ns_++] = __builtin_readcyclecounter();
 #endif
 #pragma unroll
-            for (int c = 0; c < NTP; ++c)
-#pragma unroll
-                for (int gi = 0; gi < GPW; ++gi) {
-                    acc[gi][0][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[gi][0], bq[c], acc[gi][0][c], 0, 0, 0);
-                    acc[gi][1][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[gi][1], bq[c], acc[gi][1][c], 0, 0, 0);
-                }
+            for (int c = 0; c < NTP; ++c) {
+                acc[0][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af0, bq[c], acc[0][c], 0, 0, 0);
+                acc[1][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af1, bq[c], acc[1][c], 0, 0, 0);
+            }
             cb = cb + 1 == NRING ? 0 : cb + 1;
         }
         // the layer's bias values out of LDS (copied there once, at the start: requested here from memory, they made this point a vmcnt(0) that
@@ -646,27 +632,23 @@ __global__ void __launch_bounds__(256 * NS / GPW, 1) k_gcn_b16_stack_fwd(const G
             float bv[4];
             bv[0] = bf2f(static_cast<uint16_t>(bvec[c].x & 0xffffu)); bv[1] = bf2f(static_cast<uint16_t>(bvec[c].x >> 16));
             bv[2] = bf2f(static_cast<uint16_t>(bvec[c].y & 0xffffu)); bv[3] = bf2f(static_cast<uint16_t>(bvec[c].y >> 16));
+            const bf16x8 sf = __builtin_bit_cast(bf16x8, u32x4_g{pack2(acc[0][c][0], acc[0][c][1]), pack2(acc[0][c][2], acc[0][c][3]),
+                                                                   pack2(acc[1][c][0], acc[1][c][1]), pack2(acc[1][c][2], acc[1][c][3])});
 #pragma unroll
-            for (int gi = 0; gi < GPW; ++gi) {
-                const int g = g0 + gi;
-                const bf16x8 sf = __builtin_bit_cast(bf16x8, u32x4_g{pack2(acc[gi][0][c][0], acc[gi][0][c][1]), pack2(acc[gi][0][c][2], acc[gi][0][c][3]),
-                                                                       pack2(acc[gi][1][c][0], acc[gi][1][c][1]), pack2(acc[gi][1][c][2], acc[gi][1][c][3])});
+            for (int it = 0; it < 2; ++it) {
+                f32x4 r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sf, adjf[it], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                const int i = 16 * it + li;
+                float v[4];
 #pragma unroll
-                for (int it = 0; it < 2; ++it) {
-                    f32x4 r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sf, adjf[gi][it], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                    const int i = 16 * it + li;
-                    float v[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { v[q] = r[q] + bv[q]; v[q] = (v[q] > 0.f && o0 + q < D) ? v[q] : 0.f; }
-                    const u32x2_g pk = u32x2_g{pack2(v[0], v[1]), pack2(v[2], v[3])};
-                    // the last layer's result to memory (masked by an out-of-range offset), every other one into the image (tiles past it: scratch).
-                    // Rows of nodes past n hold relu(bias): the per-layer kernel never stores them and reads them back as zeros; adj's columns
-                    // for them are zero (out-of-range loads), so they never reach a result
-                    const uint32_t off = (g < p.B && i < n && o0 < p.ldo) ? static_cast<uint32_t>(((static_cast<int64_t>(g) * n + i) * p.ldo + o0) * 2) : 0xfffffff0u;
-                    __builtin_amdgcn_raw_buffer_store_b64(pk, ro, off, 0, 0);
-                    unsigned char* hd = (!last && o0 < 32 * nkh) ? Hg + gi * nki * 2048 + (o0 >> 5) * 2048 + gf_lds_off(i, (o0 & 31) >> 3) + 2 * (o0 & 7) : st_sm + scratch;
-                    *reinterpret_cast<u32x2_g*>(hd) = pk;
-                }
+                for (int q = 0; q < 4; ++q) { v[q] = r[q] + bv[q]; v[q] = (v[q] > 0.f && o0 + q < D) ? v[q] : 0.f; }
+                const u32x2_g pk = u32x2_g{pack2(v[0], v[1]), pack2(v[2], v[3])};
+                // the last layer's result to memory (masked by an out-of-range offset), every other one into the image (tiles past it: scratch).
+                // Rows of nodes past n hold relu(bias): the per-layer kernel never stores them and reads them back as zeros; adj's columns
+                // for them are zero (out-of-range loads), so they never reach a result
+                const uint32_t off = (g < p.B && i < n && o0 < p.ldo) ? static_cast<uint32_t>(((static_cast<int64_t>(g) * n + i) * p.ldo + o0) * 2) : 0xfffffff0u;
+                __builtin_amdgcn_raw_buffer_store_b64(pk, ro, off, 0, 0);
+                unsigned char* hd = (!last && o0 < 32 * nkh) ? Hg + (o0 >> 5) * 2048 + gf_lds_off(i, (o0 & 31) >> 3) + 2 * (o0 & 7) : st_sm + scratch;
+                *reinterpret_cast<u32x2_g*>(hd) = pk;
             }
         }
     }
@@ -1152,13 +1134,10 @@ extern "C" int recon_gcn_b16_fwd(const recon_gcn_b16_args* a, recon_stream_t str
         k.B = a->B; k.n = a->n; k.I = I; k.Ip = b16_kp(I); k.O = O; k.nt = static_cast<int32_t>(ceil_div64(a->ldo, 16));
         k.adj_vec = (a->n % 4 == 0 && (reinterpret_cast<uintptr_t>(a->adj) & 7) == 0) ? 1 : 0;
         k.bias_vec = (!a->bias || (O % 4 == 0 && (reinterpret_cast<uintptr_t>(a->bias) & 7) == 0)) ? 1 : 0;
-        const int ns = [] { const int v = cfg_int(CFG_GCN_FUSED_PARTS, 4); return v == 1 || v == 2 ? v : 4; }();
         const dim3 fg(static_cast<unsigned>(ceil_div64(a->B, 4)));
-        const bool vec = k.adj_vec && k.bias_vec;
-#define CALL_F(N_) do { if (vec) hipLaunchKernelGGL((k_gcn_b16_fused_fwd<N_, true>), fg, dim3(256 * N_), 0, st, k); \
-                        else hipLaunchKernelGGL((k_gcn_b16_fused_fwd<N_, false>), fg, dim3(256 * N_), 0, st, k); } while (0)
-        if (ns == 1) CALL_F(1); else if (ns == 2 || !vec) CALL_F(2); else CALL_F(4);      // the element-wise loads of odd shapes need the registers of the two-part form
-#undef CALL_F
+        // four column parts with 8-byte loads; the element-wise loads of odd shapes need the registers of the two-part form
+        if (k.adj_vec && k.bias_vec) hipLaunchKernelGGL((k_gcn_b16_fused_fwd<4, true>), fg, dim3(1024), 0, st, k);
+        else hipLaunchKernelGGL((k_gcn_b16_fused_fwd<2, false>), fg, dim3(512), 0, st, k);
         RECON_CHECK_LAUNCH();
         return RECON_OK;
     }
@@ -1248,19 +1227,10 @@ extern "C" int recon_gcn_b16_bwd(const recon_gcn_b16_bwd_args* b, recon_stream_t
     return RECON_OK;
 }
 
-// four column parts per graph, one graph per wave (16 waves); RECON_GCN_STACK_GPW=2: two graphs per wave (8 waves; measured 36 us against 34 at cfg 3a)
+// four column parts per graph, one graph per wave: sixteen waves
 static void launch_stack_fwd(const GcnStackK& k, size_t lds, hipStream_t st) {
-    const dim3 grid(static_cast<unsigned>(ceil_div64(k.B, 4)));
-    if (cfg_int(CFG_GCN_STACK_GPW, 1) == 5) {                           // experiment: five column parts x two graph slots = ten waves, 80 KiB of fragment reads per K step
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gcn_b16_stack_fwd<5, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        hipLaunchKernelGGL((k_gcn_b16_stack_fwd<5, 2>), grid, dim3(640), lds, st, k);
-    } else if (cfg_int(CFG_GCN_STACK_GPW, 1) != 2) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gcn_b16_stack_fwd<4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        hipLaunchKernelGGL((k_gcn_b16_stack_fwd<4, 1>), grid, dim3(1024), lds, st, k);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gcn_b16_stack_fwd<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        hipLaunchKernelGGL((k_gcn_b16_stack_fwd<4, 2>), grid, dim3(512), lds, st, k);
-    }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gcn_b16_stack_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    hipLaunchKernelGGL(k_gcn_b16_stack_fwd, dim3(static_cast<unsigned>(ceil_div64(k.B, 4))), dim3(1024), lds, st, k);
 }
 
 extern "C" int recon_gcn_b16_stack_fwd(const recon_gcn_b16_stack_args* a, recon_stream_t stream) {
@@ -1289,14 +1259,7 @@ extern "C" int recon_gcn_b16_stack_fwd(const recon_gcn_b16_stack_args* a, recon_
     const int64_t nki = ((a->in_features > a->hidden ? a->in_features : a->hidden) + 31) / 32;
     const size_t lds = 3ull * kFusedNT * 16 * 64 + static_cast<size_t>(kMaxStack) * kFusedNT * 32 + 4ull * nki * 2048 + 1024;
     if (lds > 160 * 1024) return RECON_ERR_UNSUPPORTED;                 // in_features > 384: layer by layer
-    // column parts per graph: 4 (sixteen waves per CU; nothing but accumulators and fragments lives in registers)
-    const int ns = cfg_int(CFG_GCN_STACK_PARTS, 4) == 2 ? 2 : 4;
-    if (ns == 4) {
-        launch_stack_fwd(k, lds, as_stream(stream));
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gcn_b16_stack_fwd<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        hipLaunchKernelGGL((k_gcn_b16_stack_fwd<2, 1>), dim3(static_cast<unsigned>(ceil_div64(a->B, 4))), dim3(512), lds, as_stream(stream), k);
-    }
+    launch_stack_fwd(k, lds, as_stream(stream));
     RECON_CHECK_LAUNCH();
     return RECON_OK;
 }

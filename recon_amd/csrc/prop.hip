@@ -291,190 +291,6 @@ __global__ void __launch_bounds__(1024) k_propagate_fwd(const PropK p) {
     }
 }
 
-
-// ------------------------------------------------------------------------------- P2 forward on the bf16 matrix cores
-// k_propagate_fwd_x: the same L-hop propagation with every fp32 operand split into three bfloat16 terms ON THE FLY and six term
-// products accumulated in fp32 by v_mfma_f32_16x16x32_bf16 (the scheme of gemm_bx3.hip: fp32-class accuracy, no scaling — bfloat16
-// keeps fp32's exponent range — at 2.67x the fp32-MFMA ceiling).  One workgroup = one graph; wave w owns the 16 state rows
-// s = 16 w .. 16 w + 15 of every hop:  Hnew^T [S x C] = A_l [S x S] . H^T [S x C],  M = s, N = channel, K = t.
-//   * A_l is read exactly ONCE from HBM: each lane fetches its own MFMA A-fragment (row s = lane & 15, 8 consecutive t) as two
-//     float4 and splits it in registers; a hop's rows are requested while the previous hop computes;
-//   * the state lives in LDS as three bf16 planes [3][channel][t] (k-contiguous: B fragments are ds_read_b128), split once per
-//     hop when it is written, reconstructed exactly (8 + 8 + 8 mantissa bits) for the head (.) tail gather;
-//   * two barriers per hop (all reads of H^l-1 done -> write H^l -> visible).
-// Opt-in (RECON_PROP_FWD=x), parity-tested like the other forms.  Measured at cfg 3b: 207 us against 167 us for the fp32-MFMA wave
-// form below, although its matrix-pipe time is 31 us against 58: one graph = one workgroup of 9 waves (3/2/2/2 over the SIMDs)
-// with 77 KB of LDS image and 168 registers, so a CU holds a single workgroup, and the waves spend 62 % of their life parked at
-// the two barriers per hop and behind the A loads (PMC: SQ_WAIT_ANY 165 M of 267 M wave cycles, MFMA busy 31 us of 207).  Forcing
-// two workgroups per CU (96 registers) spills 420 bytes per lane: 341 us.
-using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4_t = __attribute__((ext_vector_type(4))) uint32_t;
-
-__device__ __forceinline__ void px_split8(const float (&v)[8], bf16x8_t (&out)[3]) {
-    float r[8];
-    u32x4_t w[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float x0 = q == 0 ? v[2 * j] : r[2 * j], x1 = q == 0 ? v[2 * j + 1] : r[2 * j + 1];
-            const uint32_t b0 = __builtin_bit_cast(uint16_t, static_cast<__bf16>(x0)), b1 = __builtin_bit_cast(uint16_t, static_cast<__bf16>(x1));
-            w[q][j] = b0 | (b1 << 16);
-            if (q < 2) { r[2 * j] = x0 - __builtin_bit_cast(float, b0 << 16); r[2 * j + 1] = x1 - __builtin_bit_cast(float, b1 << 16); }
-        }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) out[q] = __builtin_bit_cast(bf16x8_t, w[q]);
-}
-
-// NTC = channel tiles of 16 (C <= 16 NTC), KS = K steps of 32 (S <= 32 KS); blockDim.x = 64 * ceil(S / 16).
-// LDS image of the state: [plane 3][K step KS][channel 16 NTC][64 bytes = 32 t], the 16-byte slot of t group kq rotated by
-// 2 (channel >> 3) — the B image of gemm_bx3.hip, conflict free for the ds_read_b128 fragment reads.
-template <int NTC, int KS>
-__global__ void __launch_bounds__(128 * KS, 2) k_propagate_fwd_x(const PropK p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char xl[];
-    constexpr int STEP = NTC * 16 * 64;                               // bytes of one K step of one plane
-    constexpr int PLANE = KS * STEP;
-    const int tid = threadIdx.x, lane = tid & 63, nthreads = blockDim.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.x, S = p.S, C = p.C;
-    const int li = lane & 15, lq = lane >> 4;
-    auto state_off = [](int c, int t) { return (t >> 5) * STEP + c * 64 + ((((t >> 3) + 2 * (c >> 3)) & 3) << 4) + 2 * (t & 7); };
-    auto store_state = [&](int c, int t0, const float (&v)[4]) {      // 4 consecutive t (t0 % 4 == 0) of channel c -> the three planes
-        float r[4] = {v[0], v[1], v[2], v[3]};
-        const int off = state_off(c, t0);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            uint32_t w[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t b0 = __builtin_bit_cast(uint16_t, static_cast<__bf16>(r[2 * h])), b1 = __builtin_bit_cast(uint16_t, static_cast<__bf16>(r[2 * h + 1]));
-                w[h] = b0 | (b1 << 16);
-                r[2 * h] -= __builtin_bit_cast(float, b0 << 16); r[2 * h + 1] -= __builtin_bit_cast(float, b1 << 16);
-            }
-            *reinterpret_cast<uint2*>(xl + q * PLANE + off) = make_uint2(w[0], w[1]);
-        }
-    };
-    auto state_at = [&](int c, int t) {                               // exact fp32 value of H[c][t]: 8 + 8 + 8 mantissa bits
-        const int off = state_off(c, t);
-        float v = 0.f;
-#pragma unroll
-        for (int q = 2; q >= 0; --q) v += __builtin_bit_cast(float, static_cast<uint32_t>(*reinterpret_cast<const uint16_t*>(xl + q * PLANE + off)) << 16);
-        return v;
-    };
-    // ---- h^0 -> planes (zero padded to 16 NTC channels x 32 KS columns)
-    for (int idx = tid; idx < NTC * 16 * KS * 8; idx += nthreads) {
-        const int c = idx / (KS * 8), t0 = 4 * (idx % (KS * 8));
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (c < C && t0 + e < S) ? p.h0[b * p.h0_bs + static_cast<int64_t>(c) * S + t0 + e] : 0.f;
-        store_state(c, t0, v);
-    }
-    // ---- this wave's rows of A_l: fragment (row 16 w + li, columns 32 ks + 8 lq .. + 7) as two float4, two K steps ahead of the MFMAs
-    const int row = 16 * wave + li;
-    const bool row_ok = row < S;
-    const bool vec = (S & 3) == 0;
-    const int64_t arow = (static_cast<int64_t>(b) * S + (row_ok ? row : 0)) * S;
-    auto load_a = [&](float (&dst)[8], int l, int ks) {
-        const float* A = p.adj[l] + arow;
-        const int t0 = 32 * ks + 8 * lq;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int t = t0 + 4 * h;
-            if (vec) {                                                // S % 4 == 0: a quad is inside the row or outside it
-                const float4 q4 = *reinterpret_cast<const float4*>(A + (t < S ? t : 0));
-                dst[4 * h] = q4.x; dst[4 * h + 1] = q4.y; dst[4 * h + 2] = q4.z; dst[4 * h + 3] = q4.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) dst[4 * h + e] = A[t + e < S ? t + e : 0];
-            }
-        }
-    };
-    // gather indices of this thread's first GI output items: the same in every hop, so their (dependent, int64) loads leave the loop
-    constexpr int GI = 3;
-    int g_hi[GI], g_ti[GI];
-#pragma unroll
-    for (int i = 0; i < GI; ++i) {
-        const int idx = min(tid + i * nthreads, C * p.dd - 1);
-        const int64_t io = b * p.idx_bs + idx;
-        g_hi[i] = static_cast<int>(p.head[io]); g_ti[i] = static_cast<int>(p.tail[io]);
-    }
-    constexpr int PFD = KS >= 2 ? 2 : 1;                               // K steps in flight
-    float araw[PFD][8];
-#pragma unroll
-    for (int i = 0; i < PFD; ++i) load_a(araw[i], 0, i);
-    __syncthreads();
-    constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};      // small terms first
-    const int b_rd = li * 64 + (((lq + 2 * (li >> 3)) & 3) << 4);     // + 1024 j (the rotation depends on channel & 8 only) + STEP ks
-    for (int l = 0; l < p.L; ++l) {
-        f32x4 acc[NTC];
-#pragma unroll
-        for (int j = 0; j < NTC; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            float av[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) av[e] = (row_ok && 32 * ks + 8 * lq + e < S) ? araw[ks % PFD][e] : 0.f;      // rows / columns past S: zero
-            // refill the slot just consumed with the step PFD ahead (the next hop's first steps at the end of this one)
-            if (ks + PFD < KS) load_a(araw[ks % PFD], l, ks + PFD);
-            else if (l + 1 < p.L) load_a(araw[ks % PFD], l + 1, ks % PFD);        // step n of a hop always lives in slot n % PFD
-            bf16x8_t a[3];
-            px_split8(av, a);
-            // channel tiles in pairs: two independent accumulator chains of six products each
-#pragma unroll
-            for (int j = 0; j < NTC; j += 2) {
-                bf16x8_t bfr[2][3];
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj)
-                    if (j + jj < NTC)
-#pragma unroll
-                        for (int q = 0; q < 3; ++q)
-                            bfr[jj][q] = *reinterpret_cast<const bf16x8_t*>(xl + q * PLANE + ks * STEP + 1024 * (j + jj) + b_rd);
-#pragma unroll
-                for (int t = 0; t < 6; ++t)
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj)
-                        if (j + jj < NTC) acc[j + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[TA[t]], bfr[jj][TB[t]], acc[j + jj], 0, 0, 0);
-            }
-        }
-        __syncthreads();                                              // every wave has read H^l-1
-        // C layout: column (lane & 15) = channel 16 j + li, rows 4 lq + r = state index s = 16 w + 4 lq + r
-        float* hs = p.hsave ? p.hsave + ((static_cast<int64_t>(l) * p.B + b) * C) * S : nullptr;
-        const int s0 = 16 * wave + 4 * lq;
-#pragma unroll
-        for (int j = 0; j < NTC; ++j) {
-            const int c = 16 * j + li;
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = (s0 + r < S) ? act_fwd(acc[j][r], p.act) : 0.f;
-            store_state(c, s0, v);                                    // s0 < 16 ceil(S/16) <= 32 KS: inside the padded image
-            if (hs && c < C) {
-                if (vec && s0 + 3 < S) *reinterpret_cast<float4*>(hs + static_cast<int64_t>(c) * S + s0) = make_float4(v[0], v[1], v[2], v[3]);
-                else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (s0 + r < S) hs[static_cast<int64_t>(c) * S + s0 + r] = v[r];
-                }
-            }
-        }
-        __syncthreads();                                              // H^l complete
-        // relation_l = heads * tails   (models/models.py:270-273); the first GI items of a thread use the indices fetched before the hop loop
-#pragma unroll
-        for (int i = 0; i < GI; ++i) {
-            const int idx = tid + i * nthreads;
-            if (idx < C * p.dd) {
-                const int c = idx / p.dd, x = idx % p.dd;
-                p.out[(static_cast<int64_t>(b) * C + c) * (p.L * p.dd) + l * p.dd + x] = state_at(c, g_hi[i]) * state_at(c, g_ti[i]);
-            }
-        }
-        for (int idx = tid + GI * nthreads; idx < C * p.dd; idx += nthreads) {
-            const int c = idx / p.dd, x = idx % p.dd;
-            const int64_t io = b * p.idx_bs + static_cast<int64_t>(c) * p.dd + x;
-            const int hi = static_cast<int>(p.head[io]), ti = static_cast<int>(p.tail[io]);
-            p.out[(static_cast<int64_t>(b) * C + c) * (p.L * p.dd) + l * p.dd + x] = state_at(c, hi) * state_at(c, ti);
-        }
-        // the next hop's first barrier orders these reads before its writes
-    }
-}
-
 // ------------------------------------------------------------------------------- P2 forward, wave-independent form
 // Channels never mix, so ONE WAVE owns 16 channels of one graph for all L hops and needs no workgroup barrier:
 // its state H^T [16][S] lives in REGISTERS as MFMA A-fragments (NT float4 per lane), every hop streams the whole
@@ -563,125 +379,6 @@ __global__ void __launch_bounds__(256) k_propagate_fwd_w(const PropK p) {
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);                          // scratch reads done before the next hop overwrites it
         __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// ------------------------------------------------------------------------------- P2 forward, staged form
-// One workgroup = ONE graph, one wave per 16 channels (state in registers as MFMA A-fragments, as in the wave form), but
-// A_l is no longer fetched fragment by fragment (16 rows x 64 bytes per instruction, once per wave: PMC showed the texture
-// path 59 % busy and 49 % L2 hits).  It is streamed ONCE per graph through a ring of three LDS slabs of 16 rows (= one
-// column tile of the output) by the LDS-DMA path in full 1 KiB pieces; all waves read their B fragments from the slab.
-// Raw s_barrier + counted vmcnt keep two slabs in flight across each barrier.  Slab rows are 16 bytes longer than S
-// floats, which puts the 16 rows of a ds_read_b128 on distinct bank groups and keeps the image lane-linear (37 slots of
-// 16 bytes per row at S = 144; the extra slot is filled with a don't-care load).  Needs S % 16 == 0.
-template <int NT>
-__global__ void __launch_bounds__(1024) k_propagate_fwd_s(const PropK p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int S = p.S, pitch = p.pitch;                              // pitch = S + 4 floats
-    const int rowb = (S + 4) * 4, slots_per_row = (S + 4) / 4;       // slab row in bytes / in 16-byte slots
-    const int slab_bytes = 16 * rowb, slab_slots = 16 * slots_per_row;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nw = blockDim.x >> 6;                                  // = channel groups of the graph
-    const int b = blockIdx.x, m = wave;
-    unsigned char* ring = smem;                                      // [3][16][rowb]
-    float* scr = reinterpret_cast<float*>(smem + 3 * slab_bytes) + static_cast<int64_t>(wave) * 16 * pitch;
-    const int li = lane & 15, lq = lane >> 4;
-    const int cmine = 16 * m + li;
-    const int ndma = (slab_slots + 63) / 64;                         // DMA instructions per slab (10 at S = 144)
-    const int my_dma = (ndma - wave + nw - 1) / nw;                  // this wave's share: instructions wave, wave + nw, ...
-    const int steps = p.L * NT;
-
-    float af[NT][4];
-#pragma unroll
-    for (int s = 0; s < NT; ++s) {
-        const int k = 16 * s + 4 * lq;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) af[s][t] = (cmine < p.C) ? p.h0[b * p.h0_bs + static_cast<int64_t>(cmine) * S + k + t] : 0.f;
-    }
-    // slab g = rows 16 (g % NT) .. +15 of A_{g / NT}
-    auto dma_slab = [&](int g) {
-        const float* A = p.adj[g / NT] + static_cast<int64_t>(b) * S * S + static_cast<int64_t>(16 * (g % NT)) * S;
-        unsigned char* dst = ring + (g % 3) * slab_bytes;
-        for (int i = wave; i < ndma; i += nw) {
-            const int slot = 64 * i + lane;
-            if (slot < slab_slots) {
-                const int row = slot / slots_per_row, sl = slot % slots_per_row;
-                const float* src = A + static_cast<int64_t>(row) * S + 4 * (sl < S / 4 ? sl : 0);      // last slot of a row: padding
-                // issued as inline asm: through the builtin the compiler knows an LDS-DMA is in flight and waits vmcnt(0) before
-                // the next ds_read of the ring (it cannot tell the slots apart), which would serialise the whole pipeline.
-                // Hidden from its counters the DMA only makes the compiler's own vmcnt waits more conservative (in-order
-                // completion); the waits that matter for the ring are the explicit ones below.
-                const uint32_t lds_addr = __builtin_amdgcn_readfirstlane(
-                    static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) void*)(dst + 1024 * i))));
-                // m0 is saved and restored inside the one asm block (listing it as a clobber is undefined behaviour for a reserved register:
-                // the compiler keeps its own LDS base there for its own LDS-DMA / GWS uses)
-                uint32_t m0_saved;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(m0_saved) : "v"(src), "s"(lds_addr) : "memory");
-            }
-        }
-    };
-    // the h0 loads must be complete BEFORE the loop: otherwise their s_waitcnt vmcnt(0) sits at the first MFMA inside the loop
-    // body, where it would drain the DMA pipeline in every iteration
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-    dma_slab(0);
-    if (steps > 1) dma_slab(1);
-    f32x4 acc0, acc1;
-    for (int g = 0; g < steps; ++g) {
-        const int nt = g % NT, l = g / NT;
-        // this wave's pieces of slab g have landed (the pieces of slab g+1 may still fly), then everybody's have
-        if (g + 1 < steps) {
-            if (my_dma >= 3) __builtin_amdgcn_s_waitcnt(0x0f70 | 0);            // conservative for unusual shapes: vmcnt(0)
-            else if (my_dma == 2) __builtin_amdgcn_s_waitcnt(0x0f70 | 2);       // vmcnt(2)
-            else if (my_dma == 1) __builtin_amdgcn_s_waitcnt(0x0f70 | 1);
-            else __builtin_amdgcn_s_waitcnt(0x0f70 | 0);
-        } else {
-            __builtin_amdgcn_s_waitcnt(0x0f70 | 0);
-        }
-        __builtin_amdgcn_s_barrier();
-        if (g + 2 < steps) dma_slab(g + 2);                          // its ring slot was last read in step g-1: everyone is past that
-        const unsigned char* slab = ring + (g % 3) * slab_bytes + li * rowb + lq * 16;
-        acc0 = f32x4{0.f, 0.f, 0.f, 0.f}; acc1 = acc0;
-        float4 bq[NT];
-#pragma unroll
-        for (int s = 0; s < NT; ++s) bq[s] = *reinterpret_cast<const float4*>(slab + 64 * s);
-#pragma unroll
-        for (int s = 0; s < NT; ++s) {
-            f32x4& a = (s & 1) ? acc1 : acc0;
-            a = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s][0], bq[s].x, a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s][1], bq[s].y, a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s][2], bq[s].z, a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s][3], bq[s].w, a, 0, 0, 0);
-        }
-        // C layout: col (s) = lane&15, row (channel) = (lane>>4)*4 + r
-#pragma unroll
-        for (int r = 0; r < 4; ++r) scr[(4 * lq + r) * pitch + 16 * nt + li] = act_fwd(acc0[r] + acc1[r], p.act);
-        if (nt == NT - 1) {                                          // hop finished: wave-private epilogue, as in the wave form
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int s = 0; s < NT; ++s) {
-                const float4 v = *reinterpret_cast<const float4*>(scr + li * pitch + 16 * s + 4 * lq);
-                af[s][0] = v.x; af[s][1] = v.y; af[s][2] = v.z; af[s][3] = v.w;
-            }
-            for (int idx = lane; idx < 16 * p.dd; idx += 64) {       // relation_l = gather(h, heads) * gather(h, tails)
-                const int cl = idx / p.dd, x = idx % p.dd;
-                const int c = 16 * m + cl;
-                if (c < p.C) {
-                    const int64_t io = b * p.idx_bs + static_cast<int64_t>(c) * p.dd + x;
-                    const int hi = static_cast<int>(p.head[io]), ti = static_cast<int>(p.tail[io]);
-                    p.out[(static_cast<int64_t>(b) * p.C + c) * (p.L * p.dd) + l * p.dd + x] = scr[cl * pitch + hi] * scr[cl * pitch + ti];
-                }
-            }
-            if (p.hsave) {
-                float* hs = p.hsave + ((static_cast<int64_t>(l) * p.B + b) * p.C) * S;
-                for (int cl = 0; cl < 16 && 16 * m + cl < p.C; ++cl)
-                    for (int sidx = lane; sidx < S; sidx += 64) hs[static_cast<int64_t>(16 * m + cl) * S + sidx] = scr[cl * pitch + sidx];
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_wave_barrier();
-        }
     }
 }
 
@@ -951,6 +648,11 @@ extern "C" int recon_start_entity_embeddings_bwd(const float* grad_out, const in
     return RECON_OK;
 }
 
+static bool prop_h_form_env() {
+    const char* form = cfg(CFG_PROP_FWD);
+    return !form || form[0] == 'h' || form[0] == '\0';
+}
+
 #define RECON_DISPATCH_MT(MTV, V4, KERNEL, ...)                                                                        \
     do {                                                                                                                \
         switch (MTV) {                                                                                                  \
@@ -984,41 +686,13 @@ extern "C" int recon_propagate_fwd(const recon_prop_args* a, recon_stream_t stre
     p.stats = a->h_saved ? a->stats : nullptr;
     p.ws = a->split_ws; p.ws_bytes = a->split_ws_bytes;
     hipStream_t st = as_stream(stream);
+    // default: two-term half operands on the f16 matrix cores (prop_h.hip) wherever that form exists; RECON_PROP_FWD = w | b selects
+    // one of the fp32 MFMA forms below (per wave / per workgroup), h forces the default
+    if (prop_h_form_env() && prop_fwd_h_supported(p)) return prop_fwd_h(p, st);
+    if (prop_h_form_env() && prop_fwd_hl_supported(p)) return prop_fwd_hl(p, st);     // wide states, given a workspace
+    if (blk) return RECON_ERR_UNSUPPORTED;                              // the other forms need a materialised adjacency
     const int NTn = g.Sp / 16;
-    const int mtn_s = (a->C + 15) / 16;
-    {
-        // default: two-term half operands on the f16 matrix cores (prop_h.hip) wherever that form exists; RECON_PROP_FWD = w | b | s | x
-        // selects one of the forms below (fp32 MFMA per wave / per workgroup / staged, bf16 x 3), h forces the default
-        const char* form = cfg(CFG_PROP_FWD);
-        if ((!form || form[0] == 'h' || form[0] == '\0') && prop_fwd_h_supported(p)) return prop_fwd_h(p, st);
-        if ((!form || form[0] == 'h' || form[0] == '\0') && prop_fwd_hl_supported(p)) return prop_fwd_hl(p, st);     // wide states, given a workspace
-        if (blk) return RECON_ERR_UNSUPPORTED;                          // the other forms need a materialised adjacency
-        const int ntc = (a->C + 15) / 16, ks = (a->S + 31) / 32, mw = (a->S + 15) / 16;
-        if (form && form[0] == 'x' && ntc <= 8 && ks <= 4 && mw <= 16) {     // S <= 128: wider states spill in this form             // bf16 x 3 on the bf16 matrix cores: opt-in (see the kernel's header)
-            const size_t xlds = 3ull * ks * ntc * 16 * 64;
-            bool launched = true;
-#define CALL_X(N_, K_) do { if (xlds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_propagate_fwd_x<N_, K_>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(xlds)); \
-                            hipLaunchKernelGGL((k_propagate_fwd_x<N_, K_>), dim3(static_cast<unsigned>(a->B)), dim3(64 * mw), xlds, st, p); } while (0)
-#define CALL_XK(N_) switch (ks) { case 1: CALL_X(N_, 1); break; case 2: CALL_X(N_, 2); break; case 3: CALL_X(N_, 3); break; default: CALL_X(N_, 4); break; }
-            switch (ntc) { case 1: CALL_XK(1); break; case 2: CALL_XK(2); break; case 3: CALL_XK(3); break; case 4: CALL_XK(4); break; case 5: CALL_XK(5); break;
-                           case 6: CALL_XK(6); break; case 7: CALL_XK(7); break; case 8: CALL_XK(8); break; default: launched = false; break; }
-#undef CALL_XK
-#undef CALL_X
-            if (launched) { RECON_CHECK_LAUNCH(); return RECON_OK; }
-        }
-    }
-    if (NTn <= 9 && (a->S % 16) == 0 && v4 && mtn_s <= 16 && g.pitch == a->S + 4 && cfg_char(CFG_PROP_FWD) == 's') {   // staged form
-        const size_t slds = 3ull * 16 * (a->S + 4) * sizeof(float) + static_cast<size_t>(mtn_s) * 16 * g.pitch * sizeof(float);
-#define CALL_S(N_) do { if (slds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_propagate_fwd_s<N_>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(slds)); \
-                        hipLaunchKernelGGL((k_propagate_fwd_s<N_>), dim3(static_cast<unsigned>(a->B)), dim3(64 * mtn_s), slds, st, p); } while (0)
-        switch (NTn) { case 1: CALL_S(1); break; case 2: CALL_S(2); break; case 3: CALL_S(3); break; case 4: CALL_S(4); break;
-                       case 5: CALL_S(5); break; case 6: CALL_S(6); break; case 7: CALL_S(7); break; case 8: CALL_S(8); break;
-                       default: CALL_S(9); break; }
-#undef CALL_S
-        RECON_CHECK_LAUNCH();
-        return RECON_OK;
-    }
-    if (NTn <= 9 && cfg_char(CFG_PROP_FWD) != 'b') {      // wave-independent form (RECON_PROP_FWD=w, or shapes the bf16 form does not take)
+    if (NTn <= 9 && cfg_char(CFG_PROP_FWD) != 'b') {      // wave-independent form (RECON_PROP_FWD=w, or shapes the f16 forms do not take)
         const int64_t units = 1LL * a->B * ((a->C + 15) / 16);
         dim3 wgrid(static_cast<unsigned>(ceil_div64(units, 4)));
         const size_t wlds = 4ull * 16 * g.pitch * sizeof(float);
@@ -1044,11 +718,6 @@ extern "C" int recon_propagate_fwd(const recon_prop_args* a, recon_stream_t stre
     RECON_DISPATCH_MT(g.MT, v4, k_propagate_fwd, grid, dim3(64 * g.fwd_waves), g.fwd_lds, st, p);
     RECON_CHECK_LAUNCH();
     return RECON_OK;
-}
-
-static bool prop_h_form_env() {
-    const char* form = cfg(CFG_PROP_FWD);
-    return !form || form[0] == 'h' || form[0] == '\0';
 }
 
 extern "C" size_t recon_propagate_ws_bytes(const recon_prop_args* a) {

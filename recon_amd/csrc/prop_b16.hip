@@ -1079,13 +1079,10 @@ int launch_bgemm_cfg(BGemmB16 g, hipStream_t st) {
 }
 
 // Tile shapes: a whole graph of <= 9 nodes per workgroup (144 x 144, 9 waves); 256 x 256 with 8 waves of 128 x 64 otherwise (the copies come
-// from L2 at ~30 TB/s chip-wide: bytes per flop halve against 128 x 128, measured 657 -> 495 TF/s the other way); RECON_BGEMM_CFG=a: 128 x 128.
+// from L2 at ~30 TB/s chip-wide: bytes per flop halve against 128 x 128, measured 657 -> 495 TF/s the other way).
 template <bool PK, bool QK, int EPI, bool PBLK>
 int launch_bgemm(const BGemmB16& g, hipStream_t st) {
     if (g.M <= 144 && g.N <= 144) return launch_bgemm_cfg<PK, QK, EPI, PBLK, 3, 3, 3, 3, 3>(g, st);
-    const char tile = cfg_char(CFG_BGEMM_CFG);
-    if (tile == 'a') return launch_bgemm_cfg<PK, QK, EPI, PBLK, 2, 2, 4, 4, 3>(g, st);
-    if (tile == 'h') return launch_bgemm_cfg<PK, QK, EPI, PBLK, 1, 4, 8, 4, 3>(g, st);
     return launch_bgemm_cfg<PK, QK, EPI, PBLK, 2, 4, 8, 4, 3>(g, st);
 }
 

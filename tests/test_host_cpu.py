@@ -339,6 +339,27 @@ def test_propagation_workspace_queries():
     assert L.recon_propagate_bwd_ws_floats(C.byref(args(7, 72, 144, 3, 16))) == 0
 
 
+
+def test_config_table_refuses_retired_switches():
+    """recon_config_set refuses names that are not in the library's switch table, the switches of retired kernel forms among them, and
+    takes every name the table (csrc/config.hip) holds."""
+    from recon_amd import _lib
+    src = open(os.path.join(ROOT, "recon_amd", "csrc", "config.hip")).read()
+    table = re.search(r"kNames\[CFG_COUNT\]\s*=\s*\{(.*?)\};", src, flags=re.S).group(1)
+    names = re.findall(r'"(RECON_[A-Z0-9_]+)"', table)
+    assert len(names) >= 10 and "RECON_PROP_FWD" in names
+    for retired in ("RECON_BGEMM_CFG", "RECON_GCN_STACK_GPW", "RECON_GCN_STACK_PARTS", "RECON_GCN_FUSED_PARTS"):
+        assert retired not in names
+        with pytest.raises(RuntimeError):
+            _lib.config_set(retired, "1")
+        assert _lib.lib().recon_config_get(retired.encode()) is None
+    for name in names:
+        prev = _lib.config_set(name, "7")
+        try:
+            assert _lib.lib().recon_config_get(name.encode()) == b"7"
+        finally:
+            _lib.config_set(name, prev)
+
 def test_trust_marks_carry_version_and_bound():
     """graph.trust(): a mark is honoured only while the tensor is unmodified and only by a consumer whose table is at least as large as
     the bound the values were validated against (advisor, round 3: a permanent object tag let an edited tensor, or a smaller entity table,

@@ -1,11 +1,9 @@
 #!/usr/bin/env python3
-"""Few launches of the n = 32 bf16 propagation forward (batched GEMM form) for rocprofv3 --pmc runs: python3 tools/b16_pmc.py [cfg]"""
+"""Few launches of the n = 32 bf16 propagation forward (batched GEMM form) for rocprofv3 --pmc runs: python3 tools/b16_pmc.py"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from recon_amd.propagation import propagate, get_head_indices, get_tail_indices
-if len(sys.argv) > 1:
-    os.environ["RECON_BGEMM_CFG"] = sys.argv[1]
 dv = torch.device("cuda:0")
 n, d, L, B = 32, 8, 3, 1024
 C, S = n * (n - 1), 16 * n
