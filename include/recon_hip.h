@@ -824,6 +824,48 @@ int recon_convkb_scores(int32_t slot, int64_t Q, const int64_t* triples, const f
                         int64_t n_rel, int32_t D, const float* b1, const float* w2, const float* b2, float slope, int64_t c0, int64_t C, float* S,
                         int64_t ldS, recon_stream_t stream);
 
+/* --------------------------------------------------------------------------------------------
+ * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
+ *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
+ * ------------------------------------------------------------------------------------------*/
+/* Filtered corruption: the negative half of Corpus.get_iteration_batch (GAT/create_batch.py:103-260) and get_iteration_triples_batch
+ * (:262-351) for B positives and ratio r >= 0.  Writes indices int64 [B (2 r + 1)][3] and out_values [B (2 r + 1)]: rows 0..B are the
+ * positives; row B + c starts as a copy of positive c mod B (np.tile, :126-129) and replaces the head for c in [0, B (r/2)) (:131-141), the
+ * tail for c in [B (r/2), 2 B (r/2)) (:143-155), the relation for c in [B r, 2 B r) (:157-174); for odd r the rows c in [2 B (r/2), B r)
+ * stay copies.  A replaced row has value -1.  Entity draws are uniform over [0, n_ent), redrawn while (h, r, t) is known; a row still known
+ * after 65 536 draws stays a copy with the positive's value and adds 1 to *capped (device, never reset by the library).  Relation draws:
+ * at most n_rel membership checks, then the row keeps the positive's relation and value (:163-174).  Known: keys = sorted unique int64
+ * (r n_ent + h) n_ent + t of train + valid + test (valid_triples_dict).  Draw k of row c is a counter-based function of (seed, c, k):
+ * the output is bit-reproducible for a seed.  Positive ids are not range-checked (the caller does it); nothing is read outside keys. */
+int recon_kg_corrupt(const void* positives, int32_t index_bytes, const float* values, int64_t B, int32_t ratio, const int64_t* keys,
+                     int64_t n_keys, int64_t n_ent, int64_t n_rel, uint64_t seed, int64_t* indices, float* out_values,
+                     unsigned long long* capped, recon_stream_t stream);
+/* ConvKB training forward (SpKBGATConvOnly.forward, GAT/models.py:291-296 -> ConvKB.forward, GAT/layers.py:41-46) on M triples, the
+ * tables E [n_ent][D] and Rel [n_rel][D] read in place (no torch.cat): z = [E[h] | Rel[r] | E[t]] W1^T + b1 (W1 [D][3 D]),
+ * scores = leaky(z) . w2 + b2, leaky(x) = max(x, slope x), 0 <= slope <= 1.  1 <= D <= 512 (RECON_ERR_UNSUPPORTED above).  z [M][D]
+ * (optional, NULL: not written) is what recon_convkb_train_bwd needs.  fp32 fma chains, no split precision.  A row with an id outside
+ * its table scores NaN; nothing is read outside a table.
+ * With values [M] (+1 / -1, optional) and ratio >= 1 it also computes main.py:833-840's loss: y = (v + 1) / 2, w = y + (1 - y) / (2 ratio),
+ * loss[0] = mean_m w_m ((1 - y_m) s_m + mx + log(exp(-mx) + exp(-s_m - mx))), mx = max(-s_m, 0) (binary_cross_entropy_with_logits,
+ * weight = w), loss_terms [M] (optional) the weighted terms, g_scores [M] = dloss/ds = w (sigmoid(s) - y) / M.  The mean is a fixed-order
+ * sum.  workspace: recon_convkb_train_fwd_workspace_floats(M, D) floats, zero-filled before its first use; only needed with values.
+ * One launch. */
+size_t recon_convkb_train_fwd_workspace_floats(int64_t M, int32_t D);
+int recon_convkb_train_fwd(const void* triples, int32_t index_bytes, int64_t M, const float* E, const float* Rel, int64_t n_ent, int64_t n_rel,
+                           int32_t D, const float* W1, const float* b1, const float* w2, const float* b2, float slope, float* z, float* scores,
+                           const float* values, int32_t ratio, float* loss_terms, float* g_scores, float* loss, float* workspace,
+                           size_t workspace_floats, recon_stream_t stream);
+/* ConvKB training backward (loss.backward() of main.py:842 through fc2, nl1 and fc1; the tables are frozen, :741-742): g = g_scores
+ * (* g_scale[0] when g_scale is given), delta = (g w2) * (z > 0 ? 1 : slope), dW1 [D][3 D] = delta^T X with X gathered again, db1 = sum_m
+ * delta, dw2 [D] = sum_m g leaky(z), db2 [1] = sum_m g.  Every sum has one fixed order: the gradients are bitwise identical from run to run.
+ * workspace: recon_convkb_train_bwd_workspace_floats(M, D) floats, zero-filled before its first use.  One launch.
+ * Both workspaces begin with the same 256 arrival counters, which every call leaves at zero: one zero-filled buffer of the largest size
+ * asked for serves every shape, forward and backward alike (not two calls in flight on different streams at once). */
+size_t recon_convkb_train_bwd_workspace_floats(int64_t M, int32_t D);
+int recon_convkb_train_bwd(const void* triples, int32_t index_bytes, int64_t M, const float* E, const float* Rel, int64_t n_ent, int64_t n_rel,
+                           int32_t D, const float* w2, float slope, const float* z, const float* g_scores, const float* g_scale, float* dW1,
+                           float* db1, float* dw2, float* db2, float* workspace, size_t workspace_floats, recon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
