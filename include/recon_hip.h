@@ -825,6 +825,39 @@ int recon_convkb_scores(int32_t slot, int64_t Q, const int64_t* triples, const f
                         int64_t ldS, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * E3  link-prediction evaluation of the GAT_sep_space ConvKB scorer (csrc/kg_sep.hip, csrc/kg_eval.hip): SpKBGATConvOnly.batch_test
+ *     (GAT_sep_space/models.py:316-339) carries both entities into the triple's relation space, e' = tanh(E[e] W_ent2rel[r]), before ConvKB.
+ *     Corpus.get_validation_cnfmat (GAT_sep_space/create_batch.py:1360-1390) scores every test triple with every relation through it, 100
+ *     rows and a [100, D, D] gather of W_ent2rel per call; get_validation_pred (:905-1199) cannot run it (batch_test takes model_gat).
+ *     With W1 = [W_h | W_r | W_t] the entity tables of E1 become per relation: P_h^r = tanh(E W_ent2rel[r]) W_h^T, P_t^r = tanh(E W_ent2rel[r])
+ *     W_t^T; P_r = Rel W_r^T is E1's.  A chunk of Rc relations rel_ids (int64, device) has tables P_h, P_t [Rc][n][D] (local relation rl at
+ *     offset rl n D), and every score is E1's routine on the tables of the query's relation: bit-identical to recon_convkb_rank /
+ *     recon_convkb_scores run on ONE relation's tables.
+ * ------------------------------------------------------------------------------------------*/
+/* The tables of a relation chunk (the tanh(bmm(e, W_ent2rel[r])) of :316-320 and the entity part of fc1, GAT_sep_space/layers.py ConvKB):
+ * row m of local relation rl is built from E[ids[m]] (ids int64 [U], device; NULL: row m of E, U <= n_rows).  E [n_rows][D], W_ent2rel
+ * [n_rel][D][D] laid out [in][out] (x . W), W1 = fc1.weight [D][3 D] read in place.  1 <= D <= 512, Rc <= 65535.  Exact fp32 products
+ * (v_mfma_f32_16x16x4_f32), tanh in fp32; tanh(E_tile W_r) stays in LDS.  A relation id outside [0, n_rel) gives NaN tables; an entity id
+ * outside [0, n_rows) gives the row of a zero entity.  No atomics: bitwise identical from run to run.  One launch. */
+int recon_kgsep_tables(const float* E, int64_t n_rows, const int64_t* ids, int64_t U, const float* W_ent2rel, int64_t n_rel, const int64_t* rel_ids,
+                       int32_t Rc, const float* W1, int32_t D, float* P_h, float* P_t, recon_stream_t stream);
+/* Filtered (or raw) head or tail ranks (slot RECON_KGE_HEAD / RECON_KGE_TAIL) of queries sorted by relation, on one chunk's tables
+ * (n_ent = rows per relation): the queries of local relation rl are triples[seg[rl] .. seg[rl + 1]) (seg int64 [Rc + 1], device,
+ * non-decreasing, seg[0] = 0, seg[Rc] = Q), their relation column is rel_ids[rl] (it indexes P_r).  Ranks, true scores, the filter and the
+ * workspace (recon_convkb_rank_workspace_floats(Q, D) floats) as recon_convkb_rank, with the same tie rule and integer count.  64-query tiles
+ * never cross a relation; two launches per chunk and side, none per relation, no host read. */
+int recon_kgsep_rank(int32_t slot, int64_t Q, const int64_t* triples, const int64_t* seg, int32_t Rc, const float* P_h, const float* P_r,
+                     const float* P_t, int64_t n_ent, int64_t n_rel, int32_t D, const float* b1, const float* w2, const float* b2, float slope,
+                     const int64_t* filt_ids, const int64_t* filt_begin, const int64_t* filt_end, float* workspace, size_t workspace_floats,
+                     int64_t* ranks, float* true_scores, recon_stream_t stream);
+/* Relation scores of the sep scorer, the `scores` of :1360-1390 laid out [Q][n_rel] (before its view(-1, num_rels)): S[q][rel_ids[rl]] = the
+ * score of triple q with relation rel_ids[rl], its head and tail rows (triples' columns 0 and 2, rows of the chunk's tables) read from local
+ * relation rl's tables; u = (P_h^r' + P_t^r') + b1, candidate P_r[r'].  Other columns of S are not written; ldS >= n_rel. */
+int recon_kgsep_scores(int64_t Q, const int64_t* triples, const int64_t* rel_ids, int32_t Rc, const float* P_h, const float* P_r, const float* P_t,
+                       int64_t n_ent, int64_t n_rel, int32_t D, const float* b1, const float* w2, const float* b2, float slope, float* S, int64_t ldS,
+                       recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
  *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
  * ------------------------------------------------------------------------------------------*/

@@ -245,6 +245,12 @@ SYMBOLS = [
                                     C.c_float, c_i64p, c_i64p, c_i64p, c_f32p, C.c_size_t, c_i64p, c_f32p, C.c_void_p]),
     ("recon_convkb_scores", C.c_int, [C.c_int32, C.c_int64, c_i64p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int32, c_f32p, c_f32p, c_f32p,
                                       C.c_float, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_void_p]),
+    ("recon_kgsep_tables", C.c_int, [c_f32p, C.c_int64, c_i64p, C.c_int64, c_f32p, C.c_int64, c_i64p, C.c_int32, c_f32p, C.c_int32, c_f32p, c_f32p,
+                                     C.c_void_p]),
+    ("recon_kgsep_rank", C.c_int, [C.c_int32, C.c_int64, c_i64p, c_i64p, C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int32, c_f32p,
+                                   c_f32p, c_f32p, C.c_float, c_i64p, c_i64p, c_i64p, c_f32p, C.c_size_t, c_i64p, c_f32p, C.c_void_p]),
+    ("recon_kgsep_scores", C.c_int, [C.c_int64, c_i64p, c_i64p, C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int32, c_f32p, c_f32p,
+                                     c_f32p, C.c_float, c_f32p, C.c_int64, C.c_void_p]),
     ("recon_kg_corrupt", C.c_int, [C.c_void_p, C.c_int32, c_f32p, C.c_int64, C.c_int32, c_i64p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64,
                                    c_i64p, c_f32p, C.c_void_p, C.c_void_p]),
     ("recon_convkb_train_fwd_workspace_floats", C.c_size_t, [C.c_int64, C.c_int32]),

@@ -24,6 +24,13 @@
 //                   32-wide d chunks staged in LDS; every thread scores a 4 x 4 (query, candidate) block; the per-query counts are summed
 //                   over the workgroup and added to rank[q] with one integer atomic (order-independent: deterministic)
 //   k_kge_dense     S[q, j] = s(q, c0 + j), one thread per score (relation scores, test yardstick)
+//
+// The GAT_sep_space scorer carries both entities into the triple's relation space first, so its entity tables are per
+// relation: P_h^r = tanh(E W_ent2rel[r]) W_h^T, P_t^r likewise with W_t (csrc/kg_sep.hip builds them for a chunk of Rc relations, [Rc][n][D]).
+// The same score routine then runs on the table of the query's relation:
+//   k_kgs_prepare   k_kge_prepare on queries sorted by relation; seg [Rc + 1] delimits each local relation's queries
+//   k_kgs_count     k_kge_count on 64-query tiles that never cross a relation, each streaming ITS relation's candidate table
+//   k_kgs_dense     S[q][rel_ids[rl]] = the relation-slot score on local relation rl's tables
 #include "recon_common.h"
 
 #pragma clang fp contract(off)
@@ -197,6 +204,179 @@ __global__ void __launch_bounds__(256) k_kge_dense(const KgeArgs a, int64_t c0, 
     S[q * ldS + j] = s;
 }
 
+// ---- relation-segmented passes of the GAT_sep_space scorer ----
+// kge_prepare_query and kge_count_tiles are the bodies of k_kge_prepare and k_kge_count, statement for statement, except that the entity
+// tables are offset to the query's relation (ent_off, Pc) and the count loop ends its query range at q_end where k_kge_count reads a.Q.  The
+// section-10 kernels keep their own copies so that their code stays as it was; the tests check that both give the same bits.
+//
+// kge_query on the entity tables of one relation: P[0] and P[2] are [Rc][n_ent][D] and ent_off = rl n_ent D selects local relation rl
+__device__ __forceinline__ bool kgs_query(const KgeArgs& a, int64_t q, int64_t ent_off, const float*& pa, const float*& pb, int64_t& true_id) {
+    int ca, cb;
+    kge_fixed(a.slot, ca, cb);
+    const int64_t ia = a.tri[3 * q + ca], ib = a.tri[3 * q + cb];
+    true_id = a.tri[3 * q + a.slot];
+    if (ia < 0 || ia >= a.n[ca] || ib < 0 || ib >= a.n[cb] || true_id < 0 || true_id >= a.n[a.slot]) return false;
+    pa = a.P[ca] + (ca == 1 ? 0 : ent_off) + ia * a.D;
+    pb = a.P[cb] + (cb == 1 ? 0 : ent_off) + ib * a.D;
+    return true;
+}
+
+// one query of the prepare pass (head or tail slot): u[q] to the workspace, s*[q], and the filter correction in rank[q]
+__device__ __forceinline__ void kge_prepare_query(const KgeArgs& a, int64_t q, int64_t ent_off, const int64_t* __restrict__ filt_ids,
+                                                  const int64_t* __restrict__ filt_begin, const int64_t* __restrict__ filt_end, float* __restrict__ U,
+                                                  int64_t* __restrict__ rank, float* __restrict__ true_score) {
+    const int lane = threadIdx.x;
+    const float* pa; const float* pb; int64_t tid;
+    float* uq = U + q * a.D;
+    if (!kgs_query(a, q, ent_off, pa, pb, tid)) {                         // bad id: rank 0, s* NaN (the count pass then adds nothing)
+        for (int d = lane; d < a.D; d += kWave) uq[d] = 0.f;
+        if (lane == 0) { rank[q] = 0; true_score[q] = __builtin_nanf(""); }
+        return;
+    }
+    for (int d = lane; d < a.D; d += kWave) uq[d] = kge_u(pa, pb, a.b1, d);
+    const float b2 = a.b2[0];
+    const float* Pc = a.P[a.slot] + ent_off;
+    const int64_t nc = a.n[a.slot];
+    const float s_true = kge_score(a, pa, pb, Pc + tid * a.D, b2);
+    int cnt = 0;
+    if (filt_ids) {
+        const int64_t e = filt_end[q];
+        for (int64_t k = filt_begin[q] + lane; k < e; k += kWave) {
+            const int64_t c = filt_ids[k];
+            if (c >= 0 && c < nc && kge_score(a, pa, pb, Pc + c * a.D, b2) > s_true) ++cnt;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane == 0) { rank[q] = 1 - cnt; true_score[q] = s_true; }
+}
+
+// the main loop of the count pass: queries [q0, q0 + 64) below q_end (their u rows in U) against the candidate
+// tiles [t_begin, t_end) of Pc [nc][D]; each query's count of candidates scoring above its s* is added to rank[q]
+__device__ __forceinline__ void kge_count_tiles(const KgeArgs& a, float (*us)[kDKP], float (*ps)[kDKP], float* ws, const float* __restrict__ U,
+                                                const float* __restrict__ true_score, int64_t* __restrict__ rank, int64_t q0, int64_t q_end,
+                                                const float* __restrict__ Pc, int64_t nc, int64_t t_begin, int64_t t_end) {
+    const int tq = threadIdx.x / 16, tc = threadIdx.x % 16;              // queries tq + 16 i, candidates tc + 16 j of the tile
+    const int D = a.D;
+    const float b2 = a.b2[0];
+    float s_true[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int64_t q = q0 + tq + 16 * i;
+        s_true[i] = q < q_end ? true_score[q] : __builtin_nanf("");       // padding queries: NaN, nothing compares above it
+    }
+    int cnt[4] = {0, 0, 0, 0};
+    for (int64_t tile = t_begin; tile < t_end; ++tile) {
+        const int64_t c0 = tile * kCT;
+        float acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+        for (int d0 = 0; d0 < D; d0 += kDK) {
+            __syncthreads();                                              // the previous chunk's readers are done
+            kge_stage(us, U, q0, q_end, D, d0);
+            kge_stage(ps, Pc, c0, nc, D, d0);
+            if (threadIdx.x < kDK) ws[threadIdx.x] = d0 + static_cast<int>(threadIdx.x) < D ? a.w2[d0 + threadIdx.x] : 0.f;
+            __syncthreads();
+            for (int dd = 0; dd < kDK; dd += 4) {
+                float4 u4[4], p4[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) u4[i] = *reinterpret_cast<const float4*>(&us[tq + 16 * i][dd]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) p4[j] = *reinterpret_cast<const float4*>(&ps[tc + 16 * j][dd]);
+                const float4 w4 = *reinterpret_cast<const float4*>(&ws[dd]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        // u + p and slope (u + p) for d pairs as packed fp32 ops (per lane IEEE: the values kge_term computes)
+                        const f32x2 x0 = f32x2{u4[i].x, u4[i].y} + f32x2{p4[j].x, p4[j].y}, x1 = f32x2{u4[i].z, u4[i].w} + f32x2{p4[j].z, p4[j].w};
+                        const f32x2 m0 = x0 * a.slope, m1 = x1 * a.slope;
+                        float v = acc[i][j];
+                        v = fmaf(w4.x, fmaxf(x0.x, m0.x), v);
+                        v = fmaf(w4.y, fmaxf(x0.y, m0.y), v);
+                        v = fmaf(w4.z, fmaxf(x1.x, m1.x), v);
+                        v = fmaf(w4.w, fmaxf(x1.y, m1.y), v);
+                        acc[i][j] = v;
+                    }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (c0 + tc + 16 * j < nc)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) cnt[i] += (acc[i][j] + b2) > s_true[i];
+    }
+    // sum over the 16 threads of a query row (lanes tc = 0..15 of one 16-lane group), one atomic per query and workgroup
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int c = cnt[i];
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) c += __shfl_xor(c, o, 16);
+        const int64_t q = q0 + tq + 16 * i;
+        if (tc == 0 && q < q_end && c != 0) atomicAdd(reinterpret_cast<unsigned long long*>(rank + q), static_cast<unsigned long long>(c));
+    }
+}
+
+// the local relation of query q: seg[j] <= q < seg[j + 1] (seg non-decreasing, seg[0] = 0, seg[Rc] = Q; any seg stays inside [0, Rc))
+__device__ __forceinline__ int kgs_segment(const int64_t* __restrict__ seg, int Rc, int64_t q) {
+    int lo = 0, hi = Rc;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        if (seg[mid] <= q) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(64) k_kgs_prepare(const KgeArgs a, const int64_t* __restrict__ seg, int Rc, const int64_t* __restrict__ filt_ids,
+                                                    const int64_t* __restrict__ filt_begin, const int64_t* __restrict__ filt_end, float* __restrict__ U,
+                                                    int64_t* __restrict__ rank, float* __restrict__ true_score) {
+    const int64_t q = blockIdx.x;
+    const int64_t ent_off = static_cast<int64_t>(kgs_segment(seg, Rc, q)) * a.n[0] * a.D;
+    kge_prepare_query(a, q, ent_off, filt_ids, filt_begin, filt_end, U, rank, true_score);
+}
+
+// grid.x: the bound ceil(Q / 64) + Rc on the number of 64-query tiles that never cross a relation; a workgroup finds its tile by walking the
+// segments (Rc is a few dozen) and leaves when it has none
+__global__ void __launch_bounds__(kCountThreads) k_kgs_count(const KgeArgs a, const int64_t* __restrict__ seg, int Rc, const float* __restrict__ U,
+                                                             const float* __restrict__ true_score, int64_t* __restrict__ rank, int64_t tiles_per_split) {
+    __shared__ float us[kQT][kDKP], ps[kCT][kDKP], ws[kDK];
+    __shared__ int64_t tile[3];                                           // local relation, first query, end of the relation's queries
+    if (threadIdx.x == 0) {
+        int64_t b = blockIdx.x, rl = -1, q0 = 0, q_end = 0;
+        for (int j = 0; j < Rc; ++j) {
+            const int64_t s0 = seg[j], s1 = seg[j + 1], nt = s1 > s0 ? (s1 - s0 + kQT - 1) / kQT : 0;
+            if (b < nt) { rl = j; q0 = s0 + b * kQT; q_end = s1; break; }
+            b -= nt;
+        }
+        if (q0 < 0 || q_end > a.Q) rl = -1;                               // a malformed seg reads nothing outside the workspace
+        tile[0] = rl; tile[1] = q0; tile[2] = q_end;
+    }
+    __syncthreads();
+    const int64_t rl = tile[0], q0 = tile[1], q_end = tile[2];
+    if (rl < 0) return;
+    const int64_t nc = a.n[a.slot];
+    const int64_t n_tiles = (nc + kCT - 1) / kCT;
+    const int64_t t_begin = static_cast<int64_t>(blockIdx.y) * tiles_per_split;
+    const int64_t t_end = t_begin + tiles_per_split < n_tiles ? t_begin + tiles_per_split : n_tiles;
+    kge_count_tiles(a, us, ps, ws, U, true_score, rank, q0, q_end, a.P[a.slot] + rl * nc * a.D, nc, t_begin, t_end);
+}
+
+// S[q][rel_ids[rl]] = s(q with relation rel_ids[rl]) on local relation rl's entity tables: one thread per (query, local relation)
+__global__ void __launch_bounds__(256) k_kgs_dense(const KgeArgs a, const int64_t* __restrict__ rel_ids, int Rc, float* __restrict__ S, int64_t ldS) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= a.Q * Rc) return;
+    const int64_t q = i / Rc;
+    const int rl = static_cast<int>(i % Rc);
+    const int64_t c = rel_ids[rl];
+    if (c < 0 || c >= ldS) return;
+    const float* pa; const float* pb; int64_t tid;
+    float s = __builtin_nanf("");
+    if (kgs_query(a, q, static_cast<int64_t>(rl) * a.n[0] * a.D, pa, pb, tid) && c < a.n[1]) s = kge_score(a, pa, pb, a.P[1] + c * a.D, a.b2[0]);
+    S[q * ldS + c] = s;
+}
+
 int kge_args(KgeArgs& a, int32_t slot, int64_t Q, const int64_t* triples, const float* P_h, const float* P_r, const float* P_t, int64_t n_ent,
              int64_t n_rel, int32_t D, const float* b1, const float* w2, const float* b2, float slope) {
     if (slot < 0 || slot > 2 || Q < 0 || D < 1 || n_ent < 1 || n_rel < 1) return RECON_ERR_INVALID;
@@ -256,5 +436,47 @@ extern "C" int recon_convkb_scores(int32_t slot, int64_t Q, const int64_t* tripl
     if (Q > 65535) return RECON_ERR_UNSUPPORTED;                          // grid.y: the caller chunks the queries
     hipLaunchKernelGGL(recon::k_kge_dense, dim3(static_cast<unsigned>(ceil_div64(C, 256)), static_cast<unsigned>(Q)), dim3(256), 0, as_stream(stream),
                        a, c0, C, S, ldS);
+    return hipGetLastError() == hipSuccess ? RECON_OK : RECON_ERR_LAUNCH;
+}
+
+extern "C" int recon_kgsep_rank(int32_t slot, int64_t Q, const int64_t* triples, const int64_t* seg, int32_t Rc, const float* P_h, const float* P_r,
+                                const float* P_t, int64_t n_ent, int64_t n_rel, int32_t D, const float* b1, const float* w2, const float* b2, float slope,
+                                const int64_t* filt_ids, const int64_t* filt_begin, const int64_t* filt_end, float* workspace, size_t workspace_floats,
+                                int64_t* ranks, float* true_scores, recon_stream_t stream) {
+    recon::KgeArgs a;
+    const int st = recon::kge_args(a, slot, Q, triples, P_h, P_r, P_t, n_ent, n_rel, D, b1, w2, b2, slope);
+    if (st != RECON_OK) return st;
+    if (slot == RECON_KGE_RELATION || Rc < 1 || !seg || (filt_ids && (!filt_begin || !filt_end))) return RECON_ERR_INVALID;
+    if (Q == 0) return RECON_OK;
+    if (!ranks || !true_scores || !workspace) return RECON_ERR_INVALID;
+    if (workspace_floats < recon_convkb_rank_workspace_floats(Q, D)) return RECON_ERR_WORKSPACE;
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(recon::k_kgs_prepare, dim3(static_cast<unsigned>(Q)), dim3(recon::kWave), 0, s, a, seg, Rc, filt_ids, filt_begin, filt_end,
+                       workspace, ranks, true_scores);
+    RECON_CHECK_LAUNCH();
+    // the candidate split of recon_convkb_rank, on the tile bound
+    const int64_t q_tiles = ceil_div64(Q, recon::kQT) + Rc, c_tiles = ceil_div64(n_ent, recon::kCT);
+    if (q_tiles > 0x7fffffffLL) return RECON_ERR_UNSUPPORTED;
+    int64_t splits = ceil_div64(2048, q_tiles);
+    if (splits > c_tiles) splits = c_tiles;
+    const int64_t per = ceil_div64(c_tiles, splits);
+    splits = ceil_div64(c_tiles, per);
+    hipLaunchKernelGGL(recon::k_kgs_count, dim3(static_cast<unsigned>(q_tiles), static_cast<unsigned>(splits)), dim3(recon::kCountThreads), 0, s, a,
+                       seg, Rc, workspace, true_scores, ranks, per);
+    return hipGetLastError() == hipSuccess ? RECON_OK : RECON_ERR_LAUNCH;
+}
+
+extern "C" int recon_kgsep_scores(int64_t Q, const int64_t* triples, const int64_t* rel_ids, int32_t Rc, const float* P_h, const float* P_r,
+                                  const float* P_t, int64_t n_ent, int64_t n_rel, int32_t D, const float* b1, const float* w2, const float* b2, float slope,
+                                  float* S, int64_t ldS, recon_stream_t stream) {
+    recon::KgeArgs a;
+    const int st = recon::kge_args(a, RECON_KGE_RELATION, Q, triples, P_h, P_r, P_t, n_ent, n_rel, D, b1, w2, b2, slope);
+    if (st != RECON_OK) return st;
+    if (Rc < 1 || !rel_ids || ldS < n_rel) return RECON_ERR_INVALID;
+    if (Q == 0) return RECON_OK;
+    if (!S) return RECON_ERR_INVALID;
+    const int64_t blocks = ceil_div64(Q * Rc, 256);
+    if (blocks > 0x7fffffffLL) return RECON_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(recon::k_kgs_dense, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, as_stream(stream), a, rel_ids, Rc, S, ldS);
     return hipGetLastError() == hipSuccess ? RECON_OK : RECON_ERR_LAUNCH;
 }

@@ -5,6 +5,10 @@ of a triple's relation before the translation loss (`tanh(e W_r)`, GAT_sep_space
 (recon_amd/models.py); a checkpoint written by GAT_sep_space/main.py loads with strict=True.
 
     from recon_amd.sep_space import SpKBGATModified          # instead of `from models import SpKBGATModified` in GAT_sep_space/main.py
+
+Stage B of that tree, `SpKBGATConvOnly` (GAT_sep_space/models.py:247-339), scores a triple after carrying both entities into its relation's
+space; its forward / batch_test take model_gat for W_ent2rel.  The class below keeps that interface and the state_dict, and its `evaluate`
+and `relation_scores` run on the device (recon_amd.kg_sep).
 """
 import torch
 import torch.nn as nn
@@ -29,6 +33,50 @@ class SpKBGATModified(_models.SpKBGATModified):
         without the [T, D, D] gather the reference materialises (160 KB per triple at D = 200): rows are walked in relation order, rows of
         one relation share the passes over its matrix (csrc/rel_mm.hip: one launch forward, two backward, no host read)."""
         return self.nonlinearity_ent2rel(rel_rows_mm(entity_rows, relation_ids, self.W_ent2rel))
+
+
+class SpKBGATConvOnly(_models.SpKBGATConvOnly):
+    """The GAT_sep_space ConvKB scorer (GAT_sep_space/models.py:247-339): the GAT tree's constructor and state_dict keys
+    (final_entity_embeddings, final_relation_embeddings, convKB.*), so `conv/trained_*.pth` of that tree loads with strict=True.
+    forward / batch_test take model_gat — anything with W_ent2rel [R, D, D] (laid out [in][out], x . W) and nonlinearity_ent2rel — and
+    score [e_h' | r | e_t'] with e' = nonlinearity_ent2rel(E[e] . W_ent2rel[r]) through ConvKB in torch; the per-row products run on
+    rel_rows_mm (no [T, D, D] gather) and gradients reach convKB and W_ent2rel as in the reference.
+    Deviation: the reference squeezes the [T, 1, D] products with a bare .squeeze(), so a one-row batch fails in torch.cat; here a one-row
+    batch scores like any other."""
+
+    def _score(self, batch_inputs, model_gat):
+        if not self.final_entity_embeddings.is_cuda or not batch_inputs.is_cuda:
+            raise RuntimeError("recon_amd: SpKBGATConvOnly expects GPU tensors (this package has no CPU path)")
+        W = model_gat.W_ent2rel
+        rel = batch_inputs[:, 1]
+        head = model_gat.nonlinearity_ent2rel(rel_rows_mm(self.final_entity_embeddings[batch_inputs[:, 0], :], rel, W))      # :316-320
+        tail = model_gat.nonlinearity_ent2rel(rel_rows_mm(self.final_entity_embeddings[batch_inputs[:, 2], :], rel, W))
+        return self.convKB(torch.cat((head, self.final_relation_embeddings[rel], tail), dim=1))
+
+    def forward(self, Corpus_, adj, batch_inputs, model_gat):
+        return self._score(batch_inputs, model_gat)
+
+    def batch_test(self, batch_inputs, model_gat):
+        return self._score(batch_inputs, model_gat)
+
+    def _scorer(self, model_gat):
+        from . import kg_sep
+        return kg_sep.sep_scorer(self.final_entity_embeddings, self.final_relation_embeddings, self.convKB, model_gat)
+
+    def evaluate(self, model_gat, test_triples, known_triples, unique_entities=None):
+        """Filtered head and tail ranking of test_triples against known_triples (train + valid + test: valid_triples_dict), the metrics
+        Corpus.get_validation_pred prints (GAT_sep_space/create_batch.py:905-1199) for this scorer: kg_eval.link_prediction_metrics' dict."""
+        from . import kg_eval, kg_sep
+        with torch.no_grad():
+            rh, rt, _ = kg_sep.rank_entities(self._scorer(model_gat), test_triples, known_triples, unique_entities=unique_entities)
+        return kg_eval.link_prediction_metrics(rh, rt)
+
+    def relation_scores(self, model_gat, test_triples):
+        """[Q, R]: every test triple scored with every relation, the `scores` of get_validation_cnfmat (GAT_sep_space/create_batch.py:1360-1390)
+        before its view(-1, num_rels)."""
+        from . import kg_sep
+        with torch.no_grad():
+            return kg_sep.relation_scores(self._scorer(model_gat), test_triples)
 
 
 class _RelRowsMM(torch.autograd.Function):
