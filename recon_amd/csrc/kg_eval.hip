@@ -31,6 +31,8 @@
 //   k_kgs_prepare   k_kge_prepare on queries sorted by relation; seg [Rc + 1] delimits each local relation's queries
 //   k_kgs_count     k_kge_count on 64-query tiles that never cross a relation, each streaming ITS relation's candidate table
 //   k_kgs_dense     S[q][rel_ids[rl]] = the relation-slot score on local relation rl's tables
+// Both kernel pairs share the id check (kge_query), the prepare body (kge_prepare_query) and the count loop (kge_count_tiles); the flat
+// kernels pass entity-table offset 0, the segmented ones the offset of the query's relation.
 #include "recon_common.h"
 
 #pragma clang fp contract(off)
@@ -61,156 +63,9 @@ __device__ __forceinline__ void kge_fixed(int slot, int& ca, int& cb) {
     cb = slot == 2 ? 1 : 2;
 }
 
-// u rows of query q (pa, pb) and the candidate table; false when an id of q is outside its table
-__device__ __forceinline__ bool kge_query(const KgeArgs& a, int64_t q, const float*& pa, const float*& pb, int64_t& true_id) {
-    int ca, cb;
-    kge_fixed(a.slot, ca, cb);
-    const int64_t ia = a.tri[3 * q + ca], ib = a.tri[3 * q + cb];
-    true_id = a.tri[3 * q + a.slot];
-    if (ia < 0 || ia >= a.n[ca] || ib < 0 || ib >= a.n[cb] || true_id < 0 || true_id >= a.n[a.slot]) return false;
-    pa = a.P[ca] + ia * a.D;
-    pb = a.P[cb] + ib * a.D;
-    return true;
-}
-
-// the score routine (see the header comment): u computed on the fly, bit-identical to the workspace copy k_kge_prepare writes
-__device__ float kge_score(const KgeArgs& a, const float* pa, const float* pb, const float* pc, float b2) {
-    float acc = 0.f;
-    for (int d = 0; d < a.D; ++d) acc = kge_term(acc, kge_u(pa, pb, a.b1, d), pc[d], a.w2[d], a.slope);
-    return acc + b2;
-}
-
-__global__ void __launch_bounds__(64) k_kge_prepare(const KgeArgs a, const int64_t* __restrict__ filt_ids, const int64_t* __restrict__ filt_begin,
-                                                    const int64_t* __restrict__ filt_end, float* __restrict__ U, int64_t* __restrict__ rank,
-                                                    float* __restrict__ true_score) {
-    const int64_t q = blockIdx.x;
-    const int lane = threadIdx.x;
-    const float* pa; const float* pb; int64_t tid;
-    float* uq = U + q * a.D;
-    if (!kge_query(a, q, pa, pb, tid)) {                                  // bad id: rank 0, s* NaN (k_kge_count then adds nothing)
-        for (int d = lane; d < a.D; d += kWave) uq[d] = 0.f;
-        if (lane == 0) { rank[q] = 0; true_score[q] = __builtin_nanf(""); }
-        return;
-    }
-    for (int d = lane; d < a.D; d += kWave) uq[d] = kge_u(pa, pb, a.b1, d);
-    const float b2 = a.b2[0];
-    const float* Pc = a.P[a.slot];
-    const int64_t nc = a.n[a.slot];
-    const float s_true = kge_score(a, pa, pb, Pc + tid * a.D, b2);
-    int cnt = 0;
-    if (filt_ids) {
-        const int64_t e = filt_end[q];
-        for (int64_t k = filt_begin[q] + lane; k < e; k += kWave) {
-            const int64_t c = filt_ids[k];
-            if (c >= 0 && c < nc && kge_score(a, pa, pb, Pc + c * a.D, b2) > s_true) ++cnt;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
-    if (lane == 0) { rank[q] = 1 - cnt; true_score[q] = s_true; }
-}
-
-// stage rows [r0, r0 + 64) x [d0, d0 + 32) of a [rows, D] table into LDS (zeros outside): thread t moves column t % 32 of rows t / 32 + 8 k
-__device__ __forceinline__ void kge_stage(float (*dst)[kDKP], const float* __restrict__ src, int64_t r0, int64_t rows, int D, int d0) {
-    constexpr int kStep = kCountThreads / kDK;
-    const int r = threadIdx.x / kDK, c = threadIdx.x % kDK;
-    const int64_t row = r0 + r;
-    const bool col_ok = d0 + c < D;
-    const float* p = src + row * D + d0 + c;
-    const int64_t step = static_cast<int64_t>(kStep) * D;
-#pragma unroll
-    for (int k = 0; k < kQT / kStep; ++k) dst[r + kStep * k][c] = (col_ok && row + kStep * k < rows) ? p[k * step] : 0.f;
-}
-
-__global__ void __launch_bounds__(kCountThreads) k_kge_count(const KgeArgs a, const float* __restrict__ U, const float* __restrict__ true_score,
-                                                             int64_t* __restrict__ rank, int64_t tiles_per_split) {
-    __shared__ float us[kQT][kDKP], ps[kCT][kDKP], ws[kDK];
-    const int tq = threadIdx.x / 16, tc = threadIdx.x % 16;              // queries tq + 16 i, candidates tc + 16 j of the tile
-    const int64_t q0 = static_cast<int64_t>(blockIdx.x) * kQT;
-    const float* Pc = a.P[a.slot];
-    const int64_t nc = a.n[a.slot];
-    const int D = a.D;
-    const float b2 = a.b2[0];
-    float s_true[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int64_t q = q0 + tq + 16 * i;
-        s_true[i] = q < a.Q ? true_score[q] : __builtin_nanf("");         // padding queries: NaN, nothing compares above it
-    }
-    int cnt[4] = {0, 0, 0, 0};
-    const int64_t n_tiles = (nc + kCT - 1) / kCT;
-    const int64_t t_begin = static_cast<int64_t>(blockIdx.y) * tiles_per_split;
-    const int64_t t_end = t_begin + tiles_per_split < n_tiles ? t_begin + tiles_per_split : n_tiles;
-    for (int64_t tile = t_begin; tile < t_end; ++tile) {
-        const int64_t c0 = tile * kCT;
-        float acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-        for (int d0 = 0; d0 < D; d0 += kDK) {
-            __syncthreads();                                              // the previous chunk's readers are done
-            kge_stage(us, U, q0, a.Q, D, d0);
-            kge_stage(ps, Pc, c0, nc, D, d0);
-            if (threadIdx.x < kDK) ws[threadIdx.x] = d0 + static_cast<int>(threadIdx.x) < D ? a.w2[d0 + threadIdx.x] : 0.f;
-            __syncthreads();
-            for (int dd = 0; dd < kDK; dd += 4) {
-                float4 u4[4], p4[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) u4[i] = *reinterpret_cast<const float4*>(&us[tq + 16 * i][dd]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) p4[j] = *reinterpret_cast<const float4*>(&ps[tc + 16 * j][dd]);
-                const float4 w4 = *reinterpret_cast<const float4*>(&ws[dd]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        // u + p and slope (u + p) for d pairs as packed fp32 ops (per lane IEEE: the values kge_term computes)
-                        const f32x2 x0 = f32x2{u4[i].x, u4[i].y} + f32x2{p4[j].x, p4[j].y}, x1 = f32x2{u4[i].z, u4[i].w} + f32x2{p4[j].z, p4[j].w};
-                        const f32x2 m0 = x0 * a.slope, m1 = x1 * a.slope;
-                        float v = acc[i][j];
-                        v = fmaf(w4.x, fmaxf(x0.x, m0.x), v);
-                        v = fmaf(w4.y, fmaxf(x0.y, m0.y), v);
-                        v = fmaf(w4.z, fmaxf(x1.x, m1.x), v);
-                        v = fmaf(w4.w, fmaxf(x1.y, m1.y), v);
-                        acc[i][j] = v;
-                    }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (c0 + tc + 16 * j < nc)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) cnt[i] += (acc[i][j] + b2) > s_true[i];
-    }
-    // sum over the 16 threads of a query row (lanes tc = 0..15 of one 16-lane group), one atomic per query and workgroup
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int c = cnt[i];
-#pragma unroll
-        for (int o = 8; o >= 1; o >>= 1) c += __shfl_xor(c, o, 16);
-        const int64_t q = q0 + tq + 16 * i;
-        if (tc == 0 && q < a.Q && c != 0) atomicAdd(reinterpret_cast<unsigned long long*>(rank + q), static_cast<unsigned long long>(c));
-    }
-}
-
-__global__ void __launch_bounds__(256) k_kge_dense(const KgeArgs a, int64_t c0, int64_t C, float* __restrict__ S, int64_t ldS) {
-    const int64_t j = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x, q = blockIdx.y;
-    if (j >= C) return;
-    const float* pa; const float* pb; int64_t tid;
-    const int64_t c = c0 + j;
-    float s = __builtin_nanf("");
-    if (kge_query(a, q, pa, pb, tid) && c >= 0 && c < a.n[a.slot]) s = kge_score(a, pa, pb, a.P[a.slot] + c * a.D, a.b2[0]);
-    S[q * ldS + j] = s;
-}
-
-// ---- relation-segmented passes of the GAT_sep_space scorer (DESIGN.md section 12) ----
-// kge_prepare_query and kge_count_tiles are the bodies of k_kge_prepare and k_kge_count, statement for statement, except that the entity
-// tables are offset to the query's relation (ent_off, Pc) and the count loop ends its query range at q_end where k_kge_count reads a.Q.  The
-// section-10 kernels keep their own copies so that their code stays as it was; the tests check that both give the same bits.
-//
-// kge_query on the entity tables of one relation: P[0] and P[2] are [Rc][n_ent][D] and ent_off = rl n_ent D selects local relation rl
-__device__ __forceinline__ bool kgs_query(const KgeArgs& a, int64_t q, int64_t ent_off, const float*& pa, const float*& pb, int64_t& true_id) {
+// u rows of query q (pa, pb) and its true id; false when an id of q is outside its table.  ent_off offsets the entity tables P[0] and P[2]:
+// 0 for the flat tables, rl n_ent D for local relation rl of per-relation tables [Rc][n_ent][D]
+__device__ __forceinline__ bool kge_query(const KgeArgs& a, int64_t q, int64_t ent_off, const float*& pa, const float*& pb, int64_t& true_id) {
     int ca, cb;
     kge_fixed(a.slot, ca, cb);
     const int64_t ia = a.tri[3 * q + ca], ib = a.tri[3 * q + cb];
@@ -221,6 +76,13 @@ __device__ __forceinline__ bool kgs_query(const KgeArgs& a, int64_t q, int64_t e
     return true;
 }
 
+// the score routine (see the header comment): u computed on the fly, bit-identical to the workspace copy k_kge_prepare writes
+__device__ float kge_score(const KgeArgs& a, const float* pa, const float* pb, const float* pc, float b2) {
+    float acc = 0.f;
+    for (int d = 0; d < a.D; ++d) acc = kge_term(acc, kge_u(pa, pb, a.b1, d), pc[d], a.w2[d], a.slope);
+    return acc + b2;
+}
+
 // one query of the prepare pass (head or tail slot): u[q] to the workspace, s*[q], and the filter correction in rank[q]
 __device__ __forceinline__ void kge_prepare_query(const KgeArgs& a, int64_t q, int64_t ent_off, const int64_t* __restrict__ filt_ids,
                                                   const int64_t* __restrict__ filt_begin, const int64_t* __restrict__ filt_end, float* __restrict__ U,
@@ -228,7 +90,7 @@ __device__ __forceinline__ void kge_prepare_query(const KgeArgs& a, int64_t q, i
     const int lane = threadIdx.x;
     const float* pa; const float* pb; int64_t tid;
     float* uq = U + q * a.D;
-    if (!kgs_query(a, q, ent_off, pa, pb, tid)) {                         // bad id: rank 0, s* NaN (the count pass then adds nothing)
+    if (!kge_query(a, q, ent_off, pa, pb, tid)) {                         // bad id: rank 0, s* NaN (the count pass then adds nothing)
         for (int d = lane; d < a.D; d += kWave) uq[d] = 0.f;
         if (lane == 0) { rank[q] = 0; true_score[q] = __builtin_nanf(""); }
         return;
@@ -249,6 +111,24 @@ __device__ __forceinline__ void kge_prepare_query(const KgeArgs& a, int64_t q, i
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
     if (lane == 0) { rank[q] = 1 - cnt; true_score[q] = s_true; }
+}
+
+__global__ void __launch_bounds__(64) k_kge_prepare(const KgeArgs a, const int64_t* __restrict__ filt_ids, const int64_t* __restrict__ filt_begin,
+                                                    const int64_t* __restrict__ filt_end, float* __restrict__ U, int64_t* __restrict__ rank,
+                                                    float* __restrict__ true_score) {
+    kge_prepare_query(a, blockIdx.x, 0, filt_ids, filt_begin, filt_end, U, rank, true_score);
+}
+
+// stage rows [r0, r0 + 64) x [d0, d0 + 32) of a [rows, D] table into LDS (zeros outside): thread t moves column t % 32 of rows t / 32 + 8 k
+__device__ __forceinline__ void kge_stage(float (*dst)[kDKP], const float* __restrict__ src, int64_t r0, int64_t rows, int D, int d0) {
+    constexpr int kStep = kCountThreads / kDK;
+    const int r = threadIdx.x / kDK, c = threadIdx.x % kDK;
+    const int64_t row = r0 + r;
+    const bool col_ok = d0 + c < D;
+    const float* p = src + row * D + d0 + c;
+    const int64_t step = static_cast<int64_t>(kStep) * D;
+#pragma unroll
+    for (int k = 0; k < kQT / kStep; ++k) dst[r + kStep * k][c] = (col_ok && row + kStep * k < rows) ? p[k * step] : 0.f;
 }
 
 // the main loop of the count pass: queries [q0, q0 + 64) below q_end (their u rows in U) against the candidate
@@ -319,6 +199,27 @@ __device__ __forceinline__ void kge_count_tiles(const KgeArgs& a, float (*us)[kD
     }
 }
 
+__global__ void __launch_bounds__(kCountThreads) k_kge_count(const KgeArgs a, const float* __restrict__ U, const float* __restrict__ true_score,
+                                                             int64_t* __restrict__ rank, int64_t tiles_per_split) {
+    __shared__ float us[kQT][kDKP], ps[kCT][kDKP], ws[kDK];
+    const int64_t nc = a.n[a.slot];
+    const int64_t n_tiles = (nc + kCT - 1) / kCT;
+    const int64_t t_begin = static_cast<int64_t>(blockIdx.y) * tiles_per_split;
+    const int64_t t_end = t_begin + tiles_per_split < n_tiles ? t_begin + tiles_per_split : n_tiles;
+    kge_count_tiles(a, us, ps, ws, U, true_score, rank, static_cast<int64_t>(blockIdx.x) * kQT, a.Q, a.P[a.slot], nc, t_begin, t_end);
+}
+
+__global__ void __launch_bounds__(256) k_kge_dense(const KgeArgs a, int64_t c0, int64_t C, float* __restrict__ S, int64_t ldS) {
+    const int64_t j = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x, q = blockIdx.y;
+    if (j >= C) return;
+    const float* pa; const float* pb; int64_t tid;
+    const int64_t c = c0 + j;
+    float s = __builtin_nanf("");
+    if (kge_query(a, q, 0, pa, pb, tid) && c >= 0 && c < a.n[a.slot]) s = kge_score(a, pa, pb, a.P[a.slot] + c * a.D, a.b2[0]);
+    S[q * ldS + j] = s;
+}
+
+// ---- relation-segmented passes of the GAT_sep_space scorer (DESIGN.md section 12) ----
 // the local relation of query q: seg[j] <= q < seg[j + 1] (seg non-decreasing, seg[0] = 0, seg[Rc] = Q; any seg stays inside [0, Rc))
 __device__ __forceinline__ int kgs_segment(const int64_t* __restrict__ seg, int Rc, int64_t q) {
     int lo = 0, hi = Rc;
@@ -373,7 +274,7 @@ __global__ void __launch_bounds__(256) k_kgs_dense(const KgeArgs a, const int64_
     if (c < 0 || c >= ldS) return;
     const float* pa; const float* pb; int64_t tid;
     float s = __builtin_nanf("");
-    if (kgs_query(a, q, static_cast<int64_t>(rl) * a.n[0] * a.D, pa, pb, tid) && c < a.n[1]) s = kge_score(a, pa, pb, a.P[1] + c * a.D, a.b2[0]);
+    if (kge_query(a, q, static_cast<int64_t>(rl) * a.n[0] * a.D, pa, pb, tid) && c < a.n[1]) s = kge_score(a, pa, pb, a.P[1] + c * a.D, a.b2[0]);
     S[q * ldS + c] = s;
 }
 
@@ -389,6 +290,17 @@ int kge_args(KgeArgs& a, int32_t slot, int64_t Q, const int64_t* triples, const 
     a.b1 = b1; a.w2 = w2; a.b2 = b2;
     a.Q = Q; a.D = D; a.slot = slot; a.slope = slope;
     return RECON_OK;
+}
+
+// the count pass's grid: q_tiles query tiles (grid.x) times a split of the nc candidates (grid.y) such that about 2048 workgroups (8 per CU)
+// are in flight; per: candidate tiles per split
+dim3 kge_count_grid(int64_t q_tiles, int64_t nc, int64_t& per) {
+    const int64_t c_tiles = ceil_div64(nc, kCT);
+    int64_t splits = ceil_div64(2048, q_tiles);
+    if (splits > c_tiles) splits = c_tiles;
+    per = ceil_div64(c_tiles, splits);
+    splits = ceil_div64(c_tiles, per);
+    return dim3(static_cast<unsigned>(q_tiles), static_cast<unsigned>(splits));
 }
 
 }  // namespace
@@ -413,14 +325,9 @@ extern "C" int recon_convkb_rank(int32_t slot, int64_t Q, const int64_t* triples
     hipLaunchKernelGGL(recon::k_kge_prepare, dim3(static_cast<unsigned>(Q)), dim3(recon::kWave), 0, s, a, filt_ids, filt_begin, filt_end, workspace,
                        ranks, true_scores);
     RECON_CHECK_LAUNCH();
-    // candidate range split so that about 2048 workgroups (8 per CU) are in flight
-    const int64_t q_tiles = ceil_div64(Q, recon::kQT), c_tiles = ceil_div64(a.n[slot], recon::kCT);
-    int64_t splits = ceil_div64(2048, q_tiles);
-    if (splits > c_tiles) splits = c_tiles;
-    const int64_t per = ceil_div64(c_tiles, splits);
-    splits = ceil_div64(c_tiles, per);
-    hipLaunchKernelGGL(recon::k_kge_count, dim3(static_cast<unsigned>(q_tiles), static_cast<unsigned>(splits)), dim3(recon::kCountThreads), 0, s, a,
-                       workspace, true_scores, ranks, per);
+    int64_t per;
+    const dim3 grid = recon::kge_count_grid(ceil_div64(Q, recon::kQT), a.n[slot], per);
+    hipLaunchKernelGGL(recon::k_kge_count, grid, dim3(recon::kCountThreads), 0, s, a, workspace, true_scores, ranks, per);
     return hipGetLastError() == hipSuccess ? RECON_OK : RECON_ERR_LAUNCH;
 }
 
@@ -454,15 +361,11 @@ extern "C" int recon_kgsep_rank(int32_t slot, int64_t Q, const int64_t* triples,
     hipLaunchKernelGGL(recon::k_kgs_prepare, dim3(static_cast<unsigned>(Q)), dim3(recon::kWave), 0, s, a, seg, Rc, filt_ids, filt_begin, filt_end,
                        workspace, ranks, true_scores);
     RECON_CHECK_LAUNCH();
-    // the candidate split of recon_convkb_rank, on the tile bound
-    const int64_t q_tiles = ceil_div64(Q, recon::kQT) + Rc, c_tiles = ceil_div64(n_ent, recon::kCT);
+    const int64_t q_tiles = ceil_div64(Q, recon::kQT) + Rc;              // the tile bound of k_kgs_count
     if (q_tiles > 0x7fffffffLL) return RECON_ERR_UNSUPPORTED;
-    int64_t splits = ceil_div64(2048, q_tiles);
-    if (splits > c_tiles) splits = c_tiles;
-    const int64_t per = ceil_div64(c_tiles, splits);
-    splits = ceil_div64(c_tiles, per);
-    hipLaunchKernelGGL(recon::k_kgs_count, dim3(static_cast<unsigned>(q_tiles), static_cast<unsigned>(splits)), dim3(recon::kCountThreads), 0, s, a,
-                       seg, Rc, workspace, true_scores, ranks, per);
+    int64_t per;
+    const dim3 grid = recon::kge_count_grid(q_tiles, n_ent, per);
+    hipLaunchKernelGGL(recon::k_kgs_count, grid, dim3(recon::kCountThreads), 0, s, a, seg, Rc, workspace, true_scores, ranks, per);
     return hipGetLastError() == hipSuccess ? RECON_OK : RECON_ERR_LAUNCH;
 }
 

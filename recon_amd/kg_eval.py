@@ -25,45 +25,63 @@ ConvKBProjections = namedtuple("ConvKBProjections", "P_h P_r P_t b1 w2 b2 slope 
 def _require_gpu(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
-            raise RuntimeError("recon_amd.kg_eval: expected a GPU tensor (this package has no CPU path)")
+            raise RuntimeError("recon_amd: expected a GPU tensor (this package has no CPU path)")
+
+
+def _check_ids(triples, n_ent, n_rel, name):
+    """One device reduction and one host sync: every id of the [rows, 3] triples inside its table."""
+    if triples.numel():
+        lo, hi = triples.amin(0).tolist(), triples.amax(0).tolist()
+        if min(lo) < 0 or hi[0] >= n_ent or hi[2] >= n_ent or hi[1] >= n_rel:
+            raise ValueError("%s: an id lies outside its table (%d entities, %d relations)" % (name, n_ent, n_rel))
+
+
+def _check_triples(triples, table, n_ent, n_rel, name="test_triples"):
+    """The triples as contiguous int64 [Q, 3] on the device of `table` (a GPU tensor), every id inside its table."""
+    _require_gpu(triples, table)
+    if triples.dim() != 2 or triples.shape[1] != 3:
+        raise ValueError("%s: [Q, 3] (head, relation, tail) expected" % name)
+    t = triples.to(device=table.device, dtype=torch.int64).contiguous()
+    _check_ids(t, n_ent, n_rel, name)
+    return t
+
+
+def _check_shapes(entity_emb, relation_emb, convkb, who):
+    """D of entity [N, D] and relation [R, D] tables scored by a ConvKB module with fc1 [D, 3D] and fc2 [1, D]; ValueError otherwise."""
+    if entity_emb.dim() != 2 or relation_emb.dim() != 2 or relation_emb.shape[1] != entity_emb.shape[1]:
+        raise ValueError("%s: entity [N, D] and relation [R, D] tables expected" % who)
+    D = entity_emb.shape[1]
+    if tuple(convkb.fc1.weight.shape) != (D, 3 * D) or tuple(convkb.fc2.weight.shape) != (1, D):
+        raise ValueError("%s: fc1 [D, 3D], fc2 [1, D] expected" % who)
+    return D
+
+
+def _detached_weights(convkb):
+    """fc1.weight, b1, w2 (flat) and b2 ([1]) of a ConvKB module as detached contiguous fp32 tensors, and the slope of its LeakyReLU nl1."""
+    return (convkb.fc1.weight.detach().float().contiguous(), convkb.fc1.bias.detach().float().contiguous(),
+            convkb.fc2.weight.detach().float().reshape(-1).contiguous(), convkb.fc2.bias.detach().float().reshape(1).contiguous(),
+            float(convkb.nl1.negative_slope))
+
+
+def _project(T, W1, k):
+    """T W_k^T, fp32 [rows of T, D], with W_k block k of W1 = [W_h | W_r | W_t] (recon_sgemm_ex on the strided slice)."""
+    n, D = T.shape
+    P = torch.empty(n, D, device=T.device, dtype=torch.float32)
+    with _lib.on_device(T.device):
+        _lib.check(_lib.lib().recon_sgemm_ex(n, D, D, T.data_ptr(), D, 0, W1.data_ptr() + 4 * k * D, 3 * D, 1, P.data_ptr(), D, None,
+                                             _lib.current_stream()), "recon_sgemm_ex")
+    return P
 
 
 def convkb_projections(entity_emb, relation_emb, convkb):
     """P_h = E W_h^T, P_r = Rel W_r^T, P_t = E W_t^T with fc1.weight = [W_h | W_r | W_t] (each [D, D], read in place: ldb = 3 D), plus b1, w2,
     b2 (device) and the LeakyReLU slope of convkb.nl1 (nn.LeakyReLU(): 0.01, whatever alpha_conv says — GAT/layers.py:24)."""
-    W1, b1 = convkb.fc1.weight, convkb.fc1.bias
-    w2, b2 = convkb.fc2.weight, convkb.fc2.bias
-    _require_gpu(entity_emb, relation_emb, W1, b1, w2, b2)
+    _require_gpu(entity_emb, relation_emb, convkb.fc1.weight, convkb.fc1.bias, convkb.fc2.weight, convkb.fc2.bias)
+    D = _check_shapes(entity_emb, relation_emb, convkb, "convkb_projections")
     E = entity_emb.detach().float().contiguous()
     R = relation_emb.detach().float().contiguous()
-    D = E.shape[1]
-    if E.dim() != 2 or R.dim() != 2 or R.shape[1] != D or tuple(W1.shape) != (D, 3 * D) or tuple(w2.shape) != (1, D):
-        raise ValueError("convkb_projections: entity [N, D], relation [R, D], fc1 [D, 3D], fc2 [1, D] expected")
-    W1 = W1.detach().float().contiguous()
-    L = _lib.lib()
-    stream = _lib.current_stream()
-    out = []
-    for k, T in ((0, E), (1, R), (2, E)):
-        P = torch.empty(T.shape[0], D, device=E.device, dtype=torch.float32)
-        with _lib.on_device(E.device):
-            _lib.check(L.recon_sgemm_ex(T.shape[0], D, D, T.data_ptr(), D, 0, W1.data_ptr() + 4 * k * D, 3 * D, 1, P.data_ptr(), D, None, stream),
-                       "recon_sgemm_ex")
-        out.append(P)
-    return ConvKBProjections(out[0], out[1], out[2], b1.detach().float().contiguous(), w2.detach().float().reshape(-1).contiguous(),
-                             b2.detach().float().reshape(1).contiguous(), float(convkb.nl1.negative_slope), E.shape[0], R.shape[0], D)
-
-
-def _check_triples(proj, triples, name="test_triples"):
-    _require_gpu(triples, proj.P_h)
-    if triples.dim() != 2 or triples.shape[1] != 3:
-        raise ValueError("%s: [Q, 3] (head, relation, tail) expected" % name)
-    t = triples.to(device=proj.P_h.device, dtype=torch.int64).contiguous()
-    if t.numel():
-        lo = t.amin(0).tolist()
-        hi = t.amax(0).tolist()
-        if min(lo) < 0 or hi[0] >= proj.n_ent or hi[2] >= proj.n_ent or hi[1] >= proj.n_rel:
-            raise ValueError("%s: an id lies outside its table (%d entities, %d relations)" % (name, proj.n_ent, proj.n_rel))
-    return t
+    W1, b1, w2, b2, slope = _detached_weights(convkb)
+    return ConvKBProjections(_project(E, W1, 0), _project(R, W1, 1), _project(E, W1, 2), b1, w2, b2, slope, E.shape[0], R.shape[0], D)
 
 
 def filter_keys(triples, slot, sizes):
@@ -88,10 +106,16 @@ def build_filter(known_triples, queries, slot, sizes):
     return keys % n_slot, begin, end
 
 
+def _rank_workspace(Q, D, device):
+    """(workspace, floats) of recon_convkb_rank / recon_kgsep_rank for Q queries."""
+    floats = _lib.lib().recon_convkb_rank_workspace_floats(Q, D)
+    return torch.empty(floats, dtype=torch.float32, device=device), floats
+
+
 def rank_slot(proj, triples, slot, known_triples=None):
     """Ranks (int64 [Q]) and true scores (fp32 [Q]) of the queries `triples` with column `slot` replaced by every id of its table; filtered by
     known_triples (the union of train, valid and test: valid_triples_dict) or raw (None)."""
-    t = _check_triples(proj, triples)
+    t = _check_triples(triples, proj.P_h, proj.n_ent, proj.n_rel)
     Q = t.shape[0]
     dev = t.device
     ranks = torch.empty(Q, dtype=torch.int64, device=dev)
@@ -100,11 +124,10 @@ def rank_slot(proj, triples, slot, known_triples=None):
         return ranks, scores
     filt = (None, None, None)
     if known_triples is not None:
-        k = _check_triples(proj, known_triples, "known_triples")
+        k = _check_triples(known_triples, proj.P_h, proj.n_ent, proj.n_rel, "known_triples")
         filt = build_filter(k, t, slot, (proj.n_ent, proj.n_rel))
     L = _lib.lib()
-    ws_floats = L.recon_convkb_rank_workspace_floats(Q, proj.D)
-    ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
+    ws, ws_floats = _rank_workspace(Q, proj.D, dev)
     with _lib.on_device(dev):
         _lib.check(L.recon_convkb_rank(slot, Q, t.data_ptr(), proj.P_h.data_ptr(), proj.P_r.data_ptr(), proj.P_t.data_ptr(), proj.n_ent, proj.n_rel,
                                        proj.D, proj.b1.data_ptr(), proj.w2.data_ptr(), proj.b2.data_ptr(), proj.slope, _lib.ptr(filt[0]),
@@ -122,19 +145,22 @@ def _keep_unique(triples, unique_entities):
     return triples[keep]
 
 
+def _entity_slots(side):
+    """The slots that rank_entities' `side` ('both', 'head' or 'tail') ranks, head first."""
+    if side not in ("both", "head", "tail"):
+        raise ValueError("side: 'both', 'head' or 'tail'")
+    return tuple(slot for slot, name in ((SLOT_HEAD, "head"), (SLOT_TAIL, "tail")) if side in ("both", name))
+
+
 def rank_entities(proj, test_triples, known_triples=None, side="both", unique_entities=None):
     """Filtered (known_triples given) or raw entity ranks of every test triple: (ranks_head, ranks_tail, true_scores), device tensors; a side
     not asked for is None.  true_scores: s* of the tail pass (of the head pass when side == "head")."""
-    if side not in ("both", "head", "tail"):
-        raise ValueError("side: 'both', 'head' or 'tail'")
-    _require_gpu(test_triples)
-    t = _keep_unique(_check_triples(proj, test_triples), unique_entities)
-    rh = rt = s = None
-    if side in ("both", "head"):
-        rh, s = rank_slot(proj, t, SLOT_HEAD, known_triples)
-    if side in ("both", "tail"):
-        rt, s = rank_slot(proj, t, SLOT_TAIL, known_triples)
-    return rh, rt, s
+    slots = _entity_slots(side)
+    t = _keep_unique(_check_triples(test_triples, proj.P_h, proj.n_ent, proj.n_rel), unique_entities)
+    ranks, s = {}, None
+    for slot in slots:
+        ranks[slot], s = rank_slot(proj, t, slot, known_triples)
+    return ranks.get(SLOT_HEAD), ranks.get(SLOT_TAIL), s
 
 
 def rank_relations(proj, test_triples, known_triples=None):
@@ -144,7 +170,7 @@ def rank_relations(proj, test_triples, known_triples=None):
 
 def slot_scores(proj, triples, slot, c0=0, C=None):
     """Dense scores S[q, j] = s(q with column `slot` = c0 + j), fp32 [Q, C] (the same score routine as the rank kernel: bit-identical)."""
-    t = _check_triples(proj, triples)
+    t = _check_triples(triples, proj.P_h, proj.n_ent, proj.n_rel)
     n_slot = proj.n_rel if slot == SLOT_RELATION else proj.n_ent
     C = n_slot - c0 if C is None else C
     S = torch.empty(t.shape[0], C, dtype=torch.float32, device=t.device)

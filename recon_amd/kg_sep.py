@@ -44,25 +44,13 @@ def check_ent2rel(model_gat, n_rel, D):
 def sep_scorer(entity_emb, relation_emb, convkb, model_gat):
     """Everything the kernels read: E, W_ent2rel, fc1.weight (in place, ldb = 3 D), P_r = Rel W_r^T (recon_sgemm_ex, as
     kg_eval.convkb_projections), b1, w2, b2 and nl1's slope.  Arguments are checked before any device work."""
-    W1, b1, w2, b2 = convkb.fc1.weight, convkb.fc1.bias, convkb.fc2.weight, convkb.fc2.bias
-    if entity_emb.dim() != 2 or relation_emb.dim() != 2 or relation_emb.shape[1] != entity_emb.shape[1]:
-        raise ValueError("sep_scorer: entity [N, D] and relation [R, D] tables expected")
-    N, D = entity_emb.shape
-    R = relation_emb.shape[0]
-    if tuple(W1.shape) != (D, 3 * D) or tuple(w2.shape) != (1, D):
-        raise ValueError("sep_scorer: fc1 [D, 3D], fc2 [1, D] expected")
+    D = _kge._check_shapes(entity_emb, relation_emb, convkb, "sep_scorer")
+    N, R = entity_emb.shape[0], relation_emb.shape[0]
     W = check_ent2rel(model_gat, R, D)
-    _kge._require_gpu(entity_emb, relation_emb, W, W1, b1, w2, b2)
-    E = entity_emb.detach().float().contiguous()
-    Rel = relation_emb.detach().float().contiguous()
-    W1 = W1.detach().float().contiguous()
-    P_r = torch.empty(R, D, device=E.device, dtype=torch.float32)
-    L = _lib.lib()
-    with _lib.on_device(E.device):
-        _lib.check(L.recon_sgemm_ex(R, D, D, Rel.data_ptr(), D, 0, W1.data_ptr() + 4 * D, 3 * D, 1, P_r.data_ptr(), D, None, _lib.current_stream()),
-                   "recon_sgemm_ex")
-    return SepScorer(E, W.detach().float().contiguous(), W1, P_r, b1.detach().float().contiguous(), w2.detach().float().reshape(-1).contiguous(),
-                     b2.detach().float().reshape(1).contiguous(), float(convkb.nl1.negative_slope), N, R, D)
+    _kge._require_gpu(entity_emb, relation_emb, W, convkb.fc1.weight, convkb.fc1.bias, convkb.fc2.weight, convkb.fc2.bias)
+    W1, b1, w2, b2, slope = _kge._detached_weights(convkb)
+    P_r = _kge._project(relation_emb.detach().float().contiguous(), W1, 1)
+    return SepScorer(entity_emb.detach().float().contiguous(), W.detach().float().contiguous(), W1, P_r, b1, w2, b2, slope, N, R, D)
 
 
 def plan_chunks(relations, n_rows, D, budget_bytes=DEFAULT_BUDGET):
@@ -101,15 +89,13 @@ def relation_projections(scorer, P_h, P_t, k):
 
 
 def _check(scorer, triples, name="test_triples"):
-    return _kge._check_triples(_kge.ConvKBProjections(scorer.E, None, None, None, None, None, None, scorer.n_ent, scorer.n_rel, scorer.D),
-                               triples, name)
+    return _kge._check_triples(triples, scorer.E, scorer.n_ent, scorer.n_rel, name)
 
 
 def _rank_chunk(scorer, t, rel, seg, P_h, P_t, slot, filt, ranks, scores):
     L = _lib.lib()
     Q = t.shape[0]
-    ws_floats = L.recon_convkb_rank_workspace_floats(Q, scorer.D)
-    ws = torch.empty(ws_floats, dtype=torch.float32, device=t.device)
+    ws, ws_floats = _kge._rank_workspace(Q, scorer.D, t.device)
     with _lib.on_device(t.device):
         _lib.check(L.recon_kgsep_rank(slot, Q, t.data_ptr(), seg.data_ptr(), rel.numel(), P_h.data_ptr(), scorer.P_r.data_ptr(), P_t.data_ptr(),
                                       P_h.shape[1], scorer.n_rel, scorer.D, scorer.b1.data_ptr(), scorer.w2.data_ptr(), scorer.b2.data_ptr(),
@@ -121,12 +107,10 @@ def rank_entities(scorer, test_triples, known_triples=None, side="both", unique_
     """Filtered (known_triples given) or raw head / tail ranks of the sep scorer: (ranks_head, ranks_tail, true_scores) as
     kg_eval.rank_entities, with the queries dropped by unique_entities removed first.  The queries are sorted by relation; each chunk's
     tables (all entities) are built once and serve both sides."""
-    if side not in ("both", "head", "tail"):
-        raise ValueError("side: 'both', 'head' or 'tail'")
+    sides = _kge._entity_slots(side)
     t = _kge._keep_unique(_check(scorer, test_triples), unique_entities)
     k = None if known_triples is None else _check(scorer, known_triples, "known_triples")
     Q, dev = t.shape[0], t.device
-    sides = [s for s, name in ((_kge.SLOT_HEAD, "head"), (_kge.SLOT_TAIL, "tail")) if side in ("both", name)]
     ranks = {s: torch.empty(Q, dtype=torch.int64, device=dev) for s in sides}
     true = torch.empty(Q, dtype=torch.float32, device=dev)
     order = torch.argsort(t[:, 1], stable=True)

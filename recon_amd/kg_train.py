@@ -14,26 +14,12 @@ frozen tables in place and reduce in one fixed order (csrc/kg_train.hip).  SpKBG
 import torch
 
 from . import _lib
-from .kg_eval import SLOT_TAIL, filter_keys
+from .kg_eval import SLOT_TAIL, _check_ids, _check_shapes, _require_gpu, filter_keys
 
 MAX_D = 512                          # recon_convkb_train_*: 1 <= D <= MAX_D
 ENTITY_DRAW_CAP = 1 << 16            # recon_kg_corrupt: entity draws per row before it gives up
 _FROZEN = ("the embedding tables must be frozen, as train_conv freezes them (GAT/main.py:741-742): "
            "model.final_entity_embeddings.requires_grad = False; model.final_relation_embeddings.requires_grad = False")
-
-
-def _require_gpu(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("recon_amd.kg_train: expected a GPU tensor (this package has no CPU path)")
-
-
-def _check_ids(triples, n_ent, n_rel, name):
-    """One device reduction and one host sync: every id inside its table."""
-    if triples.numel():
-        lo, hi = triples.amin(0).tolist(), triples.amax(0).tolist()
-        if min(lo) < 0 or hi[0] >= n_ent or hi[2] >= n_ent or hi[1] >= n_rel:
-            raise ValueError("%s: an id lies outside its table (%d entities, %d relations)" % (name, n_ent, n_rel))
 
 
 def _triples(triples, name):
@@ -142,9 +128,7 @@ def _params(model):
     conv = model.convKB
     W1, b1, w2, b2 = conv.fc1.weight, conv.fc1.bias, conv.fc2.weight, conv.fc2.bias
     _require_gpu(E, R, W1, b1, w2, b2)
-    D = E.shape[1]
-    if E.dim() != 2 or R.dim() != 2 or R.shape[1] != D or tuple(W1.shape) != (D, 3 * D) or tuple(w2.shape) != (1, D):
-        raise ValueError("recon_amd.kg_train: entity [N, D], relation [R, D], fc1 [D, 3D], fc2 [1, D] expected")
+    _check_shapes(E, R, conv, "recon_amd.kg_train")
     for p in (E, R, W1, b1, w2, b2):
         if p.dtype != torch.float32:
             raise ValueError("recon_amd.kg_train: fp32 tables and weights expected")
