@@ -290,6 +290,9 @@ size_t recon_gat_atp_split_bytes(int32_t F, int32_t R, int32_t D, int32_t H);
  * 16-byte aligned a_split / V, 256-byte aligned aux and ld_out % 4 == 0 the call uses it, otherwise it falls back to BF16X3 */
 int recon_gat_atp_f16x2_supported(int32_t F, int32_t R, int32_t D, int32_t H);
 int recon_gat_atp_supported(int32_t N, int32_t E, int32_t F, int32_t R, int32_t D, int32_t H);
+/* the edge-pass kernel instance the widths select: vec * 1000 + kr * 10 + log2(ht) (vec: load width, kr: register rows per lane,
+ * ht: heads per wave), -1 where no instance exists.  Host only; says nothing about the other limits of recon_gat_atp_supported() */
+int32_t recon_gat_atp_instance(int32_t F, int32_t R, int32_t H);
 int recon_gat_atp_fwd(const recon_graph* g, const recon_gat_atp_args* args, recon_stream_t stream);
 /* the three stages of recon_gat_atp_fwd, exported for profiling / tests */
 int recon_gat_atp_scores(const recon_graph* g, const recon_gat_atp_args* args, recon_stream_t stream);    /* u, c_node, c_rel */

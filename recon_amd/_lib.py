@@ -170,6 +170,7 @@ SYMBOLS = [
     ("recon_gat_bwd", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatBwdArgs), C.c_void_p]),
     ("recon_gat_atp_supported", C.c_int, [C.c_int32] * 6),
     ("recon_gat_atp_f16x2_supported", C.c_int, [C.c_int32] * 4),
+    ("recon_gat_atp_instance", C.c_int32, [C.c_int32] * 3),
     ("recon_gat_atp_fwd", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatAtpArgs), C.c_void_p]),
     ("recon_gat_atp_scores", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatAtpArgs), C.c_void_p]),
     ("recon_gat_atp_aggregate", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatAtpArgs), C.c_void_p]),
@@ -302,12 +303,20 @@ def lib():
     return _lib
 
 
+# host-side caches of library answers that may depend on a switch (gat_layers: recon_gat_atp_bwd_gee_bf16_supported reads RECON_K2_LDS_RING,
+# the backward's split-K scratch size RECON_GEMM_SPLITK); config_set empties them, or a layer would keep asking for an instance the
+# library no longer selects, or size scratch for a split it no longer uses
+SWITCH_CACHES = []
+
+
 def config_set(name, value):
     """Override one run-time switch of the library (csrc/config.hip; value None: unset).  Returns the previous value (or None)."""
     h = lib()
     prev = h.recon_config_get(name.encode())
     prev = prev.decode() if prev is not None else None
     check(h.recon_config_set(name.encode(), None if value is None else str(value).encode()), "recon_config_set(%s)" % name)
+    for cache in SWITCH_CACHES:
+        cache.clear()
     return prev
 
 

@@ -1932,10 +1932,12 @@ bool atp_shape(int F, int R, int H, AtpShape* s) {
     return true;
 }
 bool al(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// the ATP_DISPATCH key of a shape (recon_gat_atp_instance)
+int atp_key(const AtpShape& s) { return s.vec * 1000 + s.kr * 10 + (s.ht == 8 ? 3 : s.ht == 4 ? 2 : s.ht == 2 ? 1 : 0); }
 
 #define ATP_DISPATCH(S, CALL)                                                                              \
     do {                                                                                                   \
-        const int key_ = (S).vec * 1000 + (S).kr * 10 + ((S).ht == 8 ? 3 : (S).ht == 4 ? 2 : (S).ht == 2 ? 1 : 0); \
+        const int key_ = atp_key(S);                                                                       \
         switch (key_) {                                                                                    \
             case 4010: CALL(4, 1, 1); break; case 4011: CALL(4, 1, 2); break; case 4012: CALL(4, 1, 4); break; case 4013: CALL(4, 1, 8); break; \
             case 4020: CALL(4, 2, 1); break; case 4021: CALL(4, 2, 2); break; case 4022: CALL(4, 2, 4); break;   \
@@ -1992,6 +1994,12 @@ extern "C" int recon_gat_atp_supported(int32_t N, int32_t E, int32_t F, int32_t 
     const int64_t W = 2LL * F + R, mx = F > R ? F : R;
     if (4 * H * W > 64 * 1024 || 8LL * H * (mx + 4) > 64 * 1024) return 0;
     return 1;
+}
+
+extern "C" int32_t recon_gat_atp_instance(int32_t F, int32_t R, int32_t H) {
+    AtpShape s;
+    if (F <= 0 || R <= 0 || H <= 0 || !atp_shape(F, R, H, &s)) return -1;
+    return atp_key(s);
 }
 
 // a_split layout: planes of a  [3][H][D][kp(W)]  then planes of a^T [3][H][W][kp(D)]  (bf16), each part 16-byte aligned

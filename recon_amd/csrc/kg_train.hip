@@ -203,7 +203,8 @@ __global__ void __launch_bounds__(kThreads) k_kgt_fwd(const KgtArgs a, const flo
         for (int q = 0; q < NP * 4; ++q) ws[kk_s][r_s + 16 * q] = wr[q];
         __syncthreads();
         if (k0 + kKC < K) load(k0 + kKC);
-#pragma unroll(NP > 6 ? 2 : 4)
+        constexpr int kUnrollKK = NP > 6 ? 2 : 4;
+#pragma unroll kUnrollKK
         for (int kk = 0; kk < kKC; ++kk) {
             f32x2 w[NP];
 #pragma unroll

@@ -524,8 +524,9 @@ def _view_f32(buf, ptr, n):
     return buf[off:off + 4 * n].view(torch.float32)
 
 
-_SIZE_CACHE = {}
-_GEE16 = {}
+_SIZE_CACHE = {}                  # (split-K partials follow RECON_GEMM_SPLITK)
+_GEE16 = {}                       # (the bf16 g_edge_embed store needs the LDS row ring: RECON_K2_LDS_RING)
+_lib.SWITCH_CACHES.extend((_SIZE_CACHE, _GEE16))      # answers that follow a run-time switch: emptied by _lib.config_set
 
 
 def _gee_bf16_ok(F_, R, D, H):
