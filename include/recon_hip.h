@@ -844,6 +844,18 @@ int recon_convkb_scores(int32_t slot, int64_t Q, const int64_t* triples, const f
  * outside [0, n_rows) gives the row of a zero entity.  No atomics: bitwise identical from run to run.  One launch. */
 int recon_kgsep_tables(const float* E, int64_t n_rows, const int64_t* ids, int64_t U, const float* W_ent2rel, int64_t n_rel, const int64_t* rel_ids,
                        int32_t Rc, const float* W1, int32_t D, float* P_h, float* P_t, recon_stream_t stream);
+/* The rows the training step of the sep scorer feeds ConvKB (SpKBGATConvOnly.forward, GAT_sep_space/models.py:311-324: the [M, D, D] gather
+ * W_ent2rel[batch[:, 1]], two bmm and tanh of :312-320): T [2 M][D] fp32 with T[m] = tanh(E[h_m] W_ent2rel[r_m]) and T[M + m] =
+ * tanh(E[t_m] W_ent2rel[r_m]), and remapped int64 [M][3] = (m, r_m, M + m), so that recon_convkb_train_fwd / _bwd score the batch with
+ * E := T, n_ent := 2 M.  triples int32 or int64 [M][3] (index_bytes 4 or 8), E [n_ent][D], W_ent2rel [n_rel][D][D] laid out [in][out].
+ * Item i < M is the head of triple i, item M + i its tail; order int64 [2 M] holds the items sorted by relation and seg int64 [n_rel + 1]
+ * delimits relation r's items, order[seg[r] .. seg[r + 1]) (device, no host read: a stable argsort and a bincount / cumsum of the relation
+ * column, with ids outside [0, n_rel) clamped into it first).  An item whose entity id lies outside [0, n_ent) or whose relation is not
+ * the one it was sorted under gets a NaN row, so the triple scores NaN.  Exact fp32 products (v_mfma_f32_16x16x4_f32), tanh in fp32; one
+ * lane writes each element, no atomics: bitwise identical from run to run.  1 <= D <= 512 (RECON_ERR_UNSUPPORTED above), M < 2^31.
+ * One launch of ceil(2 M / (16 RB)) + n_rel workgroups; those without a tile leave at once. */
+int recon_kgsep_ent2rel(const void* triples, int32_t index_bytes, int64_t M, const float* E, int64_t n_ent, const float* W_ent2rel, int64_t n_rel,
+                        int32_t D, const int64_t* order, const int64_t* seg, float* T, int64_t* remapped, recon_stream_t stream);
 /* Filtered (or raw) head or tail ranks (slot RECON_KGE_HEAD / RECON_KGE_TAIL) of queries sorted by relation, on one chunk's tables
  * (n_ent = rows per relation): the queries of local relation rl are triples[seg[rl] .. seg[rl + 1]) (seg int64 [Rc + 1], device,
  * non-decreasing, seg[0] = 0, seg[Rc] = Q), their relation column is rel_ids[rl] (it indexes P_r).  Ranks, true scores, the filter and the

@@ -248,6 +248,8 @@ SYMBOLS = [
                                       C.c_float, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_void_p]),
     ("recon_kgsep_tables", C.c_int, [c_f32p, C.c_int64, c_i64p, C.c_int64, c_f32p, C.c_int64, c_i64p, C.c_int32, c_f32p, C.c_int32, c_f32p, c_f32p,
                                      C.c_void_p]),
+    ("recon_kgsep_ent2rel", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int32, c_i64p, c_i64p, c_f32p,
+                                      c_i64p, C.c_void_p]),
     ("recon_kgsep_rank", C.c_int, [C.c_int32, C.c_int64, c_i64p, c_i64p, C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int32, c_f32p,
                                    c_f32p, c_f32p, C.c_float, c_i64p, c_i64p, c_i64p, c_f32p, C.c_size_t, c_i64p, c_f32p, C.c_void_p]),
     ("recon_kgsep_scores", C.c_int, [C.c_int64, c_i64p, c_i64p, C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int32, c_f32p, c_f32p,

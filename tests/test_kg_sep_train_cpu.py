@@ -1,0 +1,94 @@
+"""Training of the GAT_sep_space ConvKB scorer (recon_amd.kg_sep_train, csrc/kg_sep.hip): the parts that need no GPU — the reference fixture
+against an fp64 numpy restatement of the sep scorer, its loss and gradients, the ABI surface, and the checks that run before device work."""
+import ctypes
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT, load_golden
+
+
+def _sep_step64(g):
+    """fp64 preds, weighted-BCE loss and the four ConvKB gradients of the fixture's step, restated in numpy."""
+    idx = g["indices"]
+    h, r, t = idx[:, 0], idx[:, 1], idx[:, 2]
+    E, R, W = g["sd__final_entity_embeddings"].astype(np.float64), g["sd__final_relation_embeddings"].astype(np.float64), g["gat__W_ent2rel"].astype(np.float64)
+    th = np.tanh(np.einsum("md,mde->me", E[h], W[r]))
+    tt = np.tanh(np.einsum("md,mde->me", E[t], W[r]))
+    X = np.concatenate([th, R[r], tt], 1)
+    W1, b1 = g["sd__convKB.fc1.weight"].astype(np.float64), g["sd__convKB.fc1.bias"].astype(np.float64)
+    w2, b2 = g["sd__convKB.fc2.weight"].astype(np.float64).reshape(-1), g["sd__convKB.fc2.bias"].astype(np.float64)
+    z = X @ W1.T + b1
+    a = np.where(z > 0, z, 0.01 * z)
+    s = a @ w2 + b2
+    y = (g["values"].astype(np.float64) + 1) / 2
+    w = y + (1 - y) / (2 * int(g["ratio"]))
+    m = np.maximum(-s, 0)
+    loss = np.mean(w * ((1 - y) * s + m + np.log(np.exp(-m) + np.exp(-s - m))))
+    gs = w * (1 / (1 + np.exp(-s)) - y) / len(s)
+    delta = gs[:, None] * w2[None, :] * np.where(z > 0, 1.0, 0.01)
+    grads = {"convKB.fc1.weight": delta.T @ X, "convKB.fc1.bias": delta.sum(0), "convKB.fc2.weight": (gs @ a)[None, :],
+             "convKB.fc2.bias": np.array([gs.sum()])}
+    return s, loss, grads
+
+
+def test_fixture_is_the_sep_scorer_and_its_weighted_bce():
+    g = load_golden("convkb_sep_train1")
+    s, loss, grads = _sep_step64(g)
+    np.testing.assert_allclose(g["preds"], s, rtol=1e-5, atol=1e-5)
+    assert abs(loss - float(g["loss"])) <= 1e-6 * max(1.0, abs(loss))
+    for k, ref in grads.items():
+        np.testing.assert_allclose(g["grad__" + k], ref.reshape(g["grad__" + k].shape), rtol=1e-4, atol=1e-6 * np.abs(ref).max())
+    assert int(g["iter"]) == 1 and (g["positives"] == g["indices"][:int(g["batch_size"])]).all()
+
+
+def test_kg_sep_train_symbol_declared_exported_bound():
+    from recon_amd import _lib
+    header = open(os.path.join(ROOT, "include", "recon_hip.h")).read()
+    assert re.search(r"\brecon_kgsep_ent2rel\(", header)
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "recon_kgsep_ent2rel")
+    assert "recon_kgsep_ent2rel" in {s[0] for s in _lib.SYMBOLS}
+    L = _lib.lib()
+    fake = 16                                                                # never dereferenced: every call below returns before a launch
+    args = lambda M, D, ib: (fake, ib, M, fake, 10, fake, 3, D, fake, fake, fake, fake, None)
+    assert L.recon_kgsep_ent2rel(*args(4, 513, 8)) == -2                     # D above the limit
+    assert L.recon_kgsep_ent2rel(*args(4, 0, 8)) == -1
+    assert L.recon_kgsep_ent2rel(*args(4, 16, 2)) == -1                      # index width
+    assert L.recon_kgsep_ent2rel(*args(-1, 16, 8)) == -1
+    assert L.recon_kgsep_ent2rel(*args(0, 16, 8)) == 0                       # nothing to do
+
+
+def _shell(n_ent=40, n_rel=3, D=16):
+    from recon_amd.sep_space import SpKBGATConvOnly
+    m = SpKBGATConvOnly(torch.randn(n_ent, 8), torch.randn(n_rel, 8), [D // 2, D], [D // 2, D], 0.0, 0.0, 0.2, 0.2, [2, 2], 50)
+    return m, types.SimpleNamespace(W_ent2rel=torch.randn(n_rel, D, D), nonlinearity_ent2rel=torch.tanh)
+
+
+def test_kg_sep_train_rejects_before_device_work():
+    from recon_amd import kg_sep_train as K
+    m, gat = _shell()
+    tri, val = torch.zeros(6, 3, dtype=torch.int64), torch.ones(6)
+    with pytest.raises(RuntimeError, match="741-742"):                       # trainable tables: refused, not silently frozen
+        K.sep_convkb_scores(m, gat, tri)
+    m.final_entity_embeddings.requires_grad_(False)
+    m.final_relation_embeddings.requires_grad_(False)
+    with pytest.raises(RuntimeError, match=r"808-809(.|\n)*requires_grad_\(False\)"):
+        K.sep_convkb_bce_loss(m, types.SimpleNamespace(W_ent2rel=torch.nn.Parameter(gat.W_ent2rel), nonlinearity_ent2rel=torch.tanh), tri, val, 2)
+    with pytest.raises(ValueError, match="tanh"):
+        K.sep_convkb_scores(m, types.SimpleNamespace(W_ent2rel=gat.W_ent2rel, nonlinearity_ent2rel=torch.sigmoid), tri)
+    with pytest.raises(ValueError, match="W_ent2rel"):
+        K.sep_convkb_scores(m, types.SimpleNamespace(W_ent2rel=gat.W_ent2rel[:, :8], nonlinearity_ent2rel=torch.tanh), tri)
+    big, gbig = _shell(D=514)
+    big.requires_grad_(False)
+    with pytest.raises(ValueError, match="512"):
+        K.sep_convkb_scores(big, types.SimpleNamespace(W_ent2rel=torch.zeros(3, 514, 514), nonlinearity_ent2rel=torch.tanh), tri)
+    with pytest.raises(ValueError, match="ratio"):
+        K.sep_convkb_bce_loss(m, gat, tri, val, 0)
+    with pytest.raises(RuntimeError, match="GPU"):                           # no CPU path
+        K.sep_convkb_scores(m, gat, tri)
+    with pytest.raises(RuntimeError, match="GPU"):
+        K.ent2rel_rows(m.final_entity_embeddings, gat.W_ent2rel, tri)
