@@ -345,8 +345,46 @@ def check(code, what):
 
 
 def ptr(t):
-    """Device pointer of a torch tensor (or None)."""
-    return None if t is None else t.data_ptr()
+    """Device pointer of a torch tensor, an int that already is one (a workspace slice), or None."""
+    return t if (t is None or isinstance(t, int)) else t.data_ptr()
+
+
+def ptr_array(tensors):
+    """c_void_p array of the tensors' device pointers (None: a null entry); the caller keeps it alive across the launch."""
+    arr = (C.c_void_p * len(tensors))()
+    for i, t in enumerate(tensors):
+        arr[i] = None if t is None else t.data_ptr()
+    return arr
+
+
+MAX_BATCH = 65535           # graphs per launch (recon_propagate_* / recon_gcn_*: RECON_ERR_UNSUPPORTED above)
+
+_ZEROS = {}
+
+
+def zero_page(dev):
+    """1 KiB of zero bytes per device: what the K tails of the bf16 GEMMs read (include/recon_hip.h: recon_prop_b16_args.zeros,
+    recon_gcn_b16_bwd_args.zeros)."""
+    z = _ZEROS.get(dev)
+    if z is None:
+        import torch
+        z = _ZEROS[dev] = torch.zeros(1024, dtype=torch.uint8, device=dev)
+    return z
+
+
+_F32_ONLY = (TypeError, "recon_amd: the HIP kernels compute in float32, got %(got)s")
+
+
+def require_gpu(*tensors, dtype=None, floats_only=False, wrong_dtype=_F32_ONLY):
+    """Every tensor (None: skipped) on a GPU, else RuntimeError; with `dtype`, every tensor (floats_only: every floating-point one) of that
+    dtype, else wrong_dtype = (exception type, message; %(want)s and %(got)s stand for the two dtypes).  Tensor by tensor, in order."""
+    for t in tensors:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError("recon_amd: expected a GPU tensor (this package has no CPU path)")
+        if dtype is not None and t.dtype != dtype and (not floats_only or t.is_floating_point()):
+            raise wrong_dtype[0](wrong_dtype[1] % {"want": dtype, "got": t.dtype})
 
 
 try:                                    # the raw handle without building a torch.cuda.Stream object (3-5 us per call otherwise: a launch-bound

@@ -103,16 +103,6 @@ def _side_stream(dev):
     return s
 
 
-def _require_gpu_f32(*tensors):
-    for t in tensors:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError("recon_amd: expected a GPU tensor (this package has no CPU path)")
-        if t.dtype != torch.float32:
-            raise TypeError("recon_amd: the HIP kernels compute in float32, got %s" % t.dtype)
-
-
 class ConvKB(nn.Module):
     """Scorer exported by GAT/layers.py:12-48 (not on the hot path; re-exported so that
     `from layers import SpGraphAttentionLayer, ConvKB` keeps working).  Live path: fc1 -> LeakyReLU ->
@@ -141,7 +131,7 @@ class SpecialSpmmFunctionFinal(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, edge, edge_w, N, E, out_features):
-        _require_gpu_f32(edge_w)
+        _lib.require_gpu(edge_w, dtype=torch.float32)
         L = _lib.lib()
         g = prepare_graph(edge, None, N)
         w = edge_w.contiguous().view(g.E, -1 if g.E else int(out_features))       # no edges: the width comes from the argument
@@ -176,7 +166,7 @@ class _GatherRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, index):
-        _require_gpu_f32(table)
+        _lib.require_gpu(table, dtype=torch.float32)
         ctx.n_rows = table.shape[0]
         ctx.index = index
         return table.index_select(0, index)
@@ -194,7 +184,7 @@ class _GatherRowsPair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, idx2):
-        _require_gpu_f32(table)
+        _lib.require_gpu(table, dtype=torch.float32)
         ctx.n_rows, ctx.idx2 = table.shape[0], idx2
         table = table.contiguous()
         out = torch.empty(idx2.shape[0], table.shape[1], dtype=torch.float32, device=table.device)
@@ -253,7 +243,7 @@ class _SmallMM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, A, B):
-        _require_gpu_f32(A, B)
+        _lib.require_gpu(A, B, dtype=torch.float32)
         A, B = A.contiguous(), B.contiguous()
         ctx.save_for_backward(A, B)
         return _sgemm_small(A, False, B, False)
@@ -275,7 +265,7 @@ class _ThinWeightMM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, A, B):
-        _require_gpu_f32(A, B)
+        _lib.require_gpu(A, B, dtype=torch.float32)
         A, B = A.contiguous(), B.contiguous()
         ctx.save_for_backward(A, B)
         return _sgemm_ex(A, False, B, False)
@@ -295,7 +285,7 @@ class _GemmMM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, A, B):
-        _require_gpu_f32(A, B)
+        _lib.require_gpu(A, B, dtype=torch.float32)
         A, B = A.contiguous(), B.contiguous()
         ctx.save_for_backward(A, B)
         return _sgemm_ex(A, False, B, False)
@@ -320,7 +310,7 @@ def _sgemm_ex(A, a_is_km, B, b_is_nk):
         L = _lib.lib()
         nws = L.recon_sgemm_ex_workspace_floats(M, N, K)
         ws = torch.empty(nws, dtype=torch.float32, device=A.device) if nws else None
-        with _on_device(A.device):
+        with _lib.on_device(A.device):
             _lib.check(L.recon_sgemm_ex(M, N, K, A.data_ptr(), A.shape[1], 1 if a_is_km else 0, B.data_ptr(), B.shape[1],
                                         1 if b_is_nk else 0, out.data_ptr(), N, _lib.ptr(ws), _lib.current_stream()), "recon_sgemm_ex")
     return out
@@ -335,7 +325,7 @@ def _sgemm_small(A, a_is_km, B, b_is_nk):
         L = _lib.lib()
         nws = L.recon_sgemm_small_workspace_floats(M, N, K)
         ws = torch.empty(nws, dtype=torch.float32, device=A.device) if nws else None
-        with _on_device(A.device):
+        with _lib.on_device(A.device):
             _lib.check(L.recon_sgemm_small(M, N, K, A.data_ptr(), A.shape[1], 1 if a_is_km else 0, B.data_ptr(), B.shape[1],
                                            1 if b_is_nk else 0, out.data_ptr(), N, _lib.ptr(ws), _lib.current_stream()), "recon_sgemm_small")
     return out
@@ -402,7 +392,7 @@ class _GATHeadsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ee, a, a2, graph, keep, alpha, concat, keep_iid=False):
-        _require_gpu_f32(x, ee, a, a2, keep)
+        _lib.require_gpu(x, ee, a, a2, keep, dtype=torch.float32)
         L = _lib.lib()
         x, ee, a, a2 = x.contiguous(), ee.contiguous(), a.contiguous(), a2.contiguous()
         H, D = a2.shape
@@ -456,20 +446,15 @@ class _GATHeadsFunction(torch.autograd.Function):
         return g_x, g_ee, g_a, g_a2, None, None, None, None, None
 
 
-def _p(t):
-    """Device pointer of a tensor, an int that already is one, or None."""
-    return t if (t is None or isinstance(t, int)) else t.data_ptr()
-
-
 def _atp_args(graph, x, ee, a, a2, keep, u, c_node, c_rel, V, sigma, Z, Zk, out, alpha, concat, a_split=None, aux=None,
               keep_max=1.0, ee_index=None, io_bf16=False):
     """recon_gat_atp_args from tensors or raw device pointers (workspace slices)."""
     H, D = a2.shape
     return _lib.GatAtpArgs(graph.N, graph.E, x.shape[1], ee.shape[1], D, H, int(bool(concat)), float(alpha),
-                           x.data_ptr(), ee.data_ptr(), a.data_ptr(), a2.data_ptr(), _p(keep), _p(u),
-                           _p(c_node), _p(c_rel), _p(V), _p(sigma), _p(Z), _p(Zk),
-                           _p(out), out.shape[1] if out is not None else H * D, _p(a_split), SPLIT_F16X2 if aux is not None else SPLIT_BF16X3,
-                           float(keep_max), _p(aux), _p(ee_index), ee.shape[0] if ee_index is not None else 0, int(bool(io_bf16)))
+                           x.data_ptr(), ee.data_ptr(), a.data_ptr(), a2.data_ptr(), _lib.ptr(keep), _lib.ptr(u),
+                           _lib.ptr(c_node), _lib.ptr(c_rel), _lib.ptr(V), _lib.ptr(sigma), _lib.ptr(Z), _lib.ptr(Zk),
+                           _lib.ptr(out), out.shape[1] if out is not None else H * D, _lib.ptr(a_split), SPLIT_F16X2 if aux is not None else SPLIT_BF16X3,
+                           float(keep_max), _lib.ptr(aux), _lib.ptr(ee_index), ee.shape[0] if ee_index is not None else 0, int(bool(io_bf16)))
 
 
 _PAD_MIN_OUT = 1 << 18            # below this many output elements the padding's extra launches cost more than the aligned GEMMs win
@@ -551,22 +536,6 @@ def _lib_sizes(N, E, F_, R, D, H):
     return v
 
 
-def _on_device(dev):
-    """Context that makes `dev` current — only entered when it is not already (the context manager costs ~10 us)."""
-    return torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _NULL_CTX
-
-
-class _NullCtx:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NULL_CTX = _NullCtx()
-
-
 class _GATHeadsATPFunction(torch.autograd.Function):
     """Same contract as _GATHeadsFunction, through the aggregate-then-project kernels (csrc/gat_atp.hip)."""
 
@@ -579,9 +548,9 @@ class _GATHeadsATPFunction(torch.autograd.Function):
         if io16:
             if ee.dtype != torch.bfloat16 or ee_index is not None or not (x.is_cuda and ee.is_cuda):
                 raise ValueError("recon_amd.gat_heads: bfloat16 features need bfloat16 edge embeddings on the GPU (no table mode)")
-            _require_gpu_f32(a, a2, keep)
+            _lib.require_gpu(a, a2, keep, dtype=torch.float32)
         else:
-            _require_gpu_f32(x, ee, a, a2, keep)
+            _lib.require_gpu(x, ee, a, a2, keep, dtype=torch.float32)
         L = _lib.lib()
         x, ee, a, a2 = x.contiguous(), ee.contiguous(), a.contiguous(), a2.contiguous()
         if io16:                                                    # bfloat16 rows are read 16 bytes at a time: a view at an odd storage offset is copied
@@ -620,7 +589,7 @@ class _GATHeadsATPFunction(torch.autograd.Function):
         # stage needs none of them: it goes out first, so that the device has work behind the build while the host waits and launches again
         early = graph.pending and graph.build_stream == _lib.current_stream()
         if early:
-            with _on_device(dev):
+            with _lib.on_device(dev):
                 _lib.check(L.recon_gat_atp_scores(C.byref(graph.raw_struct()), C.byref(args), _lib.current_stream()), "recon_gat_atp_scores")
         gstruct, _hub_keep = graph.call_struct(F_, R, H)
         # few destination rows have edges (graph.ROWS_COMPACT_MAX; known once the graph is resolved): the layer runs over those rows, writes
@@ -628,7 +597,7 @@ class _GATHeadsATPFunction(torch.autograd.Function):
         NR = graph.n_rows or N
         out = torch.empty(NR, H * D, dtype=torch.float32, device=dev)
         args.out = out.data_ptr()
-        with _on_device(dev):
+        with _lib.on_device(dev):
             if early:
                 _lib.check(L.recon_gat_atp_aggregate(C.byref(gstruct), C.byref(args), _lib.current_stream()), "recon_gat_atp_aggregate")
                 _lib.check(L.recon_gat_atp_project(C.byref(gstruct), C.byref(args), _lib.current_stream()), "recon_gat_atp_project")
@@ -641,7 +610,7 @@ class _GATHeadsATPFunction(torch.autograd.Function):
             ctx.idx_slot = idx_slot
         if NR != N:
             full = torch.empty(N, H * D, dtype=torch.float32, device=dev)
-            with _on_device(dev):
+            with _lib.on_device(dev):
                 _lib.check(L.recon_rows_expand(out.data_ptr(), H * D, graph.c.node_row, N, H * D, full.data_ptr(), H * D, _lib.current_stream()), "recon_rows_expand")
             return full
         return out
@@ -681,7 +650,7 @@ class _GATHeadsATPFunction(torch.autograd.Function):
                                   _lib.ptr(g_x), _lib.ptr(g_ee), _lib.ptr(g_a), _lib.ptr(g_a2), gh_split, 1 if gee16 else 0)
         gstruct, _hub_keep = graph.call_struct(F_, R, H)
         sync = _WEIGHT_GRAD_SYNC if g_a is not None else None
-        with _on_device(dev):
+        with _lib.on_device(dev):
             if sync is not None:
                 # PREPARE -> WEIGHTS (+ split-K sum: g_a = G) -> [all-reduce G, asynchronous] || INPUTS -> all-reduce g_u -> FINISH on the means
                 st = _lib.current_stream()

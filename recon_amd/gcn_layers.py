@@ -22,20 +22,10 @@ from . import _lib
 from . import gat_layers as _gl        # the GEMM-family switch (_GEMM_BX3) is ONE module-level setting for GAT and GCN
 
 
-def _req(*ts):
-    for t in ts:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError("recon_amd: expected a GPU tensor (this package has no CPU path)")
-        if t.dtype != torch.float32:
-            raise TypeError("recon_amd: the HIP kernels compute in float32, got %s" % t.dtype)
-
-
 class _GcnFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, adj, weight, bias):
-        _req(x, adj, weight, bias)
+        _lib.require_gpu(x, adj, weight, bias, dtype=torch.float32)
         x3 = x.contiguous().view(-1, x.shape[-2], x.shape[-1])
         adj3 = adj.contiguous().view(-1, adj.shape[-2], adj.shape[-1])
         weight = weight.contiguous()
@@ -136,15 +126,7 @@ def _packed_rows(t, feat, zero_pad):
     return buf, ld
 
 
-_ZEROS = {}
 _FUSED = os.environ.get("RECON_GCN_FUSED", "1") != "0"
-
-
-def _zero_page(dev):
-    z = _ZEROS.get(dev)
-    if z is None:
-        z = _ZEROS[dev] = torch.zeros(1024, dtype=torch.uint8, device=dev)
-    return z
 
 
 class _NoGradCtx:
@@ -244,7 +226,7 @@ class _GcnB16Function(torch.autograd.Function):
         fwd = _lib.GcnB16Args(B, n, I, O, xr.data_ptr(), ldx, adj3.data_ptr(), weight.data_ptr(), _lib.ptr(bias), _lib.ptr(sup), o8,
                               out_p.data_ptr(), o8, planes.data_ptr(), 1, None, None, 0)
         args = _lib.GcnB16BwdArgs(fwd, gr.data_ptr(), ldg, g_sup.data_ptr(), partial.data_ptr(), _lib.ptr(g_x), i8, _lib.ptr(g_adj),
-                                  _lib.ptr(g_w), _lib.ptr(g_b), _zero_page(dev).data_ptr())
+                                  _lib.ptr(g_w), _lib.ptr(g_b), _lib.zero_page(dev).data_ptr())
         with _lib.on_device(dev):
             _lib.check(L.recon_gcn_b16_bwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_bwd")
         if g_x is not None:
@@ -297,8 +279,8 @@ class _GcnB16RaggedFunction(torch.autograd.Function):
                 raise TypeError("recon_amd: the ragged GraphConvolution path needs bfloat16 GPU tensors for input, adjacency values, weight and bias")
         if x.dim() != 2 or x.shape[0] != ragged.total_rows or weight.shape[0] != x.shape[1]:
             raise ValueError("GraphConvolution (ragged): input must be [total nodes, in_features]")
-        if ragged.B > _MAX_BATCH:
-            raise NotImplementedError("GraphConvolution (ragged): more than %d graphs per call" % _MAX_BATCH)
+        if ragged.B > _lib.MAX_BATCH:
+            raise NotImplementedError("GraphConvolution (ragged): more than %d graphs per call" % _lib.MAX_BATCH)
         N, I = x.shape
         O = weight.shape[1]
         dev = x.device
@@ -353,7 +335,7 @@ class _GcnB16RaggedFunction(torch.autograd.Function):
         fwd = _lib.GcnB16Args(rg.B, rg.n_max, I, O, xr.data_ptr(), ldx, values.data_ptr(), weight.data_ptr(), _lib.ptr(bias), sup.data_ptr(), o8,
                               out_p.data_ptr(), o8, planes.data_ptr(), 1, rg.node_ptr.data_ptr(), rg.adj_ptr.data_ptr(), N)
         args = _lib.GcnB16BwdArgs(fwd, gr.data_ptr(), ldg, g_sup.data_ptr(), partial.data_ptr(), _lib.ptr(g_x), i8, _lib.ptr(g_adj),
-                                  _lib.ptr(g_w), _lib.ptr(g_b), _zero_page(dev).data_ptr())
+                                  _lib.ptr(g_w), _lib.ptr(g_b), _lib.zero_page(dev).data_ptr())
         with _lib.on_device(dev):
             _lib.check(L.recon_gcn_b16_bwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_bwd (ragged)")
         if g_x is not None and i8 != I:
@@ -368,9 +350,6 @@ def _strides(lead, ld):
         st.append(acc)
         acc *= d
     return tuple(reversed(st)) + (1,)
-
-
-_MAX_BATCH = 65535          # graphs per launch (recon_gcn_fwd/bwd return RECON_ERR_UNSUPPORTED above)
 
 
 class SparseMM(torch.autograd.Function):
@@ -405,10 +384,6 @@ _STACK_PLANES = {}     # (weight data_ptr, version, in, out, device) -> (W^T pla
 def invalidate_stack_planes():
     """Drop the repacked weights gcn_stack() keeps (after an in-place write through `weight.data`)."""
     _STACK_PLANES.clear()
-
-
-def _ptr_array(tensors):
-    return (C.c_void_p * len(tensors))(*[(t.data_ptr() if t is not None else None) for t in tensors])
 
 
 def _ptrs(base, offsets):
@@ -451,7 +426,7 @@ class _GcnB16StackFunction(torch.autograd.Function):
         poff = [sum(pb[:l]) for l in range(n_layers)]
         planes = torch.empty(sum(pb), dtype=torch.uint8, device=dev)
         args = _lib.GcnB16StackTrainArgs(B, n, I, D, n_layers, xin.data_ptr(), ldin, xr.data_ptr() if xr is not xin else None, ldx, adj3.data_ptr(),
-                                         _ptr_array(ws), _ptr_array(bs),
+                                         _lib.ptr_array(ws), _lib.ptr_array(bs),
                                          _ptrs(planes.data_ptr(), poff), _ptrs(acts.data_ptr(), [l * B * n * o8 * 2 for l in range(n_layers)]), o8)
         with _lib.on_device(dev):
             _lib.check(L.recon_gcn_b16_stack_train_fwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_stack_train_fwd")
@@ -493,10 +468,10 @@ class _GcnB16StackFunction(torch.autograd.Function):
         gbuf = torch.empty(sum(wn) + nl * D, **bf)
         g_w = [gbuf[sum(wn[:l]):sum(wn[:l + 1])].view(ws[l].shape[0], D) if need[3 + 2 * l] else None for l in range(nl)]
         g_b = [gbuf[sum(wn) + l * D:sum(wn) + (l + 1) * D] if (bs[l] is not None and need[4 + 2 * l]) else None for l in range(nl)]
-        args = _lib.GcnB16StackTrainArgs(B, n, I, D, nl, xr.data_ptr(), ldx, None, 0, adj3.data_ptr(), _ptr_array(ws), _ptr_array(bs),
+        args = _lib.GcnB16StackTrainArgs(B, n, I, D, nl, xr.data_ptr(), ldx, None, 0, adj3.data_ptr(), _lib.ptr_array(ws), _lib.ptr_array(bs),
                                          _ptrs(planes.data_ptr(), poff), _ptrs(acts.data_ptr(), [l * rows * o8 * 2 for l in range(nl)]), o8,
                                          gr.data_ptr(), ldg, _ptrs(g_sup.data_ptr(), [l * rows * o8 * 2 for l in range(nl)]), partial.data_ptr(),
-                                         _lib.ptr(g_x), i8, _ptr_array(g_w), _ptr_array(g_b), _zero_page(dev).data_ptr())
+                                         _lib.ptr(g_x), i8, _lib.ptr_array(g_w), _lib.ptr_array(g_b), _lib.zero_page(dev).data_ptr())
         with _lib.on_device(dev):
             _lib.check(L.recon_gcn_b16_stack_train_bwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_stack_train_bwd")
         if g_x is not None:
@@ -531,7 +506,7 @@ def gcn_stack(x, adj, layers):
               and all(l.in_features == D and l.out_features == D for l in layers[1:])
               and all(l.weight.dtype == torch.bfloat16 and (l.bias is None or l.bias.data_ptr() % 8 == 0) for l in layers)
               and adj.is_contiguous() and adj.data_ptr() % 8 == 0
-              and adj.numel() == B * n * n and B * n * max((I + 7) // 8 * 8, (D + 7) // 8 * 8) * 2 < 2 ** 31 - 1 and B <= 4 * _MAX_BATCH)
+              and adj.numel() == B * n * n and B * n * max((I + 7) // 8 * 8, (D + 7) // 8 * 8) * 2 < 2 ** 31 - 1 and B <= 4 * _lib.MAX_BATCH)
         if ok and need_grad:
             ok = (I + 7) // 8 * 8 <= 320 and os.environ.get("RECON_GCN_STACK_TRAIN", "1") != "0"
         elif ok:
@@ -620,10 +595,10 @@ class GraphConvolution(Module):
             return _GcnB16RaggedFunction.apply(input, adj.values, self.weight, self.bias, adj)
         fn = _GcnB16Function if input.dtype == torch.bfloat16 else _GcnFunction     # bf16 storage / fp32 accumulate (module.to(torch.bfloat16))
         extra = (not self.training,) if fn is _GcnB16Function else ()              # eval(): the repacked weight planes are kept across calls
-        if input.dim() == 3 and input.shape[0] > _MAX_BATCH:   # 16-bit grid dimension over the graphs; graphs are independent: run slices
+        if input.dim() == 3 and input.shape[0] > _lib.MAX_BATCH:   # 16-bit grid dimension over the graphs; graphs are independent: run slices
             B = input.shape[0]
-            return torch.cat([fn.apply(input[b0:b0 + _MAX_BATCH], adj[b0:b0 + _MAX_BATCH] if adj.dim() == 3 else adj, self.weight, self.bias, *extra)
-                              for b0 in range(0, B, _MAX_BATCH)], dim=0)
+            return torch.cat([fn.apply(input[b0:b0 + _lib.MAX_BATCH], adj[b0:b0 + _lib.MAX_BATCH] if adj.dim() == 3 else adj, self.weight, self.bias, *extra)
+                              for b0 in range(0, B, _lib.MAX_BATCH)], dim=0)
         if fn is _GcnB16Function and not torch.is_grad_enabled():
             # inference: nothing is recorded, so the autograd.Function machinery (~10 us per call, a third of this layer's host time at
             # cfg 3a) is skipped; the same forward runs with a context that saves nothing

@@ -22,12 +22,6 @@ _QUERY_CHUNK = 65535                                  # recon_convkb_scores: que
 ConvKBProjections = namedtuple("ConvKBProjections", "P_h P_r P_t b1 w2 b2 slope n_ent n_rel D")
 
 
-def _require_gpu(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("recon_amd: expected a GPU tensor (this package has no CPU path)")
-
-
 def _check_ids(triples, n_ent, n_rel, name):
     """One device reduction and one host sync: every id of the [rows, 3] triples inside its table."""
     if triples.numel():
@@ -38,7 +32,7 @@ def _check_ids(triples, n_ent, n_rel, name):
 
 def _check_triples(triples, table, n_ent, n_rel, name="test_triples"):
     """The triples as contiguous int64 [Q, 3] on the device of `table` (a GPU tensor), every id inside its table."""
-    _require_gpu(triples, table)
+    _lib.require_gpu(triples, table)
     if triples.dim() != 2 or triples.shape[1] != 3:
         raise ValueError("%s: [Q, 3] (head, relation, tail) expected" % name)
     t = triples.to(device=table.device, dtype=torch.int64).contiguous()
@@ -76,7 +70,7 @@ def _project(T, W1, k):
 def convkb_projections(entity_emb, relation_emb, convkb):
     """P_h = E W_h^T, P_r = Rel W_r^T, P_t = E W_t^T with fc1.weight = [W_h | W_r | W_t] (each [D, D], read in place: ldb = 3 D), plus b1, w2,
     b2 (device) and the LeakyReLU slope of convkb.nl1 (nn.LeakyReLU(): 0.01, whatever alpha_conv says — GAT/layers.py:24)."""
-    _require_gpu(entity_emb, relation_emb, convkb.fc1.weight, convkb.fc1.bias, convkb.fc2.weight, convkb.fc2.bias)
+    _lib.require_gpu(entity_emb, relation_emb, convkb.fc1.weight, convkb.fc1.bias, convkb.fc2.weight, convkb.fc2.bias)
     D = _check_shapes(entity_emb, relation_emb, convkb, "convkb_projections")
     E = entity_emb.detach().float().contiguous()
     R = relation_emb.detach().float().contiguous()

@@ -47,7 +47,7 @@ def sep_scorer(entity_emb, relation_emb, convkb, model_gat):
     D = _kge._check_shapes(entity_emb, relation_emb, convkb, "sep_scorer")
     N, R = entity_emb.shape[0], relation_emb.shape[0]
     W = check_ent2rel(model_gat, R, D)
-    _kge._require_gpu(entity_emb, relation_emb, W, convkb.fc1.weight, convkb.fc1.bias, convkb.fc2.weight, convkb.fc2.bias)
+    _lib.require_gpu(entity_emb, relation_emb, W, convkb.fc1.weight, convkb.fc1.bias, convkb.fc2.weight, convkb.fc2.bias)
     W1, b1, w2, b2, slope = _kge._detached_weights(convkb)
     P_r = _kge._project(relation_emb.detach().float().contiguous(), W1, 1)
     return SepScorer(entity_emb.detach().float().contiguous(), W.detach().float().contiguous(), W1, P_r, b1, w2, b2, slope, N, R, D)

@@ -20,17 +20,12 @@ import torch
 
 from . import _lib
 from . import kg_train as _kgt
-from .kg_eval import _check_ids, _check_shapes, _require_gpu
+from .kg_eval import _check_ids, _check_shapes
 from .kg_sep import MAX_D, check_ent2rel
 
+_FP32 = "%s: fp32 tables, W_ent2rel and weights expected"
 _W_FROZEN = ("model_gat.W_ent2rel requires grad, but the device step computes no gradient for it: train_conv never steps it (its optimizer "
              "holds model_conv.parameters() only, GAT_sep_space/main.py:808-809).  Freeze it first: model_gat.W_ent2rel.requires_grad_(False)")
-
-
-def _fp32(who, *tensors):
-    for t in tensors:
-        if t.dtype != torch.float32:
-            raise ValueError("%s: fp32 tables, W_ent2rel and weights expected" % who)
 
 
 def ent2rel_rows(E, W_ent2rel, triples, check_ids=True):
@@ -38,11 +33,11 @@ def ent2rel_rows(E, W_ent2rel, triples, check_ids=True):
     GAT_sep_space/models.py:312-320 builds per triple), remapped int64 [M, 3] = (m, r_m, M + m).  E fp32 [n_ent, D], W_ent2rel fp32
     [n_rel, D, D] laid out [in][out] (x . W), triples int32 / int64 [M, 3] on the device.  check_ids=False skips the range check (one host
     sync); an id outside its table then gives a NaN row."""
-    _require_gpu(E, W_ent2rel)
+    _lib.require_gpu(E, W_ent2rel)
     tri = _kgt._triples(triples, "triples")
     if E.dim() != 2 or W_ent2rel.dim() != 3 or tuple(W_ent2rel.shape[1:]) != (E.shape[1], E.shape[1]):
         raise ValueError("ent2rel_rows: E [n_ent, D] and W_ent2rel [n_rel, D, D] expected")
-    _fp32("ent2rel_rows", E, W_ent2rel)
+    _lib.require_gpu(E, W_ent2rel, dtype=torch.float32, wrong_dtype=(ValueError, _FP32 % "ent2rel_rows"))
     n_ent, n_rel, D = E.shape[0], W_ent2rel.shape[0], E.shape[1]
     if n_ent < 1 or n_rel < 1 or D < 1:
         raise ValueError("ent2rel_rows: non-empty tables expected")
@@ -77,8 +72,7 @@ def _params(model_conv, model_gat):
     if W.requires_grad:
         raise RuntimeError("recon_amd.kg_sep_train: " + _W_FROZEN)
     E, R, W1, b1, w2, b2, slope = _kgt._params(model_conv)
-    _require_gpu(W)
-    _fp32("recon_amd.kg_sep_train", W)
+    _lib.require_gpu(W, dtype=torch.float32, wrong_dtype=(ValueError, _FP32 % "recon_amd.kg_sep_train"))
     return E, R, W, W1, b1, w2, b2, slope
 
 
@@ -102,7 +96,7 @@ def sep_convkb_bce_loss(model_conv, model_gat, indices, values, ratio, check_ids
         raise ValueError("sep_convkb_bce_loss: ratio >= 1 expected (the reference's weights divide by 2 ratio)")
     E, R, W, W1, b1, w2, b2, slope = _params(model_conv, model_gat)
     tri = _kgt._triples(indices, "indices")
-    _require_gpu(values)
+    _lib.require_gpu(values)
     val = values.reshape(-1).to(torch.float32).contiguous()
     if val.numel() != tri.shape[0]:
         raise ValueError("sep_convkb_bce_loss: one value per triple expected")

@@ -14,7 +14,7 @@ frozen tables in place and reduce in one fixed order (csrc/kg_train.hip).  SpKBG
 import torch
 
 from . import _lib
-from .kg_eval import SLOT_TAIL, _check_ids, _check_shapes, _require_gpu, filter_keys
+from .kg_eval import SLOT_TAIL, _check_ids, _check_shapes, filter_keys
 
 MAX_D = 512                          # recon_convkb_train_*: 1 <= D <= MAX_D
 ENTITY_DRAW_CAP = 1 << 16            # recon_kg_corrupt: entity draws per row before it gives up
@@ -23,7 +23,7 @@ _FROZEN = ("the embedding tables must be frozen, as train_conv freezes them (GAT
 
 
 def _triples(triples, name):
-    _require_gpu(triples)
+    _lib.require_gpu(triples)
     if triples.dim() != 2 or triples.shape[1] != 3 or triples.dtype not in (torch.int32, torch.int64):
         raise ValueError("%s: int32 or int64 [rows, 3] (head, relation, tail) expected" % name)
     return triples.contiguous()
@@ -89,7 +89,7 @@ def corrupt_batch(positives, values, filt, ratio, generator=None, check_ids=True
     if ratio < 0:
         raise ValueError("corrupt_batch: ratio >= 0 expected")
     pos = _triples(positives, "positives")
-    _require_gpu(values)
+    _lib.require_gpu(values)
     val = values.reshape(-1).to(torch.float32).contiguous()
     if val.numel() != pos.shape[0]:
         raise ValueError("corrupt_batch: one value per positive expected")
@@ -127,11 +127,9 @@ def _params(model):
         raise RuntimeError("recon_amd.kg_train: " + _FROZEN)
     conv = model.convKB
     W1, b1, w2, b2 = conv.fc1.weight, conv.fc1.bias, conv.fc2.weight, conv.fc2.bias
-    _require_gpu(E, R, W1, b1, w2, b2)
+    _lib.require_gpu(E, R, W1, b1, w2, b2)
     _check_shapes(E, R, conv, "recon_amd.kg_train")
-    for p in (E, R, W1, b1, w2, b2):
-        if p.dtype != torch.float32:
-            raise ValueError("recon_amd.kg_train: fp32 tables and weights expected")
+    _lib.require_gpu(E, R, W1, b1, w2, b2, dtype=torch.float32, wrong_dtype=(ValueError, "recon_amd.kg_train: fp32 tables and weights expected"))
     return E.detach().contiguous(), R.detach().contiguous(), W1, b1, w2, b2, float(conv.nl1.negative_slope)
 
 
@@ -225,7 +223,7 @@ def convkb_bce_loss(model, indices, values, ratio, check_ids=True):
         raise ValueError("convkb_bce_loss: ratio >= 1 expected (the reference's weights divide by 2 ratio)")
     E, R, W1, b1, w2, b2, slope = _params(model)
     tri = _triples(indices, "indices")
-    _require_gpu(values)
+    _lib.require_gpu(values)
     val = values.reshape(-1).to(torch.float32).contiguous()
     if val.numel() != tri.shape[0]:
         raise ValueError("convkb_bce_loss: one value per triple expected")

@@ -21,14 +21,8 @@ import torch
 from . import _lib
 
 
-def _req(*ts, dtype=torch.float32):
-    for t in ts:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError("recon_amd: expected a GPU tensor (this package has no CPU path)")
-        if t.is_floating_point() and t.dtype != dtype:
-            raise TypeError("recon_amd: this call runs the %s kernels, got a %s tensor" % (dtype, t.dtype))
+# how this module's calls check dtypes: index tensors pass, and the message names the kernels the call runs
+_ONE_DTYPE = dict(floats_only=True, wrong_dtype=(TypeError, "recon_amd: this call runs the %(want)s kernels, got a %(got)s tensor"))
 
 
 def _float_dtype(*ts):
@@ -37,17 +31,6 @@ def _float_dtype(*ts):
     if len(dts) != 1 or next(iter(dts)) not in (torch.float32, torch.bfloat16):
         raise TypeError("recon_amd: the propagation kernels take float32 or bfloat16 tensors of ONE dtype, got %s" % sorted(map(str, dts)))
     return next(iter(dts))
-
-
-_ZEROS = {}
-
-
-def _zeros_page(dev):
-    """1 KiB of zero bytes per device: what the K tails of the bf16 GEMMs read (include/recon_hip.h: recon_prop_b16_args.zeros)."""
-    z = _ZEROS.get(dev)
-    if z is None:
-        z = _ZEROS[dev] = torch.zeros(1024, dtype=torch.uint8, device=dev)
-    return z
 
 
 # ------------------------------------------------------------------------------- host-side index builders
@@ -93,7 +76,7 @@ def build_adjecent_matrix(n, size=72):
 class _BlockAdjacency(torch.autograd.Function):
     @staticmethod
     def forward(ctx, T, identity, n):
-        _req(T, identity)
+        _lib.require_gpu(T, identity, dtype=torch.float32, **_ONE_DTYPE)
         T, identity = T.contiguous(), identity.contiguous()
         B = T.shape[0]
         dd = identity.shape[0]
@@ -126,7 +109,7 @@ class _BlockAdjacencyB16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, T, identity, n):
-        _req(T, identity, dtype=torch.bfloat16)
+        _lib.require_gpu(T, identity, dtype=torch.bfloat16, **_ONE_DTYPE)
         T, identity = T.contiguous(), identity.contiguous()
         B = T.shape[0]
         dd = identity.shape[0]
@@ -134,8 +117,8 @@ class _BlockAdjacencyB16(torch.autograd.Function):
             raise ValueError("T must hold B x n(n-1) transition matrices of %dx%d" % (dd, dd))
         A = torch.empty(B, n * dd, n * dd, dtype=torch.bfloat16, device=T.device)
         with _lib.on_device(T.device):
-            for b0 in range(0, B, _MAX_BATCH):
-                nb = min(B, b0 + _MAX_BATCH) - b0
+            for b0 in range(0, B, _lib.MAX_BATCH):
+                nb = min(B, b0 + _lib.MAX_BATCH) - b0
                 _lib.check(_lib.lib().recon_block_adjacency_b16_fwd(T[b0:].data_ptr(), identity.data_ptr(), nb, n, dd, A[b0:].data_ptr(),
                                                                     _lib.current_stream()), "recon_block_adjacency_b16_fwd")
         ctx.dims = (B, n, dd, tuple(T.shape))
@@ -145,8 +128,8 @@ class _BlockAdjacencyB16(torch.autograd.Function):
     def backward(ctx, gA):
         B, n, dd, tshape = ctx.dims
         gA = gA.contiguous()
-        if B > _MAX_BATCH:
-            raise NotImplementedError("bfloat16 block adjacency backward: more than %d graphs per call" % _MAX_BATCH)
+        if B > _lib.MAX_BATCH:
+            raise NotImplementedError("bfloat16 block adjacency backward: more than %d graphs per call" % _lib.MAX_BATCH)
         gT = torch.empty(tshape, dtype=torch.bfloat16, device=gA.device) if ctx.needs_input_grad[0] else None
         gI = torch.empty(dd, dd, dtype=torch.bfloat16, device=gA.device) if ctx.needs_input_grad[1] else None
         L = _lib.lib()
@@ -168,16 +151,6 @@ def build_block_adjacency(T, identity, n):
 
 
 # ------------------------------------------------------------------------------- P2
-_MAX_BATCH = 65535          # graphs per launch (recon_propagate_* / recon_gcn_*: RECON_ERR_UNSUPPORTED above)
-
-
-def _ptr_array(tensors):
-    arr = (C.c_void_p * len(tensors))()
-    for i, t in enumerate(tensors):
-        arr[i] = None if t is None else t.data_ptr()
-    return arr
-
-
 def _split_workspace(args, dev):
     """Workspace of the wide-state two-term forward (include/recon_hip.h: recon_prop_args.split_ws); None where that form does not
     exist.  Sets the two fields of `args`; the caller keeps the returned tensor alive across the launch."""
@@ -192,7 +165,7 @@ def _split_workspace(args, dev):
 class _Propagate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h0, act, head, tail, *adjs):
-        _req(h0, head, tail, *adjs)
+        _lib.require_gpu(h0, head, tail, *adjs, dtype=torch.float32, **_ONE_DTYPE)
         L = len(adjs)
         adj_shapes = [tuple(a.shape) for a in adjs]
         adjs = [a.contiguous().view(a.shape[0], a.shape[-2], a.shape[-1]) for a in adjs]   # accepts [B,1,S,S]
@@ -213,7 +186,7 @@ class _Propagate(torch.autograd.Function):
         out = torch.empty(B, Cn, L * dd, dtype=torch.float32, device=dev)
         need = any(ctx.needs_input_grad)
         hs = torch.empty(L, B, Cn, S, dtype=torch.float32, device=dev) if need else None
-        parr = _ptr_array(adjs)
+        parr = _lib.ptr_array(adjs)
         args = _lib.PropArgs(B, Cn, S, L, dd, _lib.ACT[act], parr, h0c.data_ptr(), h0_bs, head.data_ptr(),
                              tail.data_ptr(), idx_bs, out.data_ptr(), _lib.ptr(hs), None, None, None, None, 0)
         ws = _split_workspace(args, dev)       # wide states (160 < S <= 512): A_l pre-split into half terms, slice by slice
@@ -242,7 +215,7 @@ class _Propagate(torch.autograd.Function):
         g_adjs = [torch.empty(B, S, S, dtype=torch.float32, device=dev) if ctx.needs_input_grad[4 + l] else None
                   for l in range(L)]
         g_h = torch.empty(B, Cn, S, dtype=torch.float32, device=dev)
-        parr, garr = _ptr_array(adjs), _ptr_array(g_adjs)
+        parr, garr = _lib.ptr_array(adjs), _lib.ptr_array(g_adjs)
         fwd = _lib.PropArgs(B, Cn, S, L, dd, _lib.ACT[act], parr, h0c.data_ptr(), h0_bs, head.data_ptr(), tail.data_ptr(),
                             idx_bs, None, hs.data_ptr(), None, None, _lib.ptr(ctx.stats), None, 0)
         fwd.out = gout.data_ptr()      # unused by the backward; must be non-null for the argument check
@@ -269,9 +242,9 @@ class _Propagate(torch.autograd.Function):
 
 
 def _b16_args(B, Cn, S, L, dd, act, adjs, h0c, h0_bs, head, tail, idx_bs, out, hs, trans=None, identity=None):
-    return _lib.PropB16Args(B, Cn, S, L, dd, _lib.ACT[act], _ptr_array(adjs) if adjs is not None else None, h0c.data_ptr(), h0_bs,
+    return _lib.PropB16Args(B, Cn, S, L, dd, _lib.ACT[act], _lib.ptr_array(adjs) if adjs is not None else None, h0c.data_ptr(), h0_bs,
                             head.data_ptr(), tail.data_ptr(), idx_bs, _lib.ptr(out), _lib.ptr(hs),
-                            _ptr_array(trans) if trans is not None else None, _lib.ptr(identity), _zeros_page(h0c.device).data_ptr())
+                            _lib.ptr_array(trans) if trans is not None else None, _lib.ptr(identity), _lib.zero_page(h0c.device).data_ptr())
 
 
 _BLK_IDX = {}
@@ -306,7 +279,7 @@ class _PropagateB16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h0, act, head, tail, want_states, *adjs):
-        _req(h0, head, tail, *adjs, dtype=torch.bfloat16)
+        _lib.require_gpu(h0, head, tail, *adjs, dtype=torch.bfloat16, **_ONE_DTYPE)
         L = len(adjs)
         adj_shapes = [tuple(a.shape) for a in adjs]
         adjs = [a.contiguous().view(a.shape[0], a.shape[-2], a.shape[-1]) for a in adjs]
@@ -351,7 +324,7 @@ class _PropagateB16(torch.autograd.Function):
         ws = torch.empty(B, Cn, S, dtype=torch.bfloat16, device=dev)
         fwd = _b16_args(B, Cn, S, L, dd, act, adjs, h0c, h0_bs, head, tail, idx_bs, gout, hs)     # `out` is unused by the backward
         blk_idx = _index_blocks(head, tail, dd, S) if idx_bs == 0 else None
-        args = _lib.PropB16BwdArgs(fwd, gout.data_ptr(), _ptr_array(g_adjs), g_h.data_ptr(), ws.data_ptr(),
+        args = _lib.PropB16BwdArgs(fwd, gout.data_ptr(), _lib.ptr_array(g_adjs), g_h.data_ptr(), ws.data_ptr(),
                                    _lib.ptr(blk_idx[0]) if blk_idx else None, _lib.ptr(blk_idx[1]) if blk_idx else None, None, None, None, None)
         with _lib.on_device(dev):
             _lib.check(_lib.lib().recon_propagate_b16_bwd(C.byref(args), _lib.current_stream()), "recon_propagate_b16_bwd")
@@ -384,15 +357,15 @@ def propagate(adj_list, h0, nonlinearity, head_indices, tail_indices, return_sta
         raise NotImplementedError(nonlinearity)
     B = adj_list[0].shape[0] if adj_list else 0
     if return_states:
-        if _float_dtype(h0, *adj_list) != torch.bfloat16 or B > _MAX_BATCH:
-            raise NotImplementedError("return_states: bfloat16 tensors, at most %d graphs" % _MAX_BATCH)
+        if _float_dtype(h0, *adj_list) != torch.bfloat16 or B > _lib.MAX_BATCH:
+            raise NotImplementedError("return_states: bfloat16 tensors, at most %d graphs" % _lib.MAX_BATCH)
         res = _propagate_b16(adj_list, h0, nonlinearity, head_indices, tail_indices, return_states=True)
         return res if isinstance(res, tuple) else (res, None)          # None: the shape ran on the float32 kernels behind casts (no bf16 states)
     one = _propagate_b16 if _float_dtype(h0, *adj_list) == torch.bfloat16 else (lambda adjs, h, act, hi, ti: _Propagate.apply(h, act, hi, ti, *adjs))
-    if B > _MAX_BATCH:                    # the kernels index graphs with a 16-bit grid dimension; graphs are independent: run slices
+    if B > _lib.MAX_BATCH:                    # the kernels index graphs with a 16-bit grid dimension; graphs are independent: run slices
         outs = []
-        for b0 in range(0, B, _MAX_BATCH):
-            sl = slice(b0, min(B, b0 + _MAX_BATCH))
+        for b0 in range(0, B, _lib.MAX_BATCH):
+            sl = slice(b0, min(B, b0 + _lib.MAX_BATCH))
             hs = h0[sl] if h0.dim() == 4 else h0
             hi = head_indices[sl] if head_indices.dim() == 3 and head_indices.shape[0] == B else head_indices
             ti = tail_indices[sl] if tail_indices.dim() == 3 and tail_indices.shape[0] == B else tail_indices
@@ -408,7 +381,7 @@ class _PropagateBlocks(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h0, identity, act, head, tail, n, *Ts):
-        _req(h0, identity, head, tail, *Ts)
+        _lib.require_gpu(h0, identity, head, tail, *Ts, dtype=torch.float32, **_ONE_DTYPE)
         L = len(Ts)
         dd = identity.shape[0]
         B = Ts[0].shape[0]
@@ -425,7 +398,7 @@ class _PropagateBlocks(torch.autograd.Function):
         need = any(ctx.needs_input_grad)
         hs = torch.empty(L, B, Cn, S, dtype=torch.float32, device=dev) if need else None
         stats = torch.empty(B, 2 * L + 1, dtype=torch.float32, device=dev) if (need and S <= 160) else None
-        tarr = _ptr_array(Ts)
+        tarr = _lib.ptr_array(Ts)
         args = _lib.PropArgs(B, Cn, S, L, dd, _lib.ACT[act], None, h0c.data_ptr(), h0_bs, head.data_ptr(), tail.data_ptr(), idx_bs,
                              out.data_ptr(), _lib.ptr(hs), tarr, identity.data_ptr(), _lib.ptr(stats), None, 0)
         ws = _split_workspace(args, dev)
@@ -448,7 +421,7 @@ class _PropagateBlocks(torch.autograd.Function):
         g_I = torch.empty(dd, dd, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         g_h = torch.empty(B, Cn, S, dtype=torch.float32, device=dev)
         Lb = _lib.lib()
-        tarr, garr = _ptr_array(Ts), _ptr_array(g_Ts)
+        tarr, garr = _lib.ptr_array(Ts), _lib.ptr_array(g_Ts)
         fwd = _lib.PropArgs(B, Cn, S, L, dd, _lib.ACT[act], None, h0c.data_ptr(), h0_bs, head.data_ptr(), tail.data_ptr(), idx_bs,
                             gout.data_ptr(), hs.data_ptr(), tarr, identity.data_ptr(), _lib.ptr(stats), None, 0)
         if S > 160:
@@ -488,7 +461,7 @@ def blocks_mode_available(B, n, dd, h0, need_grad=True, L=1, T_list=None):
     """Whether propagate_blocks() runs fused (two-term f16 kernels for the forward and, when gradients are wanted, for the backward:
     2d = 16, n <= 9; forward only — inference — for 10 <= n <= 32; B within one launch).  `L` (hops) and `T_list` (the transition tensors:
     16-byte alignment) make the probe exact: the wide form's LDS budget grows with the hop count."""
-    if dd != 16 or n < 2 or n > 32 or B > _MAX_BATCH or B == 0 or os.environ.get("RECON_PROP_BLOCKS", "1") == "0":
+    if dd != 16 or n < 2 or n > 32 or B > _lib.MAX_BATCH or B == 0 or os.environ.get("RECON_PROP_BLOCKS", "1") == "0":
         return False
     if T_list is not None and any(t.data_ptr() % 16 for t in T_list):
         return False
@@ -501,7 +474,7 @@ def blocks_mode_available(B, n, dd, h0, need_grad=True, L=1, T_list=None):
 
 
 def _blocks_b16_available(B, n, dd, h0, T_list, identity):
-    if dd != 16 or n < 2 or n > 32 or B > _MAX_BATCH or B == 0 or os.environ.get("RECON_PROP_BLOCKS", "1") == "0":
+    if dd != 16 or n < 2 or n > 32 or B > _lib.MAX_BATCH or B == 0 or os.environ.get("RECON_PROP_BLOCKS", "1") == "0":
         return False
     if h0.data_ptr() % 16 or identity.data_ptr() % 16 or any(T.data_ptr() % 16 or not T.is_contiguous() for T in T_list):
         return False
@@ -511,7 +484,7 @@ def _blocks_b16_available(B, n, dd, h0, T_list, identity):
 
 def _propagate_blocks_b16(T_list, identity, n, h0, act, head, tail):
     """Inference: block adjacency + propagation in one launch on bfloat16 tensors; A_l is never written."""
-    _req(h0, identity, head, tail, *T_list, dtype=torch.bfloat16)
+    _lib.require_gpu(h0, identity, head, tail, *T_list, dtype=torch.bfloat16, **_ONE_DTYPE)
     L, dd, B = len(T_list), identity.shape[0], T_list[0].shape[0]
     S, Cn = n * dd, n * (n - 1)
     Ts = [t.contiguous().view(B, Cn, dd * dd) for t in T_list]
@@ -533,7 +506,7 @@ class _PropagateBlocksB16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h0, identity, act, head, tail, n, want_states, *Ts):
-        _req(h0, identity, head, tail, *Ts, dtype=torch.bfloat16)
+        _lib.require_gpu(h0, identity, head, tail, *Ts, dtype=torch.bfloat16, **_ONE_DTYPE)
         L, dd, B = len(Ts), identity.shape[0], Ts[0].shape[0]
         S, Cn = n * dd, n * (n - 1)
         t_shapes = [tuple(t.shape) for t in Ts]
@@ -574,7 +547,7 @@ class _PropagateBlocksB16(torch.autograd.Function):
         blk_idx = _index_blocks(head, tail, dd, S) if idx_bs == 0 else None
         args = _lib.PropB16BwdArgs(fwd, gout.data_ptr(), None, g_h.data_ptr(), ws.data_ptr(),
                                    _lib.ptr(blk_idx[0]) if blk_idx else None, _lib.ptr(blk_idx[1]) if blk_idx else None,
-                                   _ptr_array(g_Ts), _lib.ptr(g_I), _lib.ptr(diag), _lib.ptr(iws))
+                                   _lib.ptr_array(g_Ts), _lib.ptr(g_I), _lib.ptr(diag), _lib.ptr(iws))
         with _lib.on_device(dev):
             _lib.check(Lb.recon_propagate_b16_bwd(C.byref(args), _lib.current_stream()), "recon_propagate_b16_bwd (block mode)")
         g_h0 = None
@@ -585,7 +558,7 @@ class _PropagateBlocksB16(torch.autograd.Function):
 
 def _blocks_b16_trainable(B, n, dd, h0, T_list, identity):
     """Block mode with gradients: 2d = 16 and a state size the bfloat16 kernels take (S = 16 n: always a multiple of 8)."""
-    if dd != 16 or n < 2 or B > _MAX_BATCH or B == 0 or os.environ.get("RECON_PROP_BLOCKS", "1") == "0":
+    if dd != 16 or n < 2 or B > _lib.MAX_BATCH or B == 0 or os.environ.get("RECON_PROP_BLOCKS", "1") == "0":
         return False
     if h0.data_ptr() % 16 or identity.data_ptr() % 16 or any(T.data_ptr() % 16 for T in T_list):
         return False
@@ -632,7 +605,7 @@ def make_start_entity_embeddings(entity_embeddings, entity_pos_indices, unique_e
     """utils/context_utils.py:387-426, same argument list (unique_entities and the most-frequent-entity
     hint only steer a speed trick there and do not change the result).  Returns [B, C, 2dn, 1].
     Forward and backward are kernels; the gradient of `entity_embeddings` is a fixed-order segment sum (bitwise run-to-run)."""
-    _req(entity_embeddings, start_embedding_template)
+    _lib.require_gpu(entity_embeddings, start_embedding_template, dtype=torch.float32, **_ONE_DTYPE)
     n, d = max_num_nodes, embedding_dim
     B, Cn = entity_pos_indices.shape[:2]
     S = 2 * d * n

@@ -36,6 +36,34 @@ def test_library_exports_every_declared_symbol():
     assert L.recon_gat_bwd_partial_floats(8192, 32768, 200, 200, 200, 8) >= 256 * 1600
 
 
+# entry points pinned by name: the ConvKB training step (csrc/kg_train.hip) and the sep scorer's row kernel (csrc/kg_sep.hip)
+PINNED_SYMBOLS = ("recon_kg_corrupt", "recon_convkb_train_fwd_workspace_floats", "recon_convkb_train_fwd",
+                  "recon_convkb_train_bwd_workspace_floats", "recon_convkb_train_bwd", "recon_kgsep_ent2rel")
+
+
+def test_pinned_symbols_declared_exported_bound():
+    from recon_amd import _lib
+    header = open(os.path.join(ROOT, "include", "recon_hip.h")).read()
+    h = ctypes.CDLL(_lib.LIB_PATH)
+    bound = {s[0] for s in _lib.SYMBOLS}
+    for name in PINNED_SYMBOLS:
+        assert re.search(r"\b%s\(" % name, header), name
+        assert hasattr(h, name), name
+        assert name in bound, name
+    L = _lib.lib()
+    assert L.recon_version() == 2
+    assert L.recon_convkb_train_fwd_workspace_floats(5184, 200) >= 5184 // 32 + 1
+    assert L.recon_convkb_train_bwd_workspace_floats(5184, 200) >= 200 * 600
+    assert L.recon_convkb_train_bwd_workspace_floats(0, 200) == 0
+    fake = 16                                                                # never dereferenced: every call below returns before a launch
+    args = lambda M, D, ib: (fake, ib, M, fake, 10, fake, 3, D, fake, fake, fake, fake, None)
+    assert L.recon_kgsep_ent2rel(*args(4, 513, 8)) == -2                     # D above the limit
+    assert L.recon_kgsep_ent2rel(*args(4, 0, 8)) == -1
+    assert L.recon_kgsep_ent2rel(*args(4, 16, 2)) == -1                      # index width
+    assert L.recon_kgsep_ent2rel(*args(-1, 16, 8)) == -1
+    assert L.recon_kgsep_ent2rel(*args(0, 16, 8)) == 0                       # nothing to do
+
+
 def test_no_cpu_fallback():
     from recon_amd.gat_layers import SpGraphAttentionLayer, SpecialSpmmFinal
     from recon_amd.gcn_layers import GraphConvolution

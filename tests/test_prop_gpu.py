@@ -416,8 +416,8 @@ def test_gcn_beyond_4_gib_activations(dtype):
 
 def test_batches_above_the_grid_limit_run_in_slices(monkeypatch):
     """More than 65 535 graphs per call (the kernels' 16-bit grid dimension) are run in slices by the host side; here the limit is
-    lowered to 3 / 2 graphs: outputs and gradients of a 7-graph batch must equal the one-launch results."""
-    from recon_amd import propagation, gcn_layers
+    lowered to 3, then to 2 graphs: outputs and gradients of a 7-graph batch must equal the one-launch results both times."""
+    from recon_amd import _lib, gcn_layers
     from recon_amd.propagation import build_block_adjacency, propagate, make_start_embedding, get_head_indices, get_tail_indices
     d_ = dev()
     n, d, L, B = 4, 2, 2, 7
@@ -433,9 +433,8 @@ def test_batches_above_the_grid_limit_run_in_slices(monkeypatch):
     torch.manual_seed(0)
     layer = gcn_layers.GraphConvolution(6, 4).to(d_)
     res = []
-    for lim_p, lim_g in ((65535, 65535), (3, 2)):
-        monkeypatch.setattr(propagation, "_MAX_BATCH", lim_p)
-        monkeypatch.setattr(gcn_layers, "_MAX_BATCH", lim_g)
+    for lim in (65535, 3, 2):
+        monkeypatch.setattr(_lib, "MAX_BATCH", lim)
         Tl = [t.clone().to(d_).requires_grad_(True) for t in Ts]
         I = ident0.clone().to(d_).requires_grad_(True)
         h = h00.clone().to(d_).requires_grad_(True)
@@ -447,11 +446,12 @@ def test_batches_above_the_grid_limit_run_in_slices(monkeypatch):
         (og * Gg).sum().backward()
         res.append([out, h.grad, I.grad] + [t.grad for t in Tl] + [og, x.grad, adj.grad, layer.weight.grad.clone(), layer.bias.grad.clone()])
     names = ["out", "g_h0", "g_identity", "g_T0", "g_T1", "gcn out", "gcn g_x", "gcn g_adj", "gcn g_weight", "gcn g_bias"]
-    for nm, a_, b_ in zip(names, res[0], res[1]):
-        if nm in ("g_identity", "gcn g_weight", "gcn g_bias"):            # sums over the batch: slices add in a different order
-            close(b_, a_, atol=1e-5, rel_to_max=1e-5, what=nm)
-        else:
-            assert torch.equal(a_, b_), nm
+    for sliced in res[1:]:
+        for nm, a_, b_ in zip(names, res[0], sliced):
+            if nm in ("g_identity", "gcn g_weight", "gcn g_bias"):        # sums over the batch: slices add in a different order
+                close(b_, a_, atol=1e-5, rel_to_max=1e-5, what=nm)
+            else:
+                assert torch.equal(a_, b_), nm
 
 
 def test_gcn_inplace_edit_of_result_is_caught():
