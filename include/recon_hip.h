@@ -873,6 +873,35 @@ int recon_kgsep_scores(int64_t Q, const int64_t* triples, const int64_t* rel_ids
                        recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * E4  the stage-A translation loss of the GAT_sep_space tree (csrc/kg_sep.hip): batch_gat_loss, GAT_sep_space/main.py:347-391, with
+ *     gat_loss_func = nn.MarginRankingLoss(margin) (mean reduction).  triples int64 [M][3], M = n_pos (1 + reps): the positives, then reps
+ *     corrupted copies of the block (reps = 2 * valid_invalid_ratio_gat).  T [2 M][D] = recon_kgsep_ent2rel's rows of the batch, every
+ *     triple carried into its relation's space ONCE (the reference tiles the positives reps times first); Rel [n_relp][D].
+ *         x_i = (T[i] + Rel[r_i]) - T[M + i],  norm_i = |x_i|_1,  term_j = max(0, norm_{j mod n_pos} - norm_{n_pos + j} + margin), j < P = n_pos reps,
+ *         loss = mean_j term_j  (a NaN norm reaches its terms and the loss, and raises the device's NaN word, as recon_transe_margin_fwd does).
+ * ------------------------------------------------------------------------------------------*/
+/* Forward: norms [M], terms [P], loss [1].  Two launches; every sum has one order.  A relation id outside [0, n_relp) gives a NaN norm. */
+int recon_kgsep_gat_loss_fwd(const int64_t* triples, int64_t n_pos, int32_t reps, const float* T, const float* Rel, int64_t n_relp, int32_t D,
+                             float margin, float* norms, float* terms, float* loss, recon_stream_t stream);
+/* Backward through the norms, the relation-space map and tanh, from the upstream scalar g_loss [1] (device) and the forward's T and terms:
+ *     c_i = +(g / P) #{k : term_{k n_pos + i} > 0} (positive i), -(g / P) [term_{i - n_pos} > 0] (negative i),  gx_i = c_i sign(x_i), sign(0) = 0,
+ *     gpre[i] = gx_i (1 - T[i]^2),  gpre[M + i] = -gx_i (1 - T[M + i]^2),
+ *     g_rows [2 M][D]:       g_rows[item] = gpre[item] W_ent2rel[r]^T  (the caller sums them by entity id into the entity table's gradient),
+ *     g_W    [n_rel][D][D]:  g_W[r] = sum over the items of relation r of E[e_item]^T gpre[item]  (zeros for a relation without items),
+ *     g_Rel  [n_relp][D]:    g_Rel[r] = sum over the triples of relation r of gx_i; rows r >= n_rel are NOT written.
+ * A pair is active where its term is > 0 (torch's clamp_min backward also passes a pre-clamp value of exactly 0: the two differ only there).
+ * Each of the three may be NULL: its work is skipped.  order / seg: the relation-ordered walk recon_kgsep_ent2rel took.  gpre is formed
+ * on the fly; both products run on v_mfma_f32_16x16x4_f32 in fp32.  Every output element is one k-ordered chain over the walk, written
+ * once by one lane: no partial sums across workgroups, no arrival counters, no atomics, bitwise identical from run to run.  An item with
+ * an id outside its table gets a NaN row of g_rows and adds nothing to g_W / g_Rel.  1 <= D <= 512 (RECON_ERR_UNSUPPORTED above).
+ * workspace: recon_kgsep_gat_loss_bwd_workspace_bytes(M) bytes, 8-byte aligned, any contents.  Up to three launches. */
+size_t recon_kgsep_gat_loss_bwd_workspace_bytes(int64_t M);
+int recon_kgsep_gat_loss_bwd(const int64_t* triples, int64_t n_pos, int32_t reps, const float* E, int64_t n_ent, const float* Rel, int64_t n_relp,
+                             const float* W_ent2rel, int64_t n_rel, int32_t D, const int64_t* order, const int64_t* seg, const float* T,
+                             const float* terms, const float* g_loss, void* workspace, size_t workspace_bytes, float* g_rows, float* g_W,
+                             float* g_Rel, recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
  *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
  * ------------------------------------------------------------------------------------------*/

@@ -254,6 +254,11 @@ SYMBOLS = [
                                    c_f32p, c_f32p, C.c_float, c_i64p, c_i64p, c_i64p, c_f32p, C.c_size_t, c_i64p, c_f32p, C.c_void_p]),
     ("recon_kgsep_scores", C.c_int, [C.c_int64, c_i64p, c_i64p, C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int32, c_f32p, c_f32p,
                                      c_f32p, C.c_float, c_f32p, C.c_int64, C.c_void_p]),
+    ("recon_kgsep_gat_loss_fwd", C.c_int, [c_i64p, C.c_int64, C.c_int32, c_f32p, c_f32p, C.c_int64, C.c_int32, C.c_float, c_f32p, c_f32p, c_f32p,
+                                           C.c_void_p]),
+    ("recon_kgsep_gat_loss_bwd_workspace_bytes", C.c_size_t, [C.c_int64]),
+    ("recon_kgsep_gat_loss_bwd", C.c_int, [c_i64p, C.c_int64, C.c_int32, c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int32, c_i64p,
+                                           c_i64p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     ("recon_kg_corrupt", C.c_int, [C.c_void_p, C.c_int32, c_f32p, C.c_int64, C.c_int32, c_i64p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64,
                                    c_i64p, c_f32p, C.c_void_p, C.c_void_p]),
     ("recon_convkb_train_fwd_workspace_floats", C.c_size_t, [C.c_int64, C.c_int32]),

@@ -167,6 +167,22 @@ int kgs_launch(const float* E, int64_t n_rows, const int64_t* ids, int64_t U, co
     return hipGetLastError() == hipSuccess ? RECON_OK : RECON_ERR_LAUNCH;
 }
 
+// The tile of workgroup blockIdx.x in the relation-ordered walk over `items` items: tile[0] = its relation (found by binary search on t),
+// tile[1] = its first position in order, tile[2] = the end of the relation's items (tile[1] >= tile[2]: no tile).  seg is clamped to
+// [0, items].
+__device__ __forceinline__ void kgs_find_tile(int64_t (&tile)[3], const int64_t* __restrict__ seg, int64_t n_rel, int64_t items, int BM) {
+    const auto seg_at = [&](int64_t r) { const int64_t v = seg[r]; return v < 0 ? int64_t(0) : v > items ? items : v; };
+    const int64_t b = blockIdx.x;
+    int64_t lo = 0, hi = n_rel;                                            // the last r with t(r) <= b (t(0) = 0)
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) / 2;
+        if (seg_at(mid) / BM + mid <= b) lo = mid; else hi = mid;
+    }
+    tile[0] = lo;
+    tile[1] = seg_at(lo) + (b - seg_at(lo) / BM - lo) * BM;
+    tile[2] = seg_at(lo + 1);
+}
+
 // k_kgs_ent2rel: grid.x is the bound ceil(2 M / BM) + n_rel.  Relation r's tiles are workgroups [t(r), t(r + 1)) with t(r) = seg[r] / BM + r
 // (t(r + 1) - t(r) >= ceil(items of r / BM)); a workgroup finds its relation by binary search on t and leaves when its tile is empty.
 // Item i < M is the head of triple i, item M + i its tail; T row i belongs to item i.  An item whose entity id lies outside E or whose
@@ -182,18 +198,7 @@ __global__ void __launch_bounds__(kTblThreads) k_kgs_ent2rel(const void* __restr
     __shared__ int64_t item[BM], ent[BM];                                  // item of each tile row (-1: none); its entity row (-1: NaN row)
     const int ld = kgs_ld(D), Dk = (D + 15) / 16 * 16;
     const int64_t items = 2 * M;
-    const auto seg_at = [&](int64_t r) { const int64_t v = seg[r]; return v < 0 ? int64_t(0) : v > items ? items : v; };
-    if (threadIdx.x == 0) {
-        const int64_t b = blockIdx.x;
-        int64_t lo = 0, hi = n_rel;                                        // the last r with t(r) <= b (t(0) = 0)
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) / 2;
-            if (seg_at(mid) / BM + mid <= b) lo = mid; else hi = mid;
-        }
-        tile[0] = lo;
-        tile[1] = seg_at(lo) + (b - seg_at(lo) / BM - lo) * BM;
-        tile[2] = seg_at(lo + 1);
-    }
+    if (threadIdx.x == 0) kgs_find_tile(tile, seg, n_rel, items, BM);
     __syncthreads();
     const int64_t rel = tile[0], p0 = tile[1], p_end = tile[2];
     if (p0 >= p_end) return;
@@ -252,6 +257,297 @@ int kge2r_launch(const void* triples, int32_t index_bytes, int64_t M, const floa
     return hipGetLastError() == hipSuccess ? RECON_OK : RECON_ERR_LAUNCH;
 }
 
+
+// ---- the stage-A translation loss of the GAT_sep_space tree (GAT_sep_space/main.py:347-391) --------------------------
+// With T = recon_kgsep_ent2rel's rows of the batch's M = n_pos (1 + reps) triples (each ONCE: the reference tiles the positives reps times
+// before it multiplies them), x_i = (T[i] + Rel[r_i]) - T[M + i], norm_i = |x_i|_1, term_j = max(0, norm_{j mod n_pos} - norm_{n_pos + j} +
+// margin), loss = mean_j term_j.
+//   k_kgsl_norms   a wave per triple: norm_i (lane l adds columns l, l + 64, ... in order, then the fixed butterfly of group_sum)
+//   k_kgsl_terms   one workgroup: the terms and their mean in the order of loss.hip's k_transe_mean
+// Backward, from the upstream scalar g, T and the terms; nothing per tiled copy, no [rows, D] block of the reference's gradient rows:
+// A pair counts as active where its term is > 0, as in loss.hip; torch's clamp_min backward also passes the gradient at a pre-clamp value of
+// exactly 0, so there (and only there) this path and the op-sequence fallback differ.
+//   k_kgsl_prep    per position p of the relation-ordered walk: its entity row and c = +-(g / P) #active pairs of its triple (- for a tail
+//                  item: gpre[M + i] = -gx_i (1 - T[M + i]^2))
+//   k_kgsl_rows    the walk of k_kgs_ent2rel: a tile of up to 16 RB items of one relation stages gpre = c sign(x) (1 - T^2) in LDS (formed on
+//                  the fly) and writes g_rows[item] = gpre W_r^T; B of a lane is four consecutive floats of one row of W_r (one b128 load)
+//   k_kgsl_wgrad   g_W[r] = sum over r's items of E[e]^T gpre and g_Rel[r] = sum over r's head items of gx: one workgroup per (relation, 64
+//                  rows of g_W[r], 32 columns), which walks ALL the relation's items in order, 64 at a time: the MFMA k index is the item, so
+//                  every element is one k-ordered chain written once by one lane — no partials, no arrival counters, no atomics — and a
+//                  relation that owns the whole batch still spreads over ceil(D / 64) ceil(D / 32) workgroups (28 at D = 200).
+constexpr int kWgItems = 64, kWgRows = 64, kWgCols = 32, kWgLdE = 80, kWgLdG = 48;   // LDS strides: the 4 items of an MFMA step 16 banks apart (64 banks of 4 B)
+
+__global__ void __launch_bounds__(256) k_kgsl_norms(const int64_t* __restrict__ tri, int64_t M, const float* __restrict__ T,
+                                                     const float* __restrict__ Rel, int64_t n_relp, int D, float* __restrict__ norms) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 4 + threadIdx.x / kWave;
+    if (i >= M) return;
+    const int64_t r = tri[3 * i + 1];
+    float s = 0.f;
+    if (r < 0 || r >= n_relp) {
+        s = __builtin_nanf("");                                            // a relation outside Rel: NaN, nothing read
+    } else {
+        const float* a = T + i * D; const float* b = Rel + r * D; const float* t = T + (M + i) * D;
+        for (int c = lane; c < D; c += kWave) s += fabsf((a[c] + b[c]) - t[c]);
+    }
+    s = group_sum<64>(s);
+    if (lane == 0) norms[i] = s;
+}
+
+__global__ void __launch_bounds__(256) k_kgsl_terms(const float* __restrict__ norms, int64_t n_pos, int64_t P, float margin, float* __restrict__ terms,
+                                                     float* __restrict__ loss, int32_t* __restrict__ nan_word) {
+    __shared__ float red[256];
+    float s = 0.f;
+    for (int64_t j = threadIdx.x; j < P; j += 256) {                       // thread t: terms t, t + 256, ... in order
+        // clamp_min of the reference propagates NaN (GAT_sep_space/main.py:389 then asserts on the loss); fmaxf alone would return the 0
+        const float v = norms[j % n_pos] - norms[n_pos + j] + margin;
+        const float term = (v != v) ? v : fmaxf(0.f, v);
+        if (nan_word && !(fabsf(v) <= 3.0e38f)) *nan_word = 1;
+        terms[j] = term;
+        s += term;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = red[0] / static_cast<float>(P);
+}
+
+__global__ void __launch_bounds__(256) k_kgsl_prep(const int64_t* __restrict__ tri, int64_t M, int64_t n_pos, int reps, int64_t n_ent, int64_t n_relw,
+                                                    const int64_t* __restrict__ order, const float* __restrict__ terms,
+                                                    const float* __restrict__ g_loss, int64_t* __restrict__ pent, float* __restrict__ pcf) {
+    const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (p >= 2 * M) return;
+    const int64_t it = order[p];
+    int64_t e = -1;
+    float c = 0.f;
+    if (it >= 0 && it < 2 * M) {
+        const int64_t i = it < M ? it : it - M, r = tri[3 * i + 1];
+        e = tri[3 * i + (it < M ? 0 : 2)];
+        if (e < 0 || e >= n_ent || r < 0 || r >= n_relw) e = -1;          // n_relw: rows of both W_ent2rel and Rel
+        const float w = g_loss[0] / static_cast<float>(n_pos * reps);
+        if (i < n_pos) {
+            int cnt = 0;
+            for (int k = 0; k < reps; ++k) cnt += terms[k * n_pos + i] > 0.f ? 1 : 0;
+            c = w * static_cast<float>(cnt);
+        } else {
+            c = -(w * (terms[i - n_pos] > 0.f ? 1.f : 0.f));
+        }
+        if (it >= M) c = -c;
+    }
+    pent[p] = e;
+    pcf[p] = c;
+}
+
+// gpre of column k of item `it` (triple i, coefficient c with the item's sign): x recomputed as the forward does; gx = c sign(x), sign(0) =
+// sign(NaN) = 0 (torch's sgn); *gx_out receives it
+__device__ __forceinline__ float kgsl_gpre(const float* __restrict__ T, const float* __restrict__ rel_row, int64_t M, int D, int64_t it, float c, int k,
+                                           float* gx_out) {
+    const int64_t i = it < M ? it : it - M;
+    const float a = T[i * D + k], b = T[(M + i) * D + k];
+    const float x = (a + rel_row[k]) - b;
+    const float gx = c * (x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f));
+    const float t = it < M ? a : b;
+    if (gx_out) *gx_out = gx;
+    return gx * (1.f - t * t);
+}
+
+template <int RB, bool VEC>
+__global__ void __launch_bounds__(kTblThreads) k_kgsl_rows(int64_t M, const float* __restrict__ T, const float* __restrict__ Rel,
+                                                           const float* __restrict__ W, int64_t n_rel, int D, const int64_t* __restrict__ order,
+                                                           const int64_t* __restrict__ seg, const int64_t* __restrict__ pent,
+                                                           const float* __restrict__ pcf, float* __restrict__ g_rows) {
+    extern __shared__ __attribute__((aligned(16))) float kgs_sm[];
+    constexpr int BM = 16 * RB;
+    __shared__ int64_t tile[3];
+    __shared__ int64_t item[BM];                                           // item of each tile row (-1: none)
+    __shared__ float cf[BM];                                               // its signed coefficient (NaN: an id outside its table)
+    const int ld = kgs_ld(D), Dk = (D + 15) / 16 * 16, NB = Dk / 16;
+    const int64_t items = 2 * M;
+    if (threadIdx.x == 0) kgs_find_tile(tile, seg, n_rel, items, BM);
+    __syncthreads();
+    const int64_t rel = tile[0], p0 = tile[1], p_end = tile[2];
+    if (p0 >= p_end) return;
+    if (threadIdx.x < BM) {
+        const int m = threadIdx.x;
+        int64_t it = -1;
+        float c = 0.f;
+        if (p0 + m < p_end) {
+            it = order[p0 + m];
+            if (it < 0 || it >= items) it = -1;                            // a malformed order writes nothing
+            else c = pent[p0 + m] >= 0 ? pcf[p0 + m] : __builtin_nanf("");
+        }
+        item[m] = it;
+        cf[m] = c;
+    }
+    __syncthreads();
+    float* Gs = kgs_sm;                                                    // [BM][ld]: gpre rows of the tile, zero padded
+    const float* rel_row = Rel + rel * D;
+    for (int i = threadIdx.x; i < BM * Dk; i += kTblThreads) {
+        const int m = i / Dk, k = i % Dk;
+        const int64_t it = item[m];
+        float v = 0.f;
+        if (it >= 0 && k < D) {
+            const float c = cf[m];
+            v = (c == c) ? kgsl_gpre(T, rel_row, M, D, it, c, k, nullptr) : c;
+        }
+        Gs[m * ld + k] = v;
+    }
+    __syncthreads();
+    // g_rows[item] = gpre W_r^T: B[k][n] = W_r[n][k], four consecutive floats of row n per lane and k block
+    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave, c16 = lane & 15, g = lane >> 4;
+    const float* Wr = W + rel * D * D;
+    for (int nb = wave; nb < NB; nb += kTblWaves) {
+        const int n = nb * 16 + c16;
+        const float* wrow = Wr + static_cast<int64_t>(n < D ? n : 0) * D;
+        f32x4 acc[RB];
+#pragma unroll
+        for (int i = 0; i < RB; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int k0 = 0; k0 < Dk; k0 += 16) {
+            const int kb = k0 + 4 * g;
+            float b[4];
+            if constexpr (VEC) {                                           // D % 4 == 0: kb < D implies kb + 3 < D
+                float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (kb < D && n < D) w4 = *reinterpret_cast<const float4*>(wrow + kb);
+                b[0] = w4.x; b[1] = w4.y; b[2] = w4.z; b[3] = w4.w;
+            } else {
+                kgs_load_b(b, wrow + kb, 1, kb, n, D);
+            }
+#pragma unroll
+            for (int i = 0; i < RB; ++i) acc[i] = kgs_mfma4(*reinterpret_cast<const float4*>(&Gs[(16 * i + c16) * ld + kb]), b, acc[i]);
+        }
+        if (n < D)
+#pragma unroll
+            for (int i = 0; i < RB; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int64_t it = item[16 * i + 4 * g + j];
+                    if (it >= 0) g_rows[it * D + n] = acc[i][j];
+                }
+    }
+}
+
+// grid.x = n_rel * RG * CG (RG = ceil(D / 64) row groups when g_W is wanted, else 1; CG = ceil(D / 32) column groups)
+__global__ void __launch_bounds__(256) k_kgsl_wgrad(int64_t M, const float* __restrict__ E, const float* __restrict__ T, const float* __restrict__ Rel,
+                                                     int64_t n_relp, int D, int RG, int CG, const int64_t* __restrict__ order,
+                                                     const int64_t* __restrict__ seg, const int64_t* __restrict__ pent, const float* __restrict__ pcf,
+                                                     float* __restrict__ g_W, float* __restrict__ g_Rel) {
+    __shared__ float Ea[kWgItems * kWgLdE];                                // [item][row of the group]: E[e_item][row0 + .]
+    __shared__ float Gs[kWgItems * kWgLdG];                                // [item][column of the group]: gpre
+    __shared__ float Xs[kWgItems * kWgCols];                               // [item][column]: gx of a head item, 0 of a tail item
+    __shared__ int64_t s_it[kWgItems], s_ent[kWgItems];
+    __shared__ float s_cf[kWgItems];
+    const int64_t b = blockIdx.x, items = 2 * M;
+    const int cg = static_cast<int>(b % CG), rg = static_cast<int>((b / CG) % RG);
+    const int64_t rel = b / (static_cast<int64_t>(CG) * RG);
+    const int row0 = rg * kWgRows, col0 = cg * kWgCols;
+    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave, c16 = lane & 15, g = lane >> 4;
+    const auto seg_at = [&](int64_t r) { const int64_t v = seg[r]; return v < 0 ? int64_t(0) : v > items ? items : v; };
+    const int64_t p_begin = seg_at(rel), p_end = seg_at(rel + 1);
+    const bool want_rel = g_Rel && rg == 0 && rel < n_relp;
+    const bool mma = g_W && row0 + 16 * wave < D;                          // this wave's 16 rows of g_W[rel]
+    const float* rel_row = Rel + (rel < n_relp ? rel : 0) * D;
+    f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    float gr = 0.f;                                                        // thread c < 32: g_Rel[rel][col0 + c]
+    const float rel_col = rel_row[col0 + threadIdx.x % kWgCols < D ? col0 + threadIdx.x % kWgCols : 0];   // this thread's column of Rel[rel]
+    // the ids and coefficient of item threadIdx.x of a step, read one step ahead (behind the MFMAs of the step before)
+    int64_t n_it = -1, n_ent_row = -1;
+    float n_cf = 0.f;
+    const auto fetch_ids = [&](int64_t p0) {
+        n_it = n_ent_row = -1;
+        n_cf = 0.f;
+        if (threadIdx.x < kWgItems && p0 + threadIdx.x < p_end) {
+            n_it = order[p0 + threadIdx.x];
+            n_ent_row = pent[p0 + threadIdx.x];
+            n_cf = pcf[p0 + threadIdx.x];
+            if (n_it < 0 || n_it >= items || n_ent_row < 0) n_it = n_ent_row = -1;   // a malformed order or an id outside its table adds nothing
+        }
+    };
+    fetch_ids(p_begin);
+    for (int64_t p0 = p_begin; p0 < p_end; p0 += kWgItems) {
+        if (threadIdx.x < kWgItems) { s_it[threadIdx.x] = n_it; s_ent[threadIdx.x] = n_ent_row; s_cf[threadIdx.x] = n_cf; }
+        __syncthreads();
+        fetch_ids(p0 + kWgItems);
+        // every global load of the step is issued before the first is used: the ids come from LDS, an id that adds nothing reads row 0 and
+        // is masked afterwards (no branch between the loads)
+        constexpr int NE = kWgItems * kWgRows / 256, NG = kWgItems * kWgCols / 256;
+        float ea[NE], ta[NG], tb[NG];
+        if (g_W) {
+#pragma unroll
+            for (int u = 0; u < NE; ++u) {                                 // element (item m, row k) = (wave + 4 u, lane)
+                const int64_t e = s_ent[wave + 4 * u];
+                ea[u] = E[(e >= 0 ? e : 0) * D + (row0 + lane < D ? row0 + lane : 0)];
+            }
+        }
+        const int gk = threadIdx.x % kWgCols, gm = threadIdx.x / kWgCols, gcol = col0 + gk < D ? col0 + gk : 0;
+#pragma unroll
+        for (int u = 0; u < NG; ++u) {                                     // element (item m, column k) = (gm + 8 u, gk)
+            const int64_t it = s_it[gm + 8 * u], i = it < 0 ? 0 : (it < M ? it : it - M);
+            ta[u] = T[i * D + gcol];
+            tb[u] = T[(M + i) * D + gcol];
+        }
+        if (g_W) {
+#pragma unroll
+            for (int u = 0; u < NE; ++u) Ea[(wave + 4 * u) * kWgLdE + lane] = (s_ent[wave + 4 * u] >= 0 && row0 + lane < D) ? ea[u] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < NG; ++u) {
+            const int m = gm + 8 * u;
+            const int64_t it = s_it[m];
+            float v = 0.f, gx = 0.f;
+            if (it >= 0 && col0 + gk < D) {                                // kgsl_gpre on the loaded values
+                const float x = (ta[u] + rel_col) - tb[u];
+                gx = s_cf[m] * (x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f));
+                const float t = it < M ? ta[u] : tb[u];
+                v = gx * (1.f - t * t);
+            }
+            Gs[m * kWgLdG + gk] = v;
+            Xs[m * kWgCols + gk] = it < M ? gx : 0.f;
+        }
+        __syncthreads();
+        if (mma) {
+#pragma unroll 4
+            for (int s = 0; s < kWgItems / 4; ++s) {                       // MFMA step s: items 4 s + g, in walk order
+                const int m = 4 * s + g;
+                const float a = Ea[m * kWgLdE + 16 * wave + c16];
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Gs[m * kWgLdG + c16], acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Gs[m * kWgLdG + 16 + c16], acc[1], 0, 0, 0);
+            }
+        }
+        if (want_rel && threadIdx.x >= 192 && threadIdx.x < 192 + kWgCols) {   // the last wave (the first to run out of g_W rows)
+            const int k = threadIdx.x - 192;
+            for (int m = 0; m < kWgItems; ++m) gr += Xs[m * kWgCols + k];
+        }
+        __syncthreads();
+    }
+    if (mma)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int row = row0 + 16 * wave + 4 * g + j, col = col0 + 16 * cb + c16;
+                if (row < D && col < D) g_W[(rel * D + row) * D + col] = acc[cb][j];
+            }
+    if (want_rel && threadIdx.x >= 192 && threadIdx.x < 192 + kWgCols && col0 + threadIdx.x - 192 < D)
+        g_Rel[rel * D + col0 + threadIdx.x - 192] = gr;
+}
+
+template <int RB, bool VEC>
+int kgsl_rows_launch(int64_t M, const float* T, const float* Rel, const float* W, int64_t n_rel, int32_t D, const int64_t* order, const int64_t* seg,
+                     const int64_t* pent, const float* pcf, float* g_rows, hipStream_t s) {
+    const size_t lds = static_cast<size_t>(16 * RB) * kgs_ld(D) * sizeof(float);
+    const int64_t blocks = ceil_div64(2 * M, 16 * RB) + n_rel;
+    if (blocks > 0x7fffffffLL) return RECON_ERR_UNSUPPORTED;
+    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kgsl_rows<RB, VEC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               static_cast<int>(lds)) != hipSuccess)
+        return RECON_ERR_LAUNCH;
+    hipLaunchKernelGGL((k_kgsl_rows<RB, VEC>), dim3(static_cast<unsigned>(blocks)), dim3(kTblThreads), lds, s, M, T, Rel, W, n_rel, D, order, seg, pent,
+                       pcf, g_rows);
+    return hipGetLastError() == hipSuccess ? RECON_OK : RECON_ERR_LAUNCH;
+}
+
 }  // namespace
 }  // namespace recon
 
@@ -279,4 +575,54 @@ extern "C" int recon_kgsep_tables(const float* E, int64_t n_rows, const int64_t*
         case 2: return recon::kgs_launch<2>(E, n_rows, ids, U, W_ent2rel, n_rel, rel_ids, Rc, W1, D, P_h, P_t, s);
         default: return recon::kgs_launch<1>(E, n_rows, ids, U, W_ent2rel, n_rel, rel_ids, Rc, W1, D, P_h, P_t, s);
     }
+}
+
+extern "C" int recon_kgsep_gat_loss_fwd(const int64_t* triples, int64_t n_pos, int32_t reps, const float* T, const float* Rel, int64_t n_relp, int32_t D,
+                                        float margin, float* norms, float* terms, float* loss, recon_stream_t stream) {
+    if (n_pos < 1 || reps < 1 || n_relp < 1 || D < 1 || !triples || !T || !Rel || !norms || !terms || !loss) return RECON_ERR_INVALID;
+    if (n_pos > 0x7fffffffLL / (reps + 1)) return RECON_ERR_UNSUPPORTED;
+    const int64_t M = n_pos * (reps + 1), P = n_pos * reps;
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(recon::k_kgsl_norms, dim3(static_cast<unsigned>(ceil_div64(M, 4))), dim3(256), 0, s, triples, M, T, Rel, n_relp, D, norms);
+    hipLaunchKernelGGL(recon::k_kgsl_terms, dim3(1), dim3(256), 0, s, norms, n_pos, P, margin, terms, loss, recon::nan_flag());
+    RECON_CHECK_LAUNCH();
+    return RECON_OK;
+}
+
+extern "C" size_t recon_kgsep_gat_loss_bwd_workspace_bytes(int64_t M) { return M < 1 ? 0 : static_cast<size_t>(2 * M) * (sizeof(int64_t) + sizeof(float)); }
+
+extern "C" int recon_kgsep_gat_loss_bwd(const int64_t* triples, int64_t n_pos, int32_t reps, const float* E, int64_t n_ent, const float* Rel, int64_t n_relp,
+                                        const float* W_ent2rel, int64_t n_rel, int32_t D, const int64_t* order, const int64_t* seg, const float* T,
+                                        const float* terms, const float* g_loss, void* workspace, size_t workspace_bytes, float* g_rows, float* g_W,
+                                        float* g_Rel, recon_stream_t stream) {
+    if (n_pos < 1 || reps < 1 || n_ent < 1 || n_relp < 1 || n_rel < 1 || D < 1) return RECON_ERR_INVALID;
+    if (D > recon::kTblMaxD || n_pos > 0x7fffffffLL / (reps + 1)) return RECON_ERR_UNSUPPORTED;
+    if (!triples || !E || !Rel || !W_ent2rel || !order || !seg || !T || !terms || !g_loss || !workspace) return RECON_ERR_INVALID;
+    const int64_t M = n_pos * (reps + 1);
+    if (workspace_bytes < recon_kgsep_gat_loss_bwd_workspace_bytes(M)) return RECON_ERR_WORKSPACE;
+    if (!g_rows && !g_W && !g_Rel) return RECON_OK;
+    hipStream_t s = as_stream(stream);
+    int64_t* pent = static_cast<int64_t*>(workspace);
+    float* pcf = reinterpret_cast<float*>(pent + 2 * M);
+    hipLaunchKernelGGL(recon::k_kgsl_prep, dim3(static_cast<unsigned>(ceil_div64(2 * M, 256))), dim3(256), 0, s, triples, M, n_pos, reps, n_ent,
+                       n_rel < n_relp ? n_rel : n_relp, order, terms, g_loss, pent, pcf);
+    RECON_CHECK_LAUNCH();
+    if (g_rows) {
+        const bool vec = D % 4 == 0 && !(reinterpret_cast<uintptr_t>(W_ent2rel) & 15);
+        const int rb = recon::kge2r_row_blocks(D);
+        const int rc = rb == 4 ? (vec ? recon::kgsl_rows_launch<4, true>(M, T, Rel, W_ent2rel, n_rel, D, order, seg, pent, pcf, g_rows, s)
+                                      : recon::kgsl_rows_launch<4, false>(M, T, Rel, W_ent2rel, n_rel, D, order, seg, pent, pcf, g_rows, s))
+                               : (vec ? recon::kgsl_rows_launch<2, true>(M, T, Rel, W_ent2rel, n_rel, D, order, seg, pent, pcf, g_rows, s)
+                                      : recon::kgsl_rows_launch<2, false>(M, T, Rel, W_ent2rel, n_rel, D, order, seg, pent, pcf, g_rows, s));
+        if (rc != RECON_OK) return rc;
+    }
+    if (g_W || g_Rel) {
+        const int RG = g_W ? (D + recon::kWgRows - 1) / recon::kWgRows : 1, CG = (D + recon::kWgCols - 1) / recon::kWgCols;
+        const int64_t blocks = n_rel * RG * CG;
+        if (blocks > 0x7fffffffLL) return RECON_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(recon::k_kgsl_wgrad, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, M, E, T, Rel, n_relp, D, RG, CG, order, seg, pent,
+                           pcf, g_W, g_Rel);
+        RECON_CHECK_LAUNCH();
+    }
+    return RECON_OK;
 }

@@ -79,9 +79,9 @@ class _TransEMarginLoss(torch.autograd.Function):
         return g_ent, g_rel, None, None, None, None
 
 
-def _validate(train_indices, n_ent, n_rel):
+def _validate(train_indices, n_ent, n_rel, name="recon_amd.batch_gat_loss"):
     """Ids out of range make the reference raise (index out of range); the kernels do not check.  One host round trip unless the producer
-    vouches for the tensor (graph.trust: entity bound in `bound`, relation bound in `rel_bound`)."""
+    vouches for the tensor (graph.trust: entity bound in `bound`, relation bound in `rel_bound`).  `name`: the caller, for the message."""
     from .graph import trust_bounds
     if trusted(train_indices):
         eb, rb = trust_bounds(train_indices)
@@ -92,7 +92,7 @@ def _validate(train_indices, n_ent, n_rel):
     lo, hi = torch.aminmax(train_indices, dim=0)
     lo, hi = lo.tolist(), hi.tolist()
     if min(lo) < 0 or hi[0] >= n_ent or hi[2] >= n_ent or hi[1] >= n_rel:
-        raise IndexError("recon_amd.batch_gat_loss: triple ids out of range (entities %d, relations %d)" % (n_ent, n_rel))
+        raise IndexError("%s: triple ids out of range (entities %d, relations %d)" % (name, n_ent, n_rel))
 
 
 def batch_gat_loss(gat_loss_func, train_indices, entity_embed, relation_embed, valid_invalid_ratio_gat=2):

@@ -9,6 +9,11 @@ of a triple's relation before the translation loss (`tanh(e W_r)`, GAT_sep_space
 Stage B of that tree, `SpKBGATConvOnly` (GAT_sep_space/models.py:247-339), scores a triple after carrying both entities into its relation's
 space; its forward / batch_test take model_gat for W_ent2rel.  The class below keeps that interface and the state_dict, and its `evaluate`
 and `relation_scores` run on the device (recon_amd.kg_sep).
+
+Stage A's loss of that tree, `batch_gat_loss(gat_loss_func, train_indices, entity_embed, relation_embed, model_gat)`
+(GAT_sep_space/main.py:347-391), is re-exported here from recon_amd.sep_loss:
+
+    from recon_amd.sep_space import batch_gat_loss           # instead of the function GAT_sep_space/main.py defines
 """
 import torch
 import torch.nn as nn
@@ -135,3 +140,7 @@ def rel_rows_mm(x, rel, W):
     if rel.numel() and not trusted(rel, limit=W.shape[0]):
         torch._assert_async(((rel >= 0) & (rel < W.shape[0])).all())
     return _RelRowsMM.apply(x, rel, W)
+
+
+# the stage-A loss of this tree (GAT_sep_space/main.py:347-391) on the device: recon_amd/sep_loss.py, DESIGN.md section 14
+from .sep_loss import batch_gat_loss, gat_loss_parts  # noqa: E402,F401
