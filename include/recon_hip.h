@@ -431,6 +431,25 @@ size_t recon_propagate_bwd_chain_ws_floats(const recon_prop_args* fwd);   /* L *
 
 int recon_propagate_bwd(const recon_prop_bwd_args* args, recon_stream_t stream);
 
+/* Which kernel instance a call launches: recon_propagate_instance() for recon_propagate_fwd(args), recon_propagate_bwd_instance() for
+ * recon_propagate_bwd(args) (the backward's choice depends on the workspaces of recon_prop_bwd_args, hence its own entry).  Computed by
+ * the code the launchers dispatch on, RECON_PROP_* switches included; host arithmetic only: no device is needed and the pointers are
+ * looked at for null and for alignment, never followed (the HOST arrays adj / trans / g_adj / g_trans are read).
+ * Returns -1 where the call would be refused, 0 where it launches nothing (B == 0), else
+ *     key = family * 10000 + p1 * 100 + p2 * 10 + flag
+ *     family  kernel(s)                                                        p1    p2    flag
+ *        1    k_propagate_fwd_h / k_propagate_bwd_h (two-term f16, S <= 160)   NKS   NTC   block mode
+ *        2    k_propagate_fwd_hl (two-term f16, wide states)                   NKS   RT    block mode
+ *        3    k_propagate_fwd_hl<.., true> chain + k_prop_gadj_hl<RT, 8>       NKS   RT    block mode       (backward)
+ *        4    the same with k_prop_gadj_hl<RT, 16> (C > 256)                   NKS   RT    block mode       (backward)
+ *        5    k_propagate_fwd_w (fp32 MFMA, state in registers per wave)       NTn   0     V4 (float4 loads of A_l)
+ *        6    k_propagate_fwd (fp32 MFMA, state in LDS per workgroup)          MT    0     V4
+ *        7    k_propagate_bwd_hop (fp32 MFMA, one launch per hop)              MT    0     V4 (float4 staging of the states) (backward)
+ *        8    batched fp32 GEMMs + k_prop_bwd_post (wide states)               0     0     0                (backward)
+ * e.g. 10340 = k_propagate_fwd_h<3, 4, false>, 50901 = k_propagate_fwd_w<9, true>. */
+int32_t recon_propagate_instance(const recon_prop_args* args);
+int32_t recon_propagate_bwd_instance(const recon_prop_bwd_args* args);
+
 /* --------------------------------------------------------------------------------------------
  * P1 / P2 / K5 in bfloat16 (BASELINE.json configs[2] "GP-GNN Propagation 3 hops ... bf16", configs[4] "mixed GAT+Propagation
  *     stack, bf16"): the same step (models/models.py:240-274) on bfloat16 tensors — bf16 storage, fp32 accumulation on
@@ -480,6 +499,13 @@ typedef struct {
 
 size_t recon_propagate_b16_bwd_diag_elems(const recon_prop_b16_args* fwd);
 int recon_propagate_b16_bwd(const recon_prop_b16_bwd_args* args, recon_stream_t stream);
+/* recon_propagate_instance() for the bfloat16 calls, same key layout and rules.  backward == 0: what recon_propagate_b16_fwd(args) launches,
+ *     family 11  k_prop_b16_fwd (form 1)        p1 = NKS, p2 = NTC, flag = block mode
+ *     family 12  k_prop_b16_fwd_wide (form 3)   p1 = NKS, p2 = RT,  flag = block mode
+ *     family 13  one k_bgemm_b16 product per hop + gather (form 2); flag = block mode
+ * backward != 0: 140000 + block mode (k_bgemm_b16 products for every shape) where recon_propagate_b16_bwd takes the forward's arguments
+ * (16-byte aligned gradient buffers assumed), -1 where it refuses them. */
+int32_t recon_propagate_b16_instance(const recon_prop_b16_args* args, int32_t backward);
 
 /* P1 in bf16: recon_block_adjacency_fwd / _bwd on bf16 tensors (the identity gradient is summed in fp32, fixed order, rounded once) */
 int recon_block_adjacency_b16_fwd(const void* T, const void* identity, int32_t B, int32_t n, int32_t dd, void* A, recon_stream_t stream);

@@ -185,6 +185,9 @@ SYMBOLS = [
     ("recon_propagate_fwd", C.c_int, [C.POINTER(PropArgs), C.c_void_p]),
     ("recon_propagate_bwd", C.c_int, [C.POINTER(PropBwdArgs), C.c_void_p]),
     ("recon_propagate_form", C.c_int, [C.POINTER(PropArgs)]),
+    ("recon_propagate_instance", C.c_int32, [C.POINTER(PropArgs)]),
+    ("recon_propagate_bwd_instance", C.c_int32, [C.POINTER(PropBwdArgs)]),
+    ("recon_propagate_b16_instance", C.c_int32, [C.POINTER(PropB16Args), C.c_int32]),
     ("recon_propagate_identity_ws_floats", C.c_size_t, [C.c_int32]),
     ("recon_propagate_ws_bytes", C.c_size_t, [C.POINTER(PropArgs)]),
     ("recon_propagate_bwd_ws_floats", C.c_size_t, [C.POINTER(PropArgs)]),

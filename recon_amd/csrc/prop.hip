@@ -653,24 +653,18 @@ static bool prop_h_form_env() {
     return !form || form[0] == 'h' || form[0] == '\0';
 }
 
-#define RECON_DISPATCH_MT(MTV, V4, KERNEL, ...)                                                                        \
-    do {                                                                                                                \
-        switch (MTV) {                                                                                                  \
-            case 1: if (V4) hipLaunchKernelGGL((KERNEL<1, true>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<1, false>), __VA_ARGS__); break; \
-            case 2: if (V4) hipLaunchKernelGGL((KERNEL<2, true>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<2, false>), __VA_ARGS__); break; \
-            case 3: if (V4) hipLaunchKernelGGL((KERNEL<3, true>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<3, false>), __VA_ARGS__); break; \
-            case 4: if (V4) hipLaunchKernelGGL((KERNEL<4, true>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<4, false>), __VA_ARGS__); break; \
-            default: if (V4) hipLaunchKernelGGL((KERNEL<5, true>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<5, false>), __VA_ARGS__); break; \
-        }                                                                                                               \
-    } while (0)
+#define PROP_KEYS_MT(M_, FAM_) M_(FAM_, 1, true) M_(FAM_, 1, false) M_(FAM_, 2, true) M_(FAM_, 2, false) M_(FAM_, 3, true) M_(FAM_, 3, false) \
+                               M_(FAM_, 4, true) M_(FAM_, 4, false) M_(FAM_, 5, true) M_(FAM_, 5, false)
 
-extern "C" int recon_propagate_fwd(const recon_prop_args* a, recon_stream_t stream) {
+// What recon_propagate_fwd launches for `a`: the kernel arguments, the geometry of the fp32 forms and the instance key (0: B == 0,
+// nothing to launch).  Host arithmetic only — pointers are looked at for alignment — so recon_propagate_instance can ask it without
+// a device.  Returns RECON_OK or the error the call answers with.
+static int plan_fwd(const recon_prop_args* a, PropK& p, PropGeom& g, int32_t* key) {
+    *key = -1;
     int rc = check_prop(a);
     if (rc != RECON_OK) return rc;
-    if (a->B == 0) return RECON_OK;
-    PropGeom g;
+    if (a->B == 0) { *key = 0; return RECON_OK; }
     if (!prop_geometry(a->C, a->S, &g)) return RECON_ERR_UNSUPPORTED;
-    PropK p;
     bool v4 = (a->S % 4) == 0;
     const bool blk = a->trans != nullptr;
     for (int l = 0; l < kMaxHops; ++l) {
@@ -685,37 +679,59 @@ extern "C" int recon_propagate_fwd(const recon_prop_args* a, recon_stream_t stre
     p.CC = g.CC; p.Sp = g.Sp; p.pitch = g.pitch;
     p.stats = a->h_saved ? a->stats : nullptr;
     p.ws = a->split_ws; p.ws_bytes = a->split_ws_bytes;
-    hipStream_t st = as_stream(stream);
     // default: two-term half operands on the f16 matrix cores (prop_h.hip) wherever that form exists; RECON_PROP_FWD = w | b selects
     // one of the fp32 MFMA forms below (per wave / per workgroup), h forces the default
-    if (prop_h_form_env() && prop_fwd_h_supported(p)) return prop_fwd_h(p, st);
-    if (prop_h_form_env() && prop_fwd_hl_supported(p)) return prop_fwd_hl(p, st);     // wide states, given a workspace
+    if (prop_h_form_env()) {
+        if ((*key = prop_fwd_h_key(p)) >= 0) return RECON_OK;
+        if ((*key = prop_fwd_hl_key(p)) >= 0) return RECON_OK;          // wide states, given a workspace
+    }
     if (blk) return RECON_ERR_UNSUPPORTED;                              // the other forms need a materialised adjacency
     const int NTn = g.Sp / 16;
-    if (NTn <= 9 && cfg_char(CFG_PROP_FWD) != 'b') {      // wave-independent form (RECON_PROP_FWD=w, or shapes the f16 forms do not take)
-        const int64_t units = 1LL * a->B * ((a->C + 15) / 16);
-        dim3 wgrid(static_cast<unsigned>(ceil_div64(units, 4)));
-        const size_t wlds = 4ull * 16 * g.pitch * sizeof(float);
-#define CALL_W(N_) do { if (v4) hipLaunchKernelGGL((k_propagate_fwd_w<N_, true>), wgrid, dim3(256), wlds, st, p); \
-                        else hipLaunchKernelGGL((k_propagate_fwd_w<N_, false>), wgrid, dim3(256), wlds, st, p); } while (0)
-        switch (NTn) { case 1: CALL_W(1); break; case 2: CALL_W(2); break; case 3: CALL_W(3); break; case 4: CALL_W(4); break;
-                       case 5: CALL_W(5); break; case 6: CALL_W(6); break; case 7: CALL_W(7); break; case 8: CALL_W(8); break;
-                       default: CALL_W(9); break; }
+    if (NTn <= 9 && cfg_char(CFG_PROP_FWD) != 'b')        // wave-independent form (RECON_PROP_FWD=w, or shapes the f16 forms do not take)
+        *key = prop_key(PF_WAVE, NTn, 0, v4);
+    else
+        *key = prop_key(PF_BLOCK, g.MT, 0, v4);
+    return RECON_OK;
+}
+
+extern "C" int32_t recon_propagate_instance(const recon_prop_args* a) {
+    PropK p;
+    PropGeom g;
+    int32_t key;
+    return plan_fwd(a, p, g, &key) == RECON_OK ? key : -1;
+}
+
+extern "C" int recon_propagate_fwd(const recon_prop_args* a, recon_stream_t stream) {
+    PropK p;
+    PropGeom g;
+    int32_t key;
+    const int rc = plan_fwd(a, p, g, &key);
+    if (rc != RECON_OK) return rc;
+    if (key == 0) return RECON_OK;
+    hipStream_t st = as_stream(stream);
+    if (prop_key_family(key) == PF_H) return prop_fwd_h(p, st);
+    if (prop_key_family(key) == PF_HL) return prop_fwd_hl(p, st);
+    const int64_t units = 1LL * a->B * ((a->C + 15) / 16);
+    const dim3 wgrid(static_cast<unsigned>(ceil_div64(units, 4)));
+    const size_t wlds = 4ull * 16 * g.pitch * sizeof(float);
+    const dim3 grid(static_cast<unsigned>(g.chunks), static_cast<unsigned>(a->B));
+#define CALL_W(FAM_, N_, V_) case prop_key(FAM_, N_, 0, V_): hipLaunchKernelGGL((k_propagate_fwd_w<N_, V_>), wgrid, dim3(256), wlds, st, p); break;
+#define CALL_BLK(FAM_, M_, V_)                                                                                               \
+    case prop_key(FAM_, M_, 0, V_):                                                                                          \
+        if (g.fwd_lds > 64 * 1024)                                                                                           \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_propagate_fwd<M_, V_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                      static_cast<int>(g.fwd_lds));                                                          \
+        hipLaunchKernelGGL((k_propagate_fwd<M_, V_>), grid, dim3(64 * g.fwd_waves), g.fwd_lds, st, p);                       \
+        break;
+    switch (key) {
+        PROP_KEYS_MT(CALL_W, PF_WAVE)
+        CALL_W(PF_WAVE, 6, true) CALL_W(PF_WAVE, 6, false) CALL_W(PF_WAVE, 7, true) CALL_W(PF_WAVE, 7, false) CALL_W(PF_WAVE, 8, true) CALL_W(PF_WAVE, 8, false)
+        CALL_W(PF_WAVE, 9, true) CALL_W(PF_WAVE, 9, false)
+        PROP_KEYS_MT(CALL_BLK, PF_BLOCK)
+        default: return RECON_ERR_UNSUPPORTED;
+    }
 #undef CALL_W
-        RECON_CHECK_LAUNCH();
-        return RECON_OK;
-    }
-    dim3 grid(static_cast<unsigned>(g.chunks), static_cast<unsigned>(a->B));
-    if (g.fwd_lds > 64 * 1024) {
-#define SET_ATTR(MTV, V)                                                                                             \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_propagate_fwd<MTV, V>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              static_cast<int>(g.fwd_lds))
-        switch (g.MT) { case 1: SET_ATTR(1, true); SET_ATTR(1, false); break; case 2: SET_ATTR(2, true); SET_ATTR(2, false); break;
-                        case 3: SET_ATTR(3, true); SET_ATTR(3, false); break; case 4: SET_ATTR(4, true); SET_ATTR(4, false); break;
-                        default: SET_ATTR(5, true); SET_ATTR(5, false); break; }
-#undef SET_ATTR
-    }
-    RECON_DISPATCH_MT(g.MT, v4, k_propagate_fwd, grid, dim3(64 * g.fwd_waves), g.fwd_lds, st, p);
+#undef CALL_BLK
     RECON_CHECK_LAUNCH();
     return RECON_OK;
 }
@@ -882,20 +898,24 @@ extern "C" size_t recon_propagate_bwd_ws_floats(const recon_prop_args* a) {
     return static_cast<size_t>(a->B) * a->C * a->S;
 }
 
-extern "C" int recon_propagate_bwd(const recon_prop_bwd_args* ba, recon_stream_t stream) {
+// What recon_propagate_bwd launches for `ba` (see plan_fwd): the instance key, the two-term form's arguments (PF_H) and the geometry
+// of the per-hop kernel (PF_BWD_HOP).
+static int plan_bwd(const recon_prop_bwd_args* ba, PropBwdH& q, PropGeom& g, int32_t* key) {
+    *key = -1;
     if (!ba) return RECON_ERR_INVALID;
     const recon_prop_args* a = &ba->fwd;
     int rc = check_prop(a);
     if (rc != RECON_OK) return rc;
     if (!a->h_saved || !ba->grad_out || !ba->g_h) return RECON_ERR_INVALID;
-    if (a->B == 0) return RECON_OK;
+    if (a->B == 0) { *key = 0; return RECON_OK; }
+    const bool blk = a->trans != nullptr;
     if (a->S > 160 && ba->chain_ws && ba->head_blk && ba->tail_blk && recon_propagate_bwd_chain_ws_floats(a) > 0 &&
         cfg_char(CFG_PROP_BWD_WIDE) != '0') {
-        return prop_bwd_wide_chain(a, ba, as_stream(stream));          // wide states, structured indices: chain + d A on the two-term f16 kernels (block mode too)
+        // wide states, structured indices: chain + d A on the two-term f16 kernels (block mode too)
+        *key = prop_bwd_hl_key(a->C, a->S, a->L, blk);
+        return *key >= 0 ? RECON_OK : RECON_ERR_UNSUPPORTED;
     }
     if (a->stats && prop_h_form_env() && cfg_char(CFG_PROP_BWD) != 'f') {      // two-term f16 form (RECON_PROP_BWD=f: fp32 MFMA form)
-        PropBwdH q{};
-        const bool blk = a->trans != nullptr;
         for (int l = 0; l < kMaxHops; ++l) {
             q.adj[l] = (l < a->L && !blk) ? a->adj[l] : nullptr; q.gadj[l] = (l < a->L && !blk && ba->g_adj) ? ba->g_adj[l] : nullptr;
             q.trans[l] = (l < a->L && blk) ? a->trans[l] : nullptr; q.gtrans[l] = (l < a->L && blk && ba->g_trans) ? ba->g_trans[l] : nullptr;
@@ -906,33 +926,47 @@ extern "C" int recon_propagate_bwd(const recon_prop_bwd_args* ba, recon_stream_t
         q.h0 = a->h0; q.h0_bs = a->h0_batch_stride; q.hsave = a->h_saved; q.head = a->head_idx; q.tail = a->tail_idx; q.idx_bs = a->idx_batch_stride;
         q.gout = ba->grad_out; q.gH = ba->g_h; q.stats = a->stats;
         q.B = a->B; q.C = a->C; q.S = a->S; q.L = a->L; q.dd = a->dd; q.act = a->act;
-        if (prop_bwd_h_supported(q)) {
-            rc = prop_bwd_h(q, as_stream(stream));
-            if (rc == RECON_OK && q.gident_ws)                          // per-workgroup partial sums -> g_identity, fixed order
-                hipLaunchKernelGGL(k_sum_rows, dim3(16), dim3(1024), 0, as_stream(stream), q.gident_ws, prop_h_grid(a->B), 256, ba->g_identity);
-            return rc;
-        }
+        if ((*key = prop_bwd_h_key(q)) >= 0) return RECON_OK;
         if (blk) return RECON_ERR_UNSUPPORTED;
-    } else if (a->trans) return RECON_ERR_UNSUPPORTED;
-    {
-        const bool wide_off = cfg_char(CFG_PROP_BWD_WIDE) == '0';
-        if (!wide_off && ba->wide_ws && a->S > 160 && 4ull * a->S * sizeof(float) <= 64 * 1024)     // wide states: both products as batched GEMMs
-            return prop_bwd_wide(a, ba, as_stream(stream));
+    } else if (blk) return RECON_ERR_UNSUPPORTED;
+    if (cfg_char(CFG_PROP_BWD_WIDE) != '0' && ba->wide_ws && a->S > 160 && 4ull * a->S * sizeof(float) <= 64 * 1024) {
+        *key = prop_key(PF_BWD_GEMM, 0, 0, false);                      // wide states: both products as batched GEMMs
+        return RECON_OK;
     }
-    PropGeom g;
     if (!prop_geometry(a->C, a->S, &g)) return RECON_ERR_UNSUPPORTED;
+    // float4 staging of the states: every hop's H^l, H^l-1 (h0 for the first hop) and g_h 16-byte aligned — one instance for all hops
+    const bool v4b = (a->S % 4) == 0 && al16(a->h_saved) && al16(a->h0) && al16(ba->g_h) && (a->h0_batch_stride % 4) == 0;
+    *key = prop_key(PF_BWD_HOP, g.MT, 0, v4b);
+    return RECON_OK;
+}
+
+extern "C" int32_t recon_propagate_bwd_instance(const recon_prop_bwd_args* ba) {
+    PropBwdH q{};
+    PropGeom g;
+    int32_t key;
+    return plan_bwd(ba, q, g, &key) == RECON_OK ? key : -1;
+}
+
+extern "C" int recon_propagate_bwd(const recon_prop_bwd_args* ba, recon_stream_t stream) {
+    PropBwdH q{};
+    PropGeom g;
+    int32_t key;
+    int rc = plan_bwd(ba, q, g, &key);
+    if (rc != RECON_OK) return rc;
+    if (key == 0) return RECON_OK;
+    const recon_prop_args* a = &ba->fwd;
     hipStream_t st = as_stream(stream);
+    const int fam = prop_key_family(key);
+    if (fam == PF_HL_CHAIN8 || fam == PF_HL_CHAIN16) return prop_bwd_wide_chain(a, ba, st);
+    if (fam == PF_H) {
+        rc = prop_bwd_h(q, st);
+        if (rc == RECON_OK && q.gident_ws)                              // per-workgroup partial sums -> g_identity, fixed order
+            hipLaunchKernelGGL(k_sum_rows, dim3(16), dim3(1024), 0, st, q.gident_ws, prop_h_grid(a->B), 256, ba->g_identity);
+        return rc;
+    }
+    if (fam == PF_BWD_GEMM) return prop_bwd_wide(a, ba, st);
     const int64_t BCS = 1LL * a->B * a->C * a->S;
     dim3 grid(static_cast<unsigned>(g.chunks), static_cast<unsigned>(a->B));
-    if (g.lds > 64 * 1024) {
-#define SET_ATTR(MTV, V)                                                                                                 \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_propagate_bwd_hop<MTV, V>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              static_cast<int>(g.lds))
-        switch (g.MT) { case 1: SET_ATTR(1, true); SET_ATTR(1, false); break; case 2: SET_ATTR(2, true); SET_ATTR(2, false); break;
-                        case 3: SET_ATTR(3, true); SET_ATTR(3, false); break; case 4: SET_ATTR(4, true); SET_ATTR(4, false); break;
-                        default: SET_ATTR(5, true); SET_ATTR(5, false); break; }
-#undef SET_ATTR
-    }
     for (int l = a->L; l >= 1; --l) {
         PropBwdK p;
         p.A = a->adj[l - 1];
@@ -945,8 +979,18 @@ extern "C" int recon_propagate_bwd(const recon_prop_bwd_args* ba, recon_stream_t
         p.B = a->B; p.C = a->C; p.S = a->S; p.L = a->L; p.dd = a->dd; p.act = a->act;
         p.CC = g.CC; p.Sp = g.Sp; p.pitch = g.pitch; p.hop = l - 1; p.first = (l == a->L) ? 1 : 0; p.chunks = g.chunks;
         if (p.gA && g.chunks > 1 && hipMemsetAsync(p.gA, 0, sizeof(float) * a->B * a->S * a->S, st) != hipSuccess) return RECON_ERR_LAUNCH;
-        const bool v4b = (a->S % 4) == 0 && al16(p.Hl) && al16(p.Hprev) && al16(p.gH) && (p.hprev_bs % 4) == 0;
-        RECON_DISPATCH_MT(g.MT, v4b, k_propagate_bwd_hop, grid, dim3(1024), g.lds, st, p);
+#define CALL_HOP(FAM_, M_, V_)                                                                                               \
+    case prop_key(FAM_, M_, 0, V_):                                                                                          \
+        if (g.lds > 64 * 1024 && l == a->L)                              /* once, ahead of the first hop's launch */          \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_propagate_bwd_hop<M_, V_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                      static_cast<int>(g.lds));                                                              \
+        hipLaunchKernelGGL((k_propagate_bwd_hop<M_, V_>), grid, dim3(1024), g.lds, st, p);                                   \
+        break;
+        switch (key) {
+            PROP_KEYS_MT(CALL_HOP, PF_BWD_HOP)
+            default: return RECON_ERR_UNSUPPORTED;
+        }
+#undef CALL_HOP
         RECON_CHECK_LAUNCH();
     }
     return RECON_OK;

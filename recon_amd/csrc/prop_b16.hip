@@ -1086,7 +1086,27 @@ int launch_bgemm(const BGemmB16& g, hipStream_t st) {
     return launch_bgemm_cfg<PK, QK, EPI, PBLK, 2, 4, 8, 4, 3>(g, st);
 }
 
+// The instance a forward of form_b16() = `form` launches: the small fused kernel by (NKS, NTC) — block mode (S = 16 n, C = n (n - 1)) one pair
+// per n —, the wide fused kernel by its K steps (RT = rows / 128 follows from them), the GEMM form as one key.
+int32_t key_b16(const recon_prop_b16_args* a, int form) {
+    const bool blk = a->trans != nullptr;
+    if (form == 1) {
+        int nks = (a->S + 31) / 32, ntc = (a->C + 15) / 16;
+        if (blk && !prop_block_kn(a->S / 16, &nks, &ntc)) return -1;
+        if (nks < 1 || nks > 5 || ntc < 1 || ntc > 6) return -1;
+        return prop_key(PF_B16_FUSED, nks, ntc, blk);
+    }
+    if (form == 3) {
+        const int nks = a->S / 32;
+        if (nks < 6 || nks > 16 || (nks & 1)) return -1;
+        return prop_key(PF_B16_WIDE, nks, nks <= 8 ? 2 : nks <= 12 ? 3 : 4, blk);
+    }
+    return form == 2 ? prop_key(PF_B16_GEMM, 0, 0, blk) : -1;
+}
+
 int fwd_fused(const recon_prop_b16_args* a, hipStream_t st) {
+    const int32_t key = key_b16(a, 1);
+    if (key < 0) return RECON_ERR_UNSUPPORTED;
     PropB16K p{};
     const bool blk = a->trans != nullptr;
     for (int l = 0; l < kMaxHops; ++l) {
@@ -1101,7 +1121,7 @@ int fwd_fused(const recon_prop_b16_args* a, hipStream_t st) {
     const int nks = (a->S + 31) / 32, ntc = (a->C + 15) / 16, nw = a->S / 16;
     const size_t lds = fused_lds(nks, ntc);
 #define CALL_F(K_, N_, X_)                                                                                                              \
-    do {                                                                                                                                \
+    case prop_key(PF_B16_FUSED, K_, N_, X_): {                                                                                          \
         auto kern = k_prop_b16_fwd<K_, N_, X_>;                                                                                         \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                                        static_cast<int>(lds));                                                         \
@@ -1111,18 +1131,14 @@ int fwd_fused(const recon_prop_b16_args* a, hipStream_t st) {
         const int64_t rounds = ceil_div64(a->B, cap);                                                                                   \
         const int grid = static_cast<int>(ceil_div64(a->B, rounds));      /* every workgroup walks `rounds` graphs (the last ones one less) */ \
         hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * nw), lds, st, p);                                         \
-    } while (0)
-    if (blk) {                                                          // block mode: S = 16 n, C = n (n - 1): one (NKS, NTC) per n
-        switch (nw) { case 2: CALL_F(1, 1, true); break; case 3: case 4: CALL_F(2, 1, true); break; case 5: case 6: CALL_F(3, 2, true); break;
-                      case 7: CALL_F(4, 3, true); break; case 8: CALL_F(4, 4, true); break; case 9: CALL_F(5, 5, true); break; case 10: CALL_F(5, 6, true); break;
-                      default: return RECON_ERR_UNSUPPORTED; }
-    } else {
-#define CALL_FN(K_)                                                                                                                     \
-    switch (ntc) { case 1: CALL_F(K_, 1, false); break; case 2: CALL_F(K_, 2, false); break; case 3: CALL_F(K_, 3, false); break; case 4: CALL_F(K_, 4, false); break; \
-                   case 5: CALL_F(K_, 5, false); break; default: CALL_F(K_, 6, false); break; }
-        switch (nks) { case 1: CALL_FN(1); break; case 2: CALL_FN(2); break; case 3: CALL_FN(3); break; case 4: CALL_FN(4); break; default: CALL_FN(5); break; }
-#undef CALL_FN
+    } break;
+#define CALL_FN(K_) CALL_F(K_, 1, false) CALL_F(K_, 2, false) CALL_F(K_, 3, false) CALL_F(K_, 4, false) CALL_F(K_, 5, false) CALL_F(K_, 6, false)
+    switch (key) {
+        CALL_F(1, 1, true) CALL_F(2, 1, true) CALL_F(3, 2, true) CALL_F(4, 3, true) CALL_F(4, 4, true) CALL_F(5, 5, true) CALL_F(5, 6, true)   // block mode: n = 2 .. 10
+        CALL_FN(1) CALL_FN(2) CALL_FN(3) CALL_FN(4) CALL_FN(5)
+        default: return RECON_ERR_UNSUPPORTED;
     }
+#undef CALL_FN
 #undef CALL_F
     if (hipGetLastError() != hipSuccess) return RECON_ERR_LAUNCH;
     return RECON_OK;
@@ -1144,17 +1160,19 @@ int fwd_wide(const recon_prop_b16_args* a, hipStream_t st) {
     const size_t lds = static_cast<size_t>(nks) * 128 * 64 + 2 * 5 * 512 * sizeof(uint32_t);
     const int64_t nblk = ceil_div64(a->B, 8) * 8 * nchunk;
     if (nblk >= (1LL << 31)) return RECON_ERR_UNSUPPORTED;
+    const int32_t key = key_b16(a, 3);
 #define CALL_W(K_, R_, X_)                                                                                                              \
-    do {                                                                                                                                \
+    case prop_key(PF_B16_WIDE, K_, R_, X_): {                                                                                           \
         auto kern = k_prop_b16_fwd_wide<K_, R_, X_>;                                                                                    \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                                        static_cast<int>(lds));                                                         \
         hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(nblk)), dim3(512), lds, st, p, nchunk);                                     \
-    } while (0)
-#define CALL_WK(X_)                                                                                                                     \
-    switch (nks) { case 6: CALL_W(6, 2, X_); break; case 8: CALL_W(8, 2, X_); break; case 10: CALL_W(10, 3, X_); break; case 12: CALL_W(12, 3, X_); break; \
-                   case 14: CALL_W(14, 4, X_); break; case 16: CALL_W(16, 4, X_); break; default: return RECON_ERR_UNSUPPORTED; }
-    if (blk) { CALL_WK(true); } else { CALL_WK(false); }
+    } break;
+#define CALL_WK(X_) CALL_W(6, 2, X_) CALL_W(8, 2, X_) CALL_W(10, 3, X_) CALL_W(12, 3, X_) CALL_W(14, 4, X_) CALL_W(16, 4, X_)
+    switch (key) {
+        CALL_WK(true) CALL_WK(false)
+        default: return RECON_ERR_UNSUPPORTED;
+    }
 #undef CALL_WK
 #undef CALL_W
     if (hipGetLastError() != hipSuccess) return RECON_ERR_LAUNCH;
@@ -1196,11 +1214,48 @@ extern "C" int recon_propagate_b16_form(const recon_prop_b16_args* a) {
     return form_b16(a, false);
 }
 
-extern "C" int recon_propagate_b16_fwd(const recon_prop_b16_args* a, recon_stream_t stream) {
+// the backward's conditions on the forward's arguments (recon_propagate_b16_bwd adds those on its own buffers)
+static int bwd_b16_check(const recon_prop_b16_args* a) {
+    const int rc0 = check_b16(a);
+    if (rc0 != RECON_OK) return rc0;
+    if (!a->h_saved || !a->zeros) return RECON_ERR_INVALID;
+    const bool blk = a->trans != nullptr;
+    if (a->S % 8 != 0 || !al16(a->h0) || (a->h0_batch_stride % 8) != 0 || !al16(a->h_saved) || !al16(a->zeros) ||
+        static_cast<int64_t>(a->C) * a->S >= (1LL << 31) || static_cast<int64_t>(a->S) * a->S >= (1LL << 31) || 8ull * a->S * sizeof(float) > 64 * 1024)
+        return RECON_ERR_UNSUPPORTED;
+    for (int l = 0; l < a->L; ++l)
+        if (!al16(blk ? a->trans[l] : a->adj[l])) return RECON_ERR_UNSUPPORTED;
+    if (blk && !al16(a->identity)) return RECON_ERR_UNSUPPORTED;
+    return RECON_OK;
+}
+
+// What recon_propagate_b16_fwd launches for `a` (host arithmetic only): RECON_OK and the instance key (0: B == 0, nothing to launch), or the
+// error the call answers with.
+static int plan_b16_fwd(const recon_prop_b16_args* a, int* form, int32_t* key) {
+    *key = -1; *form = 0;
     const int rc = check_b16(a);
     if (rc != RECON_OK) return rc;
-    if (a->B == 0) return RECON_OK;
-    const int form = form_b16(a, true);
+    if (a->B == 0) { *key = 0; return RECON_OK; }
+    *form = form_b16(a, true);
+    if (*form == 2 && (!a->h_saved || !a->zeros || !al16(a->zeros))) return RECON_ERR_INVALID;                  // fwd_gemm's workspaces
+    if (*form == 3 && ceil_div64(a->B, 8) * 8 * ((a->C + 127) / 128) >= (1LL << 31)) return RECON_ERR_UNSUPPORTED;   // fwd_wide's grid
+    *key = key_b16(a, *form);
+    return *key >= 0 ? RECON_OK : RECON_ERR_UNSUPPORTED;
+}
+
+extern "C" int32_t recon_propagate_b16_instance(const recon_prop_b16_args* a, int32_t backward) {
+    if (backward) return bwd_b16_check(a) == RECON_OK ? (a->B == 0 ? 0 : prop_key(PF_B16_BWD, 0, 0, a->trans != nullptr)) : -1;
+    int form;
+    int32_t key;
+    return plan_b16_fwd(a, &form, &key) == RECON_OK ? key : -1;
+}
+
+extern "C" int recon_propagate_b16_fwd(const recon_prop_b16_args* a, recon_stream_t stream) {
+    int form;
+    int32_t key;
+    const int rc = plan_b16_fwd(a, &form, &key);
+    if (rc != RECON_OK) return rc;
+    if (key == 0) return RECON_OK;
     if (form == 1) return fwd_fused(a, as_stream(stream));
     if (form == 2) return fwd_gemm(a, as_stream(stream));
     if (form == 3) return fwd_wide(a, as_stream(stream));
@@ -1240,14 +1295,12 @@ extern "C" int recon_propagate_b16_bwd(const recon_prop_b16_bwd_args* ba, recon_
     const int32_t B = a->B, C = a->C, S = a->S, L = a->L;
     const bool blk = a->trans != nullptr;
     if (blk && ba->g_identity && (!ba->diag_ws || !ba->ident_ws)) return RECON_ERR_INVALID;
-    if (S % 8 != 0 || !al16(a->h0) || (a->h0_batch_stride % 8) != 0 || !al16(a->h_saved) || !al16(ba->g_h) || !al16(ba->ws) || !al16(a->zeros) ||
-        static_cast<int64_t>(C) * S >= (1LL << 31) || static_cast<int64_t>(S) * S >= (1LL << 31) || 8ull * S * sizeof(float) > 64 * 1024)
-        return RECON_ERR_UNSUPPORTED;
-    for (int l = 0; l < L; ++l) {
-        if (!al16(blk ? a->trans[l] : a->adj[l])) return RECON_ERR_UNSUPPORTED;
+    const int rc1 = bwd_b16_check(a);
+    if (rc1 != RECON_OK) return rc1;
+    if (!al16(ba->g_h) || !al16(ba->ws)) return RECON_ERR_UNSUPPORTED;
+    for (int l = 0; l < L; ++l)
         if (blk ? (ba->g_trans && ba->g_trans[l] && !al16(ba->g_trans[l])) : (ba->g_adj && ba->g_adj[l] && !al16(ba->g_adj[l]))) return RECON_ERR_UNSUPPORTED;
-    }
-    if (blk && (!al16(a->identity) || (ba->diag_ws && !al16(ba->diag_ws)))) return RECON_ERR_UNSUPPORTED;
+    if (blk && ba->diag_ws && !al16(ba->diag_ws)) return RECON_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
     const int64_t CS = 1LL * C * S, BCS = CS * B, rows = 1LL * B * C;
     const int nn = S / 16;

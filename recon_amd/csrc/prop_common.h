@@ -6,6 +6,33 @@ namespace recon {
 
 constexpr int kMaxHops = 8;
 
+// Kernel-instance keys (include/recon_hip.h: recon_propagate_instance): family * 10000 + p1 * 100 + p2 * 10 + flag.  Every launcher
+// switches on the key its selection function returns, and the instance queries return the same key: one piece of code decides.
+enum PropFamily {
+    PF_H = 1,            // k_propagate_fwd_h / k_propagate_bwd_h <NKS = p1, NTC = p2, BLK = flag>
+    PF_HL = 2,           // k_propagate_fwd_hl <RT = p2, NKS = p1>; flag: block mode (k_prop_split_adj<true>)
+    PF_HL_CHAIN8 = 3,    // k_propagate_fwd_hl <RT = p2, NKS = p1, true> + k_prop_gadj_hl <RT, 8>; flag: block mode
+    PF_HL_CHAIN16 = 4,   // the same with k_prop_gadj_hl <RT, 16>
+    PF_WAVE = 5,         // k_propagate_fwd_w <NTn = p1, V4 = flag>
+    PF_BLOCK = 6,        // k_propagate_fwd <MT = p1, V4 = flag>
+    PF_BWD_HOP = 7,      // k_propagate_bwd_hop <MT = p1, V4 = flag>
+    PF_BWD_GEMM = 8,     // both products of a hop as batched fp32 GEMMs + k_prop_bwd_post
+    PF_B16_FUSED = 11,   // k_prop_b16_fwd <NKS = p1, NTC = p2, BLK = flag>
+    PF_B16_WIDE = 12,    // k_prop_b16_fwd_wide <NKS = p1, RT = p2, BLK = flag>
+    PF_B16_GEMM = 13,    // one k_bgemm_b16 product per hop + gather; flag: block mode
+    PF_B16_BWD = 14,     // the bfloat16 backward: k_bgemm_b16 products; flag: block mode
+};
+constexpr int32_t prop_key(int fam, int p1, int p2, bool flag) { return fam * 10000 + p1 * 100 + p2 * 10 + (flag ? 1 : 0); }
+constexpr int prop_key_family(int32_t key) { return key / 10000; }
+constexpr int32_t prop_key_noflag(int32_t key) { return key - key % 10; }
+// block mode of the small fused kernels (S = 16 n, C = n (n - 1), n = 2 .. 10): one (NKS, NTC) per n; false outside that range
+inline bool prop_block_kn(int n, int* nks, int* ntc) {
+    static const signed char kn[11][2] = {{0, 0}, {0, 0}, {1, 1}, {2, 1}, {2, 1}, {3, 2}, {3, 2}, {4, 3}, {4, 4}, {5, 5}, {5, 6}};
+    if (n < 2 || n > 10) return false;
+    *nks = kn[n][0]; *ntc = kn[n][1];
+    return true;
+}
+
 struct PropK {
     const float* adj[kMaxHops];
     const float* h0; int64_t h0_bs;
@@ -62,10 +89,12 @@ __device__ __forceinline__ float act_bwd(float y, int act) {
 // prop_h.hip: forward on the f16 matrix cores with two-term operands (fp32-class accuracy); false / UNSUPPORTED for shapes it
 // does not take (the caller then runs a fp32-MFMA form of prop.hip)
 bool prop_fwd_h_supported(const PropK& p);
+int32_t prop_fwd_h_key(const PropK& p);   // the instance prop_fwd_h launches (PF_H), -1 where prop_fwd_h_supported says no
 int prop_fwd_h(const PropK& p, hipStream_t st);
 // prop_hl.hip: the same arithmetic for wide states (160 < S <= 512) in 64-channel chunks, A_l pre-split into a caller-owned workspace
 size_t prop_hl_ws_bytes(int B, int S, int L);
 bool prop_fwd_hl_supported(const PropK& p);
+int32_t prop_fwd_hl_key(const PropK& p);  // PF_HL, -1 where prop_fwd_hl_supported says no
 int prop_fwd_hl(const PropK& p, hipStream_t st);
 // prop_hl.hip: the backward's chain d loss / d H^{l-1} = A_l^T Y_l, Y_{l-1} = (. + relation gradient) act'(H^{l-1}) for a SLICE of G graphs
 // (all pointers slice-local) on the forward's kernel; step k = 0 .. L-1 is hop l = L - k
@@ -85,6 +114,7 @@ struct PropBwdHL {
 };
 int64_t prop_bwd_hl_slice(int C, int S, int L, int64_t ws_bytes, int B);   // graphs per slice the workspace allows (0: form not available)
 int prop_bwd_hl_chain(const PropBwdHL& a, hipStream_t st);
+int32_t prop_bwd_hl_key(int C, int S, int L, bool blk);   // PF_HL_CHAIN8 / 16: the chain kernel's and the d A kernel's instances for this shape
 size_t prop_bwd_hl_ws_floats(int C, int S, int L, int64_t G);
 void prop_bwd_hl_ws_layout(int C, int S, int L, int64_t G, float* ws, float** y_in, unsigned char** planes, float** isg, size_t* plane_set_bytes, size_t* isg_set_floats);
 // d A_l[g] = Y_l[g]^T H^{l-1}[g] from one plane set of the chain kernel
@@ -94,6 +124,7 @@ int prop_bwd_hl_gadj(const unsigned char* yplanes, const float* yisg, const floa
 bool prop_bwd_h_shape_ok(int C, int S);   // LDS budget of the backward's two-term form
 int prop_h_grid(int B);               // workgroups the two-term kernels launch for B graphs (one per CU, persistent)
 bool prop_bwd_h_supported(const PropBwdH& p);
+int32_t prop_bwd_h_key(const PropBwdH& p);    // PF_H, -1 where prop_bwd_h_supported says no
 int prop_bwd_h(const PropBwdH& p, hipStream_t st);
 
 }  // namespace recon

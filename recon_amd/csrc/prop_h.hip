@@ -786,10 +786,10 @@ __global__ void __launch_bounds__(128 * NKS) k_propagate_bwd_h(const PropBwdH p)
         float* red = reinterpret_cast<float*>(ring);                    // [NW][16][16]
         *reinterpret_cast<f32x4*>(red + wave * 256 + li * 16 + 4 * lq) = gI_acc;
         lds_barrier();
-        if (tid < 256) {
+        for (int e = tid; e < 256; e += static_cast<int>(blockDim.x)) {       // n = 2, 3: fewer than 256 threads
             float sum = 0.f;
-            for (int w = 0; w < NW; ++w) sum += red[w * 256 + tid];
-            p.gident_ws[static_cast<int64_t>(blockIdx.x) * 256 + tid] = sum;
+            for (int w = 0; w < NW; ++w) sum += red[w * 256 + e];
+            p.gident_ws[static_cast<int64_t>(blockIdx.x) * 256 + e] = sum;
         }
     }
 }
@@ -835,26 +835,37 @@ bool prop_bwd_h_supported(const PropBwdH& p) {
     return bwd_h_lds(nks, ntc, p.S) <= 160 * 1024;
 }
 
+// (NKS, NTC) of the instance: dense mode by the state and channel counts, block mode (S = 16 n, C = n (n - 1)) one pair per n
+static int32_t h_key(int S, int C, bool blk, int max_nw) {
+    int nks = (S + 31) / 32, ntc = (C + 15) / 16;
+    if (blk && (S / 16 > max_nw || !prop_block_kn(S / 16, &nks, &ntc))) return -1;
+    if (nks < 1 || nks > 5 || ntc < 1 || ntc > 6) return -1;
+    return prop_key(PF_H, nks, ntc, blk);
+}
+#define H_KEY_ROW(M_, K_) M_(K_, 1, false) M_(K_, 2, false) M_(K_, 3, false) M_(K_, 4, false) M_(K_, 5, false) M_(K_, 6, false)
+#define H_KEY_DENSE(M_) H_KEY_ROW(M_, 1) H_KEY_ROW(M_, 2) H_KEY_ROW(M_, 3) H_KEY_ROW(M_, 4) H_KEY_ROW(M_, 5)
+
+int32_t prop_bwd_h_key(const PropBwdH& p) {
+    if (!prop_bwd_h_supported(p)) return -1;
+    return h_key(p.S, p.C, p.identity != nullptr, 9);
+}
+
 int prop_bwd_h(const PropBwdH& p, hipStream_t st) {
-    if (!prop_bwd_h_supported(p)) return RECON_ERR_UNSUPPORTED;
+    const int32_t key = prop_bwd_h_key(p);
+    if (key < 0) return RECON_ERR_UNSUPPORTED;
     const int nks = (p.S + 31) / 32, ntc = (p.C + 15) / 16, nw = p.S / 16;
     const size_t lds = bwd_h_lds(nks, ntc, p.S);
     const int grid = p.B < num_cus() ? p.B : num_cus();
 #define CALL_B(K_, N_, X_)                                                                                                              \
-    do {                                                                                                                                \
+    case prop_key(PF_H, K_, N_, X_): {                                                                                                  \
         if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_propagate_bwd_h<K_, N_, X_>),                 \
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));             \
         hipLaunchKernelGGL((k_propagate_bwd_h<K_, N_, X_>), dim3(static_cast<unsigned>(grid)), dim3(64 * nw), lds, st, p);              \
-    } while (0)
-    if (p.identity) {                                                   // block mode: S = 16 n, C = n (n - 1): one (NKS, NTC) per n
-        switch (nw) { case 2: CALL_B(1, 1, true); break; case 3: case 4: CALL_B(2, 1, true); break; case 5: case 6: CALL_B(3, 2, true); break;
-                      case 7: CALL_B(4, 3, true); break; case 8: CALL_B(4, 4, true); break; case 9: CALL_B(5, 5, true); break; default: return RECON_ERR_UNSUPPORTED; }
-    } else {
-#define CALL_BN(K_)                                                                                                                     \
-    switch (ntc) { case 1: CALL_B(K_, 1, false); break; case 2: CALL_B(K_, 2, false); break; case 3: CALL_B(K_, 3, false); break; case 4: CALL_B(K_, 4, false); break; \
-                   case 5: CALL_B(K_, 5, false); break; default: CALL_B(K_, 6, false); break; }
-    switch (nks) { case 1: CALL_BN(1); break; case 2: CALL_BN(2); break; case 3: CALL_BN(3); break; case 4: CALL_BN(4); break; default: CALL_BN(5); break; }
-#undef CALL_BN
+    } break;
+    switch (key) {
+        CALL_B(1, 1, true) CALL_B(2, 1, true) CALL_B(3, 2, true) CALL_B(4, 3, true) CALL_B(4, 4, true) CALL_B(5, 5, true)      // block mode: n = 2 .. 9
+        H_KEY_DENSE(CALL_B)
+        default: return RECON_ERR_UNSUPPORTED;
     }
 #undef CALL_B
     if (hipGetLastError() != hipSuccess) return RECON_ERR_LAUNCH;
@@ -871,27 +882,27 @@ bool prop_fwd_h_supported(const PropK& p) {
     return fwd_h_lds(nks, ntc, p.S) <= 160 * 1024;
 }
 
+int32_t prop_fwd_h_key(const PropK& p) {
+    if (!prop_fwd_h_supported(p)) return -1;
+    return h_key(p.S, p.C, p.identity != nullptr, 10);
+}
+
 int prop_fwd_h(const PropK& p, hipStream_t st) {
-    if (!prop_fwd_h_supported(p)) return RECON_ERR_UNSUPPORTED;
+    const int32_t key = prop_fwd_h_key(p);
+    if (key < 0) return RECON_ERR_UNSUPPORTED;
     const int nks = (p.S + 31) / 32, ntc = (p.C + 15) / 16, nw = p.S / 16;
     const size_t lds = fwd_h_lds(nks, ntc, p.S);
     const int grid = p.B < num_cus() ? p.B : num_cus();
 #define CALL_H(K_, N_, X_)                                                                                                              \
-    do {                                                                                                                                \
+    case prop_key(PF_H, K_, N_, X_): {                                                                                                  \
         if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_propagate_fwd_h<K_, N_, X_>),                 \
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));             \
         hipLaunchKernelGGL((k_propagate_fwd_h<K_, N_, X_>), dim3(static_cast<unsigned>(grid)), dim3(64 * nw), lds, st, p);              \
-    } while (0)
-    if (p.identity) {                                                   // block mode: S = 16 n, C = n (n - 1): one (NKS, NTC) per n
-        switch (nw) { case 2: CALL_H(1, 1, true); break; case 3: case 4: CALL_H(2, 1, true); break; case 5: case 6: CALL_H(3, 2, true); break;
-                      case 7: CALL_H(4, 3, true); break; case 8: CALL_H(4, 4, true); break; case 9: CALL_H(5, 5, true); break; case 10: CALL_H(5, 6, true); break;
-                      default: return RECON_ERR_UNSUPPORTED; }
-    } else {
-#define CALL_HN(K_)                                                                                                                     \
-    switch (ntc) { case 1: CALL_H(K_, 1, false); break; case 2: CALL_H(K_, 2, false); break; case 3: CALL_H(K_, 3, false); break; case 4: CALL_H(K_, 4, false); break; \
-                   case 5: CALL_H(K_, 5, false); break; default: CALL_H(K_, 6, false); break; }
-    switch (nks) { case 1: CALL_HN(1); break; case 2: CALL_HN(2); break; case 3: CALL_HN(3); break; case 4: CALL_HN(4); break; default: CALL_HN(5); break; }
-#undef CALL_HN
+    } break;
+    switch (key) {
+        CALL_H(1, 1, true) CALL_H(2, 1, true) CALL_H(3, 2, true) CALL_H(4, 3, true) CALL_H(4, 4, true) CALL_H(5, 5, true) CALL_H(5, 6, true)   // block mode: n = 2 .. 10
+        H_KEY_DENSE(CALL_H)
+        default: return RECON_ERR_UNSUPPORTED;
     }
 #undef CALL_H
     if (hipGetLastError() != hipSuccess) return RECON_ERR_LAUNCH;

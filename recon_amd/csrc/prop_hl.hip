@@ -808,8 +808,22 @@ bool prop_fwd_hl_supported(const PropK& p) {
     return p.ws_bytes >= static_cast<int64_t>(g.per_graph_split + g.per_graph_alpha + 256);
 }
 
+// RT = rows / 128 follows from the K steps: one instance per even NKS in 6 .. 16
+static int32_t hl_key(int fam, int S, int L, bool blk) {
+    const HLGeom g = hl_geom(S, L);
+    if (g.NKS < 6 || g.NKS > 16 || g.RT != (g.NKS <= 8 ? 2 : g.NKS <= 12 ? 3 : 4)) return -1;
+    return prop_key(fam, g.NKS, g.RT, blk);
+}
+#define HL_KEYS(M_) M_(2, 6) M_(2, 8) M_(3, 10) M_(3, 12) M_(4, 14) M_(4, 16)
+
+int32_t prop_fwd_hl_key(const PropK& p) {
+    if (!prop_fwd_hl_supported(p)) return -1;
+    return hl_key(PF_HL, p.S, p.L, p.identity != nullptr);
+}
+
 int prop_fwd_hl(const PropK& p, hipStream_t st) {
-    if (!prop_fwd_hl_supported(p)) return RECON_ERR_UNSUPPORTED;
+    const int32_t key = prop_fwd_hl_key(p);
+    if (key < 0) return RECON_ERR_UNSUPPORTED;
     const HLGeom g = hl_geom(p.S, p.L);
     int64_t G = (p.ws_bytes - 256) / static_cast<int64_t>(g.per_graph_split + g.per_graph_alpha);
     if (G > p.B) G = p.B;
@@ -828,14 +842,14 @@ int prop_fwd_hl(const PropK& p, hipStream_t st) {
         else hipLaunchKernelGGL(k_prop_split_adj<false>, sgrid, dim3(256), 0, st, q);
         const dim3 grid(static_cast<unsigned>(((q.G + 7) / 8) * 8 * q.nchunks));
 #define CALL_HL(R_, K_)                                                                                                                 \
-    do {                                                                                                                                \
+    case prop_key(PF_HL, K_, R_, false): {                                                                                              \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_propagate_fwd_hl<R_, K_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                   static_cast<int>(g.lds));                                                                             \
         hipLaunchKernelGGL((k_propagate_fwd_hl<R_, K_>), grid, dim3(64 * kHLWaves), g.lds, st, q);                                      \
-    } while (0)
-        switch (g.NKS) {                                                // RT = rows / 128 follows from the K steps
-            case 6: CALL_HL(2, 6); break; case 8: CALL_HL(2, 8); break; case 10: CALL_HL(3, 10); break; case 12: CALL_HL(3, 12); break;
-            case 14: CALL_HL(4, 14); break; default: CALL_HL(4, 16); break;
+    } break;
+        switch (prop_key_noflag(key)) {                                 // without the block-mode flag
+            HL_KEYS(CALL_HL)
+            default: return RECON_ERR_UNSUPPORTED;
         }
 #undef CALL_HL
     }
@@ -859,6 +873,7 @@ int64_t prop_bwd_hl_slice(int C, int S, int L, int64_t ws_bytes, int B) {
 
 // chain workspace of a slice of G graphs, in floats: Y_L as fp32 [G][C][S] | L plane sets [G][RTT][NKC][2][256 floats] | L x [G][32 NKC] scales
 static int hl_nkc(int C) { return 2 * ((C + kCH - 1) / kCH); }
+static int hl_gadj_nks(int C) { return hl_nkc(C) <= 8 ? 8 : 16; }        // K steps per pass of the d A kernel
 size_t prop_bwd_hl_ws_floats(int C, int S, int L, int64_t G) {
     const HLGeom g = hl_geom(S, L);
     const size_t planes = static_cast<size_t>(8) * g.RT * hl_nkc(C) * 512;
@@ -875,31 +890,44 @@ void prop_bwd_hl_ws_layout(int C, int S, int L, int64_t G, float* ws, float** y_
 
 int prop_bwd_hl_gadj(const unsigned char* yplanes, const float* yisg, const float* Hprev, int64_t h_bs, float* out, float* gtrans, float* gdiag, int G,
                      int C, int S, hipStream_t st) {
-    const HLGeom g = hl_geom(S, 1);
     PropGadj q{};
     q.yplanes = yplanes; q.yisg = yisg; q.Hprev = Hprev; q.h_bs = h_bs; q.out = out; q.gtrans = gtrans; q.gdiag = gdiag;
     q.G = G; q.C = C; q.S = S; q.NKC = hl_nkc(C); q.nchunks = (S + kCH - 1) / kCH;
-    const int NKS = q.NKC <= 8 ? 8 : 16;
+    const int NKS = hl_gadj_nks(C);
     q.npass = (q.NKC + NKS - 1) / NKS;
     if (static_cast<int64_t>(C) * S * 4 >= (1LL << 31)) return RECON_ERR_UNSUPPORTED;
     const size_t lds = 2ull * NKS * kSTEP + 2ull * kCH * sizeof(uint32_t) + static_cast<size_t>(NKS) * 32 * sizeof(float);
     const dim3 grid(static_cast<unsigned>(((G + 7) / 8) * 8 * q.nchunks));
+    const int32_t key = prop_bwd_hl_key(C, S, 1, false);
+    if (key < 0) return RECON_ERR_UNSUPPORTED;
 #define CALL_GA(R_, K_)                                                                                                             \
-    do {                                                                                                                            \
+    {                                                                                                                               \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prop_gadj_hl<R_, K_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                   static_cast<int>(lds));                                                                           \
         hipLaunchKernelGGL((k_prop_gadj_hl<R_, K_>), grid, dim3(64 * kHLWaves), lds, st, q);                                        \
-    } while (0)
-    if (NKS == 8) { if (g.RT == 2) CALL_GA(2, 8); else if (g.RT == 3) CALL_GA(3, 8); else CALL_GA(4, 8); }
-    else { if (g.RT == 2) CALL_GA(2, 16); else if (g.RT == 3) CALL_GA(3, 16); else CALL_GA(4, 16); }
+    } break;
+    switch (prop_key(prop_key_family(key), 0, key / 10 % 10, false)) {  // the d A kernel's part of the key: family (8 | 16 K steps) and RT
+        case prop_key(PF_HL_CHAIN8, 0, 2, false): CALL_GA(2, 8) case prop_key(PF_HL_CHAIN8, 0, 3, false): CALL_GA(3, 8)
+        case prop_key(PF_HL_CHAIN8, 0, 4, false): CALL_GA(4, 8)
+        case prop_key(PF_HL_CHAIN16, 0, 2, false): CALL_GA(2, 16) case prop_key(PF_HL_CHAIN16, 0, 3, false): CALL_GA(3, 16)
+        case prop_key(PF_HL_CHAIN16, 0, 4, false): CALL_GA(4, 16)
+        default: return RECON_ERR_UNSUPPORTED;
+    }
 #undef CALL_GA
     if (hipGetLastError() != hipSuccess) return RECON_ERR_LAUNCH;
     return RECON_OK;
 }
 
+int32_t prop_bwd_hl_key(int C, int S, int L, bool blk) {
+    if (S <= 160 || S > 512 || L < 1 || L > kMaxHops) return -1;
+    return hl_key(hl_gadj_nks(C) == 8 ? PF_HL_CHAIN8 : PF_HL_CHAIN16, S, L, blk);
+}
+
 int prop_bwd_hl_chain(const PropBwdHL& a, hipStream_t st) {
     const int64_t G = prop_bwd_hl_slice(a.C, a.S, a.L, a.ws_bytes, a.G);
     if (G < a.G || a.dd != 16 || !a.hblk || !a.tblk) return RECON_ERR_UNSUPPORTED;
+    const int32_t key = prop_bwd_hl_key(a.C, a.S, a.L, false);
+    if (key < 0) return RECON_ERR_UNSUPPORTED;
     const HLGeom g = hl_geom(a.S, a.L);
     PropHL q{};
     q.p.B = a.G; q.p.C = a.C; q.p.S = a.S; q.p.L = a.L; q.p.dd = a.dd; q.p.act = a.act;
@@ -921,14 +949,14 @@ int prop_bwd_hl_chain(const PropBwdHL& a, hipStream_t st) {
     }
     const dim3 grid(static_cast<unsigned>(((q.G + 7) / 8) * 8 * q.nchunks));
 #define CALL_HLB(R_, K_)                                                                                                                      \
-    do {                                                                                                                                      \
+    case prop_key(PF_HL, K_, R_, false): {                                                                                                    \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_propagate_fwd_hl<R_, K_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                   static_cast<int>(g.lds));                                                                                   \
         hipLaunchKernelGGL((k_propagate_fwd_hl<R_, K_, true>), grid, dim3(64 * kHLWaves), g.lds, st, q);                                      \
-    } while (0)
-    switch (g.NKS) {
-        case 6: CALL_HLB(2, 6); break; case 8: CALL_HLB(2, 8); break; case 10: CALL_HLB(3, 10); break; case 12: CALL_HLB(3, 12); break;
-        case 14: CALL_HLB(4, 14); break; default: CALL_HLB(4, 16); break;
+    } break;
+    switch (prop_key(PF_HL, key / 100 % 100, key / 10 % 10, false)) {   // the chain kernel's part of the key: NKS and RT
+        HL_KEYS(CALL_HLB)
+        default: return RECON_ERR_UNSUPPORTED;
     }
 #undef CALL_HLB
     if (hipGetLastError() != hipSuccess) return RECON_ERR_LAUNCH;

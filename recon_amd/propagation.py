@@ -33,6 +33,39 @@ def _float_dtype(*ts):
     return next(iter(dts))
 
 
+# ------------------------------------------------------------------------------- which kernel instance ran
+_TRACE = None
+
+
+class trace_instances:
+    """`with trace_instances() as t: ...` — t collects (call, key) for every propagation launch of the block, `call` the C entry's name
+    and `key` the kernel instance the library selects for exactly the arguments of that launch (include/recon_hip.h:
+    recon_propagate_instance).  For tests: tests/test_prop_instances_gpu.py pins every row of its table to the instance it names.
+    One module-wide list: not re-entrant across threads (launches of another thread inside the block are recorded too), inert when unused."""
+
+    def __enter__(self):
+        global _TRACE
+        self.prev, _TRACE = _TRACE, []
+        return _TRACE
+
+    def __exit__(self, *exc):
+        global _TRACE
+        _TRACE = self.prev
+        return False
+
+
+def _launch(name, args, what=None):
+    """One propagation entry of the library on the current stream of the caller's device (set by the caller's on_device block)."""
+    L = _lib.lib()
+    if _TRACE is not None:
+        if name.startswith("recon_propagate_b16"):
+            key = L.recon_propagate_b16_instance(C.byref(args.fwd if name.endswith("bwd") else args), int(name.endswith("bwd")))
+        else:
+            key = (L.recon_propagate_bwd_instance if name.endswith("bwd") else L.recon_propagate_instance)(C.byref(args))
+        _TRACE.append((name, key))
+    _lib.check(getattr(L, name)(C.byref(args), _lib.current_stream()), what or name)
+
+
 # ------------------------------------------------------------------------------- host-side index builders
 def _pairs(n):
     return [(i, j) for i in range(n) for j in range(n) if i != j]     # channel order, conversion_util.py:6-20
@@ -197,7 +230,7 @@ class _Propagate(torch.autograd.Function):
             stats = torch.empty(B, 2 * L + 1, dtype=torch.float32, device=dev)
             args.stats = C.cast(stats.data_ptr(), _lib.c_f32p)
         with _lib.on_device(dev):
-            _lib.check(_lib.lib().recon_propagate_fwd(C.byref(args), _lib.current_stream()), "recon_propagate_fwd")
+            _launch("recon_propagate_fwd", args)
         if need:
             ctx.save_for_backward(h0c, head, tail, hs, *adjs)
             ctx.stats = stats
@@ -234,7 +267,7 @@ class _Propagate(torch.autograd.Function):
         args = _lib.PropBwdArgs(fwd, gout.data_ptr(), garr, g_h.data_ptr(), None, None, None, _lib.ptr(wide),
                                 blk[0].data_ptr() if chain is not None else None, blk[1].data_ptr() if chain is not None else None, _lib.ptr(chain))
         with _lib.on_device(dev):
-            _lib.check(_lib.lib().recon_propagate_bwd(C.byref(args), _lib.current_stream()), "recon_propagate_bwd")
+            _launch("recon_propagate_bwd", args)
         g_h0 = None
         if ctx.needs_input_grad[0]:
             g_h0 = (g_h if h0_bs else g_h.sum(0)).view(h0_shape)
@@ -302,7 +335,7 @@ class _PropagateB16(torch.autograd.Function):
         hs = torch.empty(L, B, Cn, S, dtype=torch.bfloat16, device=dev) if (need or form == 2 or want_states) else None
         args.h_saved = _lib.ptr(hs)
         with _lib.on_device(dev):
-            _lib.check(_lib.lib().recon_propagate_b16_fwd(C.byref(args), _lib.current_stream()), "recon_propagate_b16_fwd")
+            _launch("recon_propagate_b16_fwd", args)
         if need:
             ctx.save_for_backward(h0c, head, tail, hs, *adjs)
             ctx.meta = (B, Cn, S, L, dd, act, h0_bs, idx_bs, tuple(h0.shape), adj_shapes)
@@ -327,7 +360,7 @@ class _PropagateB16(torch.autograd.Function):
         args = _lib.PropB16BwdArgs(fwd, gout.data_ptr(), _lib.ptr_array(g_adjs), g_h.data_ptr(), ws.data_ptr(),
                                    _lib.ptr(blk_idx[0]) if blk_idx else None, _lib.ptr(blk_idx[1]) if blk_idx else None, None, None, None, None)
         with _lib.on_device(dev):
-            _lib.check(_lib.lib().recon_propagate_b16_bwd(C.byref(args), _lib.current_stream()), "recon_propagate_b16_bwd")
+            _launch("recon_propagate_b16_bwd", args)
         g_h0 = None
         if ctx.needs_input_grad[0]:
             g_h0 = (g_h if h0_bs else g_h.sum(0, dtype=torch.float32).to(torch.bfloat16)).view(h0_shape)
@@ -403,7 +436,7 @@ class _PropagateBlocks(torch.autograd.Function):
                              out.data_ptr(), _lib.ptr(hs), tarr, identity.data_ptr(), _lib.ptr(stats), None, 0)
         ws = _split_workspace(args, dev)
         with _lib.on_device(dev):
-            _lib.check(_lib.lib().recon_propagate_fwd(C.byref(args), _lib.current_stream()), "recon_propagate_fwd (block mode)")
+            _launch("recon_propagate_fwd", args, "recon_propagate_fwd (block mode)")
         if need:
             ctx.save_for_backward(h0c, identity, head, tail, hs, stats, *Ts)
             ctx.meta = (B, Cn, S, L, dd, act, h0_bs, idx_bs, tuple(h0.shape), t_shapes)
@@ -435,7 +468,7 @@ class _PropagateBlocks(torch.autograd.Function):
             ws = torch.empty(Lb.recon_propagate_identity_ws_floats(dd), dtype=torch.float32, device=dev) if g_I is not None else None
             args = _lib.PropBwdArgs(fwd, gout.data_ptr(), None, g_h.data_ptr(), garr, _lib.ptr(g_I), _lib.ptr(ws), None)
         with _lib.on_device(dev):
-            _lib.check(Lb.recon_propagate_bwd(C.byref(args), _lib.current_stream()), "recon_propagate_bwd (block mode)")
+            _launch("recon_propagate_bwd", args, "recon_propagate_bwd (block mode)")
         g_h0 = None
         if ctx.needs_input_grad[0]:
             g_h0 = (g_h if h0_bs else g_h.sum(0)).view(h0_shape)
@@ -495,7 +528,7 @@ def _propagate_blocks_b16(T_list, identity, n, h0, act, head, tail):
     out = torch.empty(B, Cn, L * dd, dtype=torch.bfloat16, device=h0.device)
     args = _b16_args(B, Cn, S, L, dd, act, None, h0c, h0_bs, head, tail, idx_bs, out, None, trans=Ts, identity=identity)
     with _lib.on_device(h0.device):
-        _lib.check(_lib.lib().recon_propagate_b16_fwd(C.byref(args), _lib.current_stream()), "recon_propagate_b16_fwd (block mode)")
+        _launch("recon_propagate_b16_fwd", args, "recon_propagate_b16_fwd (block mode)")
     return out
 
 
@@ -520,7 +553,7 @@ class _PropagateBlocksB16(torch.autograd.Function):
         hs = torch.empty(L, B, Cn, S, dtype=torch.bfloat16, device=dev)
         args = _b16_args(B, Cn, S, L, dd, act, None, h0c, h0_bs, head, tail, idx_bs, out, hs, trans=Ts, identity=identity)
         with _lib.on_device(dev):
-            _lib.check(_lib.lib().recon_propagate_b16_fwd(C.byref(args), _lib.current_stream()), "recon_propagate_b16_fwd (block mode)")
+            _launch("recon_propagate_b16_fwd", args, "recon_propagate_b16_fwd (block mode)")
         ctx.save_for_backward(h0c, identity, head, tail, hs, *Ts)
         ctx.meta = (B, Cn, S, L, dd, act, h0_bs, idx_bs, tuple(h0.shape), t_shapes)
         if want_states:
@@ -549,7 +582,7 @@ class _PropagateBlocksB16(torch.autograd.Function):
                                    _lib.ptr(blk_idx[0]) if blk_idx else None, _lib.ptr(blk_idx[1]) if blk_idx else None,
                                    _lib.ptr_array(g_Ts), _lib.ptr(g_I), _lib.ptr(diag), _lib.ptr(iws))
         with _lib.on_device(dev):
-            _lib.check(Lb.recon_propagate_b16_bwd(C.byref(args), _lib.current_stream()), "recon_propagate_b16_bwd (block mode)")
+            _launch("recon_propagate_b16_bwd", args, "recon_propagate_b16_bwd (block mode)")
         g_h0 = None
         if ctx.needs_input_grad[0]:
             g_h0 = (g_h if h0_bs else g_h.sum(0, dtype=torch.float32).to(torch.bfloat16)).view(h0_shape)

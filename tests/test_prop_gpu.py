@@ -121,22 +121,22 @@ def test_propagation_vs_oracle(n, d, L, B, act, per_batch, form, recon_config):
     tail = torch.from_numpy(get_tail_indices(n, d, bs=1)[0])
     Gr = torch.randn(B, C, dd * L, generator=g)
 
-    def run(device, build, prop):
-        Tl = [t.clone().to(device).requires_grad_(True) for t in Ts]
-        I = ident.clone().to(device).requires_grad_(True)
-        h = h0.clone().to(device).requires_grad_(per_batch)
+    def run(device, build, prop, dt):
+        Tl = [t.clone().to(device=device, dtype=dt).requires_grad_(True) for t in Ts]
+        I = ident.clone().to(device=device, dtype=dt).requires_grad_(True)
+        h = h0.clone().to(device=device, dtype=dt).requires_grad_(per_batch)
         adjs = [build(torch.relu(t), I, n) for t in Tl]
         out = prop(adjs, h, act, head.to(device), tail.to(device))
-        (out * Gr.to(device)).sum().backward()
-        return out, [t.grad for t in Tl], I.grad, h.grad
-    out_r, gT_r, gI_r, gh_r = run("cpu", O.build_block_adjacency, O.propagate)
-    out_h, gT_h, gI_h, gh_h = run(d_, build_block_adjacency, propagate)
-    close(out_h, out_r, what="out")
-    close(gI_h, gI_r, atol=1e-5, what="g_identity")
+        (out * Gr.to(device=device, dtype=dt)).sum().backward()
+        return out.detach(), [t.grad for t in Tl], I.grad, h.grad
+    out_r, gT_r, gI_r, gh_r = run("cpu", O.build_block_adjacency, O.propagate, torch.float64)      # the float64 oracle on the float32 inputs
+    out_h, gT_h, gI_h, gh_h = run(d_, build_block_adjacency, propagate, torch.float32)
+    close(out_h, out_r.float(), what="out")
+    close(gI_h, gI_r.float(), atol=1e-5, what="g_identity")
     for l in range(L):
-        close(gT_h[l], gT_r[l], atol=1e-5, what="g_T[%d]" % l)
+        close(gT_h[l], gT_r[l].float(), atol=1e-5, what="g_T[%d]" % l)
     if per_batch:
-        close(gh_h, gh_r, atol=1e-5, what="g_h0")
+        close(gh_h, gh_r.float(), atol=1e-5, what="g_h0")
 
 
 @pytest.mark.parametrize("S,C,dd,L,B,act,per_batch,grad", [
