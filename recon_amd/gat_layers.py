@@ -692,14 +692,7 @@ class _GATHeadsATPFunction(torch.autograd.Function):
 
 def _rowsum_by_index(rows, index, n_rows):
     """out[r] = sum of rows[k] over k with index[k] == r (index int64 [E]), fixed summation order."""
-    g = prepare_graph(_segment_key(index), None, n_rows, rows_only=True)
-    out = torch.empty(n_rows, rows.shape[1], dtype=torch.float32, device=rows.device)
-    L = _lib.lib()
-    ws = torch.empty(L.recon_spmm_rowsum_workspace_floats(g.E, rows.shape[1]), dtype=torch.float32, device=rows.device)
-    with _lib.on_device(rows.device):
-        _lib.check(L.recon_spmm_rowsum_fwd(C.byref(g.c), rows.data_ptr(), rows.shape[1], out.data_ptr(), ws.data_ptr(), _lib.current_stream()),
-                   "recon_spmm_rowsum_fwd")
-    return out
+    return _rowsum_keyed(rows, _segment_key(index), n_rows)
 
 
 def _rowsum_keyed(rows, key, n_rows):

@@ -184,6 +184,94 @@ def build_block_adjacency(T, identity, n):
 
 
 # ------------------------------------------------------------------------------- P2
+_STANDIN = 16        # a probe's non-null, 16-byte-aligned stand-in for a pointer the queries test but never follow
+
+
+class _Call:
+    """One propagation call, normalised once: the sizes, the strides, the contiguous tensors and the callers' shapes, for float32 and bfloat16,
+    adjacency mode (`mats` = the L adjacencies [B,S,S] or [B,1,S,S]) and block mode (`identity` and `n` given: `mats` = the L transition
+    tensors [B, n(n-1), (2d)^2] or [B, n-1, n, (2d)^2]).  Performs the shape checks, and writes the library's argument struct for a launch,
+    for the `fwd` field of a backward and (probe) for a query ahead of the call — every field by name."""
+    __slots__ = ("B", "Cn", "S", "L", "dd", "act", "h0_bs", "idx_bs", "b16", "dev", "h0", "head", "tail", "identity", "mats", "given", "h0_shape", "mat_shapes")
+
+    def __init__(self, h0, act, head, tail, mats, identity=None, n=None):
+        self.act, self.L, self.b16, self.dev, self.given = act, len(mats), h0.dtype == torch.bfloat16, h0.device, mats
+        if identity is None:
+            self.mats = mats = [a.contiguous().view(a.shape[0], a.shape[-2], a.shape[-1]) for a in mats]   # accepts [B,1,S,S]
+            B, S = mats[0].shape[0], mats[0].shape[-1]
+            h0 = h0.contiguous()
+            Cn = h0.shape[1] if h0.dim() == 4 else h0.shape[0]
+            dd = head.shape[-1]
+        else:
+            dd, B = identity.shape[0], mats[0].shape[0]
+            S, Cn = n * dd, n * (n - 1)
+            self.mats = [t.contiguous().view(B, Cn, dd * dd) for t in mats]
+            identity, h0 = identity.contiguous(), h0.contiguous()
+        self.B, self.Cn, self.S, self.dd = B, Cn, S, dd
+        self.h0, self.identity = h0, identity
+        self.h0_bs = Cn * S if h0.dim() == 4 else 0       # [B, C, S, 1] (RECON*: models/models.py:470), else [C, S, 1] shared (GPGNN: :260)
+        self.head, self.tail = head.contiguous(), tail.contiguous()
+        per_graph = head.dim() == 3 and head.shape[0] > 1   # the kernels then index head / tail by graph: rows for every graph, or one set shared
+        self.idx_bs = Cn * dd if per_graph else 0
+        if per_graph and head.shape[0] < B:
+            raise ValueError("head/tail indices hold %d batch rows but the batch has %d" % (head.shape[0], B))
+
+    def new(self, *shape):
+        return torch.empty(shape, dtype=torch.bfloat16 if self.b16 else torch.float32, device=self.dev)
+
+    def new_out(self):
+        return self.new(self.B, self.Cn, self.L * self.dd)
+
+    def new_states(self):
+        return self.new(self.L, self.B, self.Cn, self.S)
+
+    def args(self, out, hs=None, stats=None):
+        """recon_prop_args / recon_prop_b16_args of this call (include/recon_hip.h).  A launch passes its buffers; a backward's `fwd` field
+        passes grad_out as `out` (unused there, but the argument check wants it non-null).  The struct keeps the pointer array alive."""
+        a = (_lib.PropB16Args if self.b16 else _lib.PropArgs)(
+            B=self.B, C=self.Cn, S=self.S, L=self.L, dd=self.dd, act=_lib.ACT[self.act], h0=self.h0.data_ptr(), h0_batch_stride=self.h0_bs,
+            head_idx=self.head.data_ptr(), tail_idx=self.tail.data_ptr(), idx_batch_stride=self.idx_bs, out=out.data_ptr(), h_saved=_lib.ptr(hs))
+        if self.identity is None:
+            a.adj = _lib.ptr_array(self.mats)
+        else:
+            a.trans, a.identity = _lib.ptr_array(self.mats), self.identity.data_ptr()
+        if self.b16:
+            a.zeros = _lib.zero_page(self.dev).data_ptr()
+        else:
+            a.stats = _lib.ptr(stats)
+        return a
+
+    @staticmethod
+    def probe(b16, B, Cn, S, L, dd, h0=None, wide_blocks=False):
+        """The struct of a call that does not exist yet, for the library's form and workspace queries: sizes, and h0's address and stride
+        where the query looks at them.  wide_blocks: as block mode's wide-state forms see it — the queries test `trans`, `identity` and
+        `split_ws` for null and never follow them (csrc/prop.hip: recon_propagate_ws_bytes, recon_propagate_bwd_chain_ws_floats), so
+        stand-ins are set here, and nowhere else: `split_ws` where the library says that workspace exists."""
+        p = (_lib.PropB16Args if b16 else _lib.PropArgs)(B=B, C=Cn, S=S, L=L, dd=dd, act=1)
+        if h0 is not None:
+            p.h0, p.h0_batch_stride = h0.data_ptr(), Cn * S if h0.dim() == 4 else 0
+        if wide_blocks:
+            p.trans, p.identity = (C.c_void_p * 1)(), _STANDIN
+            p.split_ws_bytes = _lib.lib().recon_propagate_ws_bytes(C.byref(p))
+            p.split_ws = _STANDIN if p.split_ws_bytes else None
+        return p
+
+    def save(self, ctx, *extra):
+        """For the backward: the tensors through save_for_backward (`extra` first); on ctx only a tuple of the sizes and the callers' shapes."""
+        ctx.save_for_backward(*extra, self.h0, self.head, self.tail, self.identity, *self.mats)
+        ctx.sizes = (self.B, self.Cn, self.S, self.L, self.dd, self.act, self.h0_bs, self.idx_bs, self.b16, self.dev,
+                     self.h0.shape, [m.shape for m in self.given], len(extra))
+
+    @staticmethod
+    def saved(ctx):
+        """(the call save() saw, rebuilt from ctx.sizes and autograd's saved tensors; the `extra` tensors of save())."""
+        nz, t = object.__new__(_Call), ctx.saved_tensors
+        nz.B, nz.Cn, nz.S, nz.L, nz.dd, nz.act, nz.h0_bs, nz.idx_bs, nz.b16, nz.dev, nz.h0_shape, nz.mat_shapes, k = ctx.sizes
+        nz.h0, nz.head, nz.tail, nz.identity = t[k:k + 4]
+        nz.mats = list(t[k + 4:])
+        return nz, t[:k]
+
+
 def _split_workspace(args, dev):
     """Workspace of the wide-state two-term forward (include/recon_hip.h: recon_prop_args.split_ws); None where that form does not
     exist.  Sets the two fields of `args`; the caller keeps the returned tensor alive across the launch."""
@@ -195,89 +283,92 @@ def _split_workspace(args, dev):
     return ws
 
 
+def _chain_workspaces(nz, args):
+    """The wide-state backward on the forward's two-term f16 kernels (csrc/prop_hl.hip: all hops in one launch), for GP-GNN's block-structured
+    gather indices: sets fwd.split_ws, head_blk, tail_blk and chain_ws of `args` where that form exists.  Returns the tensors to keep alive
+    across the launch, the chain workspace last (None: no chain form)."""
+    blk = _index_blocks(nz.head, nz.tail, nz.dd, nz.S, align=16)
+    if blk is None:
+        return None, None
+    fwd = args.fwd
+    ws = _split_workspace(fwd, nz.dev)
+    nch = _lib.lib().recon_propagate_bwd_chain_ws_floats(C.byref(fwd)) if ws is not None else 0
+    if not nch:
+        return ws, None
+    chain = torch.empty(nch, dtype=torch.float32, device=nz.dev)
+    args.head_blk, args.tail_blk, args.chain_ws = blk[0].data_ptr(), blk[1].data_ptr(), chain.data_ptr()
+    return ws, chain
+
+
+def _forward_f32(ctx, nz, what=None):
+    need = any(ctx.needs_input_grad)
+    out = nz.new_out()
+    hs = nz.new_states() if need else None
+    args = nz.args(out, hs)
+    ws = _split_workspace(args, nz.dev)       # wide states (160 < S <= 512): A_l pre-split into half terms, slice by slice
+    stats = None
+    if need and _lib.lib().recon_propagate_form(C.byref(args)) & 1:
+        # two-term f16 kernels: the forward records per graph the max magnitudes of the states and adjacencies, the backward takes its
+        # per-tensor scales from them (include/recon_hip.h: recon_prop_args.stats)
+        stats = nz.new(nz.B, 2 * nz.L + 1)
+        args.stats = stats.data_ptr()
+    with _lib.on_device(nz.dev):
+        _launch("recon_propagate_fwd", args, what)
+    if need:
+        nz.save(ctx, hs, stats)
+    return out
+
+
+def _backward(ctx, gout, first, name, what, fill):
+    """What the four backwards share.  grad_out contiguous and 16-byte aligned (a view at an odd offset is copied: the kernels read it in
+    16-byte pieces); d loss / d A_l or d T_l for the inputs from position `first` on that want one; g_h [B, C, S]; the backward's struct
+    with `fwd`, grad_out, g_h and g_adj | g_trans set.  fill(nz, args, stats) adds the workspaces and fields of its form and returns
+    (g_identity or None, what must outlive the launch).  Then d loss / d h0 — g_h itself per graph, its sum over the graphs (bfloat16:
+    summed in fp32, rounded once) where h0 is shared — and every gradient in its input's own shape.  Returns (g_h0, g_identity, the L
+    gradients)."""
+    nz, (hs, stats) = _Call.saved(ctx)
+    gout = gout.contiguous()
+    if gout.data_ptr() % 16:
+        gout = gout.clone()
+    g_mats = [nz.new(*m.shape) if ctx.needs_input_grad[first + l] else None for l, m in enumerate(nz.mats)]
+    g_h = nz.new(nz.B, nz.Cn, nz.S)
+    fwd = nz.args(gout, hs, stats)
+    args = (_lib.PropB16BwdArgs if nz.b16 else _lib.PropBwdArgs)(fwd=fwd, grad_out=gout.data_ptr(), g_h=g_h.data_ptr())
+    garr = _lib.ptr_array(g_mats)
+    if nz.identity is None:
+        args.g_adj = garr
+    else:
+        args.g_trans = garr
+    g_identity, keep = fill(nz, args, stats)
+    with _lib.on_device(nz.dev):
+        _launch(name, args, what)
+    g_h0 = None
+    if ctx.needs_input_grad[0]:
+        g_h0 = (g_h if nz.h0_bs else g_h.sum(0, dtype=torch.float32).to(torch.bfloat16) if nz.b16 else g_h.sum(0)).view(nz.h0_shape)
+    return g_h0, g_identity, tuple(g.view(sh) if g is not None else None for g, sh in zip(g_mats, nz.mat_shapes))
+
+
 class _Propagate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h0, act, head, tail, *adjs):
         _lib.require_gpu(h0, head, tail, *adjs, dtype=torch.float32, **_ONE_DTYPE)
-        L = len(adjs)
-        adj_shapes = [tuple(a.shape) for a in adjs]
-        adjs = [a.contiguous().view(a.shape[0], a.shape[-2], a.shape[-1]) for a in adjs]   # accepts [B,1,S,S]
-        B, S = adjs[0].shape[0], adjs[0].shape[-1]
-        h0c = h0.contiguous()
-        if h0c.dim() == 4:            # [B, C, S, 1]   (RECON*: models/models.py:470)
-            Cn = h0c.shape[1]
-            h0_bs = Cn * S
-        else:                         # [C, S, 1]      (GPGNN: models/models.py:260)
-            Cn = h0c.shape[0]
-            h0_bs = 0
-        head, tail = head.contiguous(), tail.contiguous()
-        dd = head.shape[-1]
-        idx_bs = Cn * dd if head.dim() == 3 and head.shape[0] > 1 else 0
-        if head.dim() == 3 and head.shape[0] < B and head.shape[0] > 1:
-            raise ValueError("head/tail indices hold %d batch rows but the batch has %d" % (head.shape[0], B))
-        dev = h0.device
-        out = torch.empty(B, Cn, L * dd, dtype=torch.float32, device=dev)
-        need = any(ctx.needs_input_grad)
-        hs = torch.empty(L, B, Cn, S, dtype=torch.float32, device=dev) if need else None
-        parr = _lib.ptr_array(adjs)
-        args = _lib.PropArgs(B, Cn, S, L, dd, _lib.ACT[act], parr, h0c.data_ptr(), h0_bs, head.data_ptr(),
-                             tail.data_ptr(), idx_bs, out.data_ptr(), _lib.ptr(hs), None, None, None, None, 0)
-        ws = _split_workspace(args, dev)       # wide states (160 < S <= 512): A_l pre-split into half terms, slice by slice
-        stats = None
-        if need and _lib.lib().recon_propagate_form(C.byref(args)) & 1:
-            # two-term f16 kernels: the forward records per graph the max magnitudes of the states and adjacencies, the backward takes its
-            # per-tensor scales from them (include/recon_hip.h: recon_prop_args.stats)
-            stats = torch.empty(B, 2 * L + 1, dtype=torch.float32, device=dev)
-            args.stats = C.cast(stats.data_ptr(), _lib.c_f32p)
-        with _lib.on_device(dev):
-            _launch("recon_propagate_fwd", args)
-        if need:
-            ctx.save_for_backward(h0c, head, tail, hs, *adjs)
-            ctx.stats = stats
-            ctx.meta = (B, Cn, S, L, dd, act, h0_bs, idx_bs, tuple(h0.shape), adj_shapes)
-        return out
+        return _forward_f32(ctx, _Call(h0, act, head, tail, adjs))
 
     @staticmethod
     def backward(ctx, gout):
-        h0c, head, tail, hs, *adjs = ctx.saved_tensors
-        B, Cn, S, L, dd, act, h0_bs, idx_bs, h0_shape, adj_shapes = ctx.meta
-        dev = gout.device
-        gout = gout.contiguous()
-        if gout.data_ptr() % 16:
-            gout = gout.clone()                                         # (a view at an odd offset: the wide-state kernels read 16-byte pieces)
-        g_adjs = [torch.empty(B, S, S, dtype=torch.float32, device=dev) if ctx.needs_input_grad[4 + l] else None
-                  for l in range(L)]
-        g_h = torch.empty(B, Cn, S, dtype=torch.float32, device=dev)
-        parr, garr = _lib.ptr_array(adjs), _lib.ptr_array(g_adjs)
-        fwd = _lib.PropArgs(B, Cn, S, L, dd, _lib.ACT[act], parr, h0c.data_ptr(), h0_bs, head.data_ptr(), tail.data_ptr(),
-                            idx_bs, None, hs.data_ptr(), None, None, _lib.ptr(ctx.stats), None, 0)
-        fwd.out = gout.data_ptr()      # unused by the backward; must be non-null for the argument check
-        # wide states (S > 160): GP-GNN's block-structured gather indices let the chain of products run on the forward's two-term f16 kernel
-        # (all hops in one launch); otherwise both products of a hop are batched fp32 GEMMs
-        blk = chain = ws = wide = None
-        if S > 160 and dd == 16 and not idx_bs and h0c.data_ptr() % 16 == 0 and all(a.data_ptr() % 16 == 0 for a in adjs):
-            blk = _index_blocks(head, tail, dd, S, align=16)
-            if blk is not None:
-                ws = _split_workspace(fwd, dev)
-                nch = _lib.lib().recon_propagate_bwd_chain_ws_floats(C.byref(fwd)) if ws is not None else 0
-                chain = torch.empty(nch, dtype=torch.float32, device=dev) if nch else None
-        if chain is None:
-            nws = _lib.lib().recon_propagate_bwd_ws_floats(C.byref(fwd))
-            wide = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
-        args = _lib.PropBwdArgs(fwd, gout.data_ptr(), garr, g_h.data_ptr(), None, None, None, _lib.ptr(wide),
-                                blk[0].data_ptr() if chain is not None else None, blk[1].data_ptr() if chain is not None else None, _lib.ptr(chain))
-        with _lib.on_device(dev):
-            _launch("recon_propagate_bwd", args)
-        g_h0 = None
-        if ctx.needs_input_grad[0]:
-            g_h0 = (g_h if h0_bs else g_h.sum(0)).view(h0_shape)
-        return (g_h0, None, None, None) + tuple(g.view(sh) if g is not None else None for g, sh in zip(g_adjs, adj_shapes))
-
-
-def _b16_args(B, Cn, S, L, dd, act, adjs, h0c, h0_bs, head, tail, idx_bs, out, hs, trans=None, identity=None):
-    return _lib.PropB16Args(B, Cn, S, L, dd, _lib.ACT[act], _lib.ptr_array(adjs) if adjs is not None else None, h0c.data_ptr(), h0_bs,
-                            head.data_ptr(), tail.data_ptr(), idx_bs, _lib.ptr(out), _lib.ptr(hs),
-                            _lib.ptr_array(trans) if trans is not None else None, _lib.ptr(identity), _lib.zero_page(h0c.device).data_ptr())
+        def fill(nz, args, stats):
+            # wide states (the library sizes `wide_ws` for them alone): GP-GNN's block-structured gather indices let the chain of products run
+            # on the forward's two-term f16 kernel (all hops in one launch); otherwise both products of a hop are batched fp32 GEMMs
+            nws = _lib.lib().recon_propagate_bwd_ws_floats(C.byref(args.fwd))
+            ws = chain = wide = None
+            if nws and nz.dd == 16 and not nz.idx_bs and nz.h0.data_ptr() % 16 == 0 and all(a.data_ptr() % 16 == 0 for a in nz.mats):
+                ws, chain = _chain_workspaces(nz, args)
+            if nws and chain is None:
+                wide = torch.empty(nws, dtype=torch.float32, device=nz.dev)
+                args.wide_ws = wide.data_ptr()
+            return None, (ws, chain, wide)
+        g_h0, _, g_adjs = _backward(ctx, gout, 4, "recon_propagate_bwd", None, fill)
+        return (g_h0, None, None, None) + g_adjs
 
 
 _BLK_IDX = {}
@@ -306,6 +397,34 @@ def _index_blocks(head, tail, dd, S, align=8):
     return hit[0]
 
 
+def _fill_b16(nz, args):
+    """Both bfloat16 backwards: the second [B, C, S] buffer the products alternate with, and the index blocks where the batch shares them."""
+    ws = nz.new(nz.B, nz.Cn, nz.S)
+    args.ws = ws.data_ptr()
+    blk = _index_blocks(nz.head, nz.tail, nz.dd, nz.S) if nz.idx_bs == 0 else None
+    if blk:
+        args.head_blk, args.tail_blk = blk[0].data_ptr(), blk[1].data_ptr()
+    return ws, blk
+
+
+def _forward_b16(ctx, nz, want_states=False, what=None):
+    """The bfloat16 forward (ctx None: inference outside autograd).  It stores the states H^1 .. H^L where the backward, the caller or the
+    library's GEMM form (2: its products go through them) wants them."""
+    need = ctx is not None and any(ctx.needs_input_grad)
+    out = nz.new_out()
+    args = nz.args(out)
+    hs = nz.new_states() if need or want_states or _lib.lib().recon_propagate_b16_form(C.byref(args)) == 2 else None
+    args.h_saved = _lib.ptr(hs)
+    with _lib.on_device(nz.dev):
+        _launch("recon_propagate_b16_fwd", args, what)
+    if need:
+        nz.save(ctx, hs, None)
+    if want_states:                                                       # the states [L, B, C, S] as the forward stored them (no gradient)
+        ctx.mark_non_differentiable(hs)
+        return out, hs
+    return out
+
+
 class _PropagateB16(torch.autograd.Function):
     """models/models.py:260-274 on bfloat16 tensors (csrc/prop_b16.hip): bf16 storage, fp32 accumulation, every state rounded to bf16 once
     per hop, gradients in bf16."""
@@ -313,64 +432,18 @@ class _PropagateB16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h0, act, head, tail, want_states, *adjs):
         _lib.require_gpu(h0, head, tail, *adjs, dtype=torch.bfloat16, **_ONE_DTYPE)
-        L = len(adjs)
-        adj_shapes = [tuple(a.shape) for a in adjs]
-        adjs = [a.contiguous().view(a.shape[0], a.shape[-2], a.shape[-1]) for a in adjs]
-        B, S = adjs[0].shape[0], adjs[0].shape[-1]
-        h0c = h0.contiguous()
-        if h0c.dim() == 4:
-            Cn, h0_bs = h0c.shape[1], h0c.shape[1] * S
-        else:
-            Cn, h0_bs = h0c.shape[0], 0
-        head, tail = head.contiguous(), tail.contiguous()
-        dd = head.shape[-1]
-        idx_bs = Cn * dd if head.dim() == 3 and head.shape[0] > 1 else 0
-        if head.dim() == 3 and head.shape[0] < B and head.shape[0] > 1:
-            raise ValueError("head/tail indices hold %d batch rows but the batch has %d" % (head.shape[0], B))
-        dev = h0.device
-        out = torch.empty(B, Cn, L * dd, dtype=torch.bfloat16, device=dev)
-        need = any(ctx.needs_input_grad)
-        args = _b16_args(B, Cn, S, L, dd, act, adjs, h0c, h0_bs, head, tail, idx_bs, out, None)
-        form = _lib.lib().recon_propagate_b16_form(C.byref(args))
-        hs = torch.empty(L, B, Cn, S, dtype=torch.bfloat16, device=dev) if (need or form == 2 or want_states) else None
-        args.h_saved = _lib.ptr(hs)
-        with _lib.on_device(dev):
-            _launch("recon_propagate_b16_fwd", args)
-        if need:
-            ctx.save_for_backward(h0c, head, tail, hs, *adjs)
-            ctx.meta = (B, Cn, S, L, dd, act, h0_bs, idx_bs, tuple(h0.shape), adj_shapes)
-        if want_states:                                                   # the states H^1 .. H^L [L, B, C, S] as the forward stored them (no gradient)
-            ctx.mark_non_differentiable(hs)
-            return out, hs
-        return out
+        return _forward_b16(ctx, _Call(h0, act, head, tail, adjs), want_states)
 
     @staticmethod
     def backward(ctx, gout, *_unused):
-        h0c, head, tail, hs, *adjs = ctx.saved_tensors
-        B, Cn, S, L, dd, act, h0_bs, idx_bs, h0_shape, adj_shapes = ctx.meta
-        dev = gout.device
-        gout = gout.contiguous()
-        if gout.data_ptr() % 16:                 # a contiguous view at an odd storage offset: the kernels read grad_out in 16-byte pieces
-            gout = gout.clone()
-        g_adjs = [torch.empty(B, S, S, dtype=torch.bfloat16, device=dev) if ctx.needs_input_grad[5 + l] else None for l in range(L)]
-        g_h = torch.empty(B, Cn, S, dtype=torch.bfloat16, device=dev)
-        ws = torch.empty(B, Cn, S, dtype=torch.bfloat16, device=dev)
-        fwd = _b16_args(B, Cn, S, L, dd, act, adjs, h0c, h0_bs, head, tail, idx_bs, gout, hs)     # `out` is unused by the backward
-        blk_idx = _index_blocks(head, tail, dd, S) if idx_bs == 0 else None
-        args = _lib.PropB16BwdArgs(fwd, gout.data_ptr(), _lib.ptr_array(g_adjs), g_h.data_ptr(), ws.data_ptr(),
-                                   _lib.ptr(blk_idx[0]) if blk_idx else None, _lib.ptr(blk_idx[1]) if blk_idx else None, None, None, None, None)
-        with _lib.on_device(dev):
-            _launch("recon_propagate_b16_bwd", args)
-        g_h0 = None
-        if ctx.needs_input_grad[0]:
-            g_h0 = (g_h if h0_bs else g_h.sum(0, dtype=torch.float32).to(torch.bfloat16)).view(h0_shape)
-        return (g_h0, None, None, None, None) + tuple(g.view(sh) if g is not None else None for g, sh in zip(g_adjs, adj_shapes))
+        g_h0, _, g_adjs = _backward(ctx, gout, 5, "recon_propagate_b16_bwd", None, lambda nz, args, stats: (None, _fill_b16(nz, args)))
+        return (g_h0, None, None, None, None) + g_adjs
 
 
 def _propagate_b16(adj_list, h0, nonlinearity, head_indices, tail_indices, return_states=False):
     B, S = adj_list[0].shape[0], adj_list[0].shape[-1]
     Cn = h0.shape[1] if h0.dim() == 4 else h0.shape[0]
-    probe = _lib.PropB16Args(B, Cn, S, len(adj_list), head_indices.shape[-1], 1, None, None, 0, None, None, 0, None, None, None, None, None)
+    probe = _Call.probe(True, B, Cn, S, len(adj_list), head_indices.shape[-1])
     aligned = all(a.data_ptr() % 16 == 0 for a in adj_list) and h0.data_ptr() % 16 == 0
     if not aligned or _lib.lib().recon_propagate_b16_form(C.byref(probe)) == 0:
         # shapes the bf16 kernels do not take (S % 8 != 0): bf16 storage around the float32 kernels
@@ -415,121 +488,81 @@ class _PropagateBlocks(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h0, identity, act, head, tail, n, *Ts):
         _lib.require_gpu(h0, identity, head, tail, *Ts, dtype=torch.float32, **_ONE_DTYPE)
-        L = len(Ts)
-        dd = identity.shape[0]
-        B = Ts[0].shape[0]
-        S, Cn = n * dd, n * (n - 1)
-        t_shapes = [tuple(t.shape) for t in Ts]
-        Ts = [t.contiguous().view(B, Cn, dd * dd) for t in Ts]
-        identity = identity.contiguous()
-        h0c = h0.contiguous()
-        h0_bs = Cn * S if h0c.dim() == 4 else 0
-        head, tail = head.contiguous(), tail.contiguous()
-        idx_bs = Cn * dd if head.dim() == 3 and head.shape[0] > 1 else 0
-        dev = h0.device
-        out = torch.empty(B, Cn, L * dd, dtype=torch.float32, device=dev)
-        need = any(ctx.needs_input_grad)
-        hs = torch.empty(L, B, Cn, S, dtype=torch.float32, device=dev) if need else None
-        stats = torch.empty(B, 2 * L + 1, dtype=torch.float32, device=dev) if (need and S <= 160) else None
-        tarr = _lib.ptr_array(Ts)
-        args = _lib.PropArgs(B, Cn, S, L, dd, _lib.ACT[act], None, h0c.data_ptr(), h0_bs, head.data_ptr(), tail.data_ptr(), idx_bs,
-                             out.data_ptr(), _lib.ptr(hs), tarr, identity.data_ptr(), _lib.ptr(stats), None, 0)
-        ws = _split_workspace(args, dev)
-        with _lib.on_device(dev):
-            _launch("recon_propagate_fwd", args, "recon_propagate_fwd (block mode)")
-        if need:
-            ctx.save_for_backward(h0c, identity, head, tail, hs, stats, *Ts)
-            ctx.meta = (B, Cn, S, L, dd, act, h0_bs, idx_bs, tuple(h0.shape), t_shapes)
-        return out
+        return _forward_f32(ctx, _Call(h0, act, head, tail, Ts, identity, n), "recon_propagate_fwd (block mode)")
 
     @staticmethod
     def backward(ctx, gout):
-        h0c, identity, head, tail, hs, stats, *Ts = ctx.saved_tensors
-        B, Cn, S, L, dd, act, h0_bs, idx_bs, h0_shape, t_shapes = ctx.meta
-        dev = gout.device
-        gout = gout.contiguous()
-        if gout.data_ptr() % 16:
-            gout = gout.clone()
-        g_Ts = [torch.empty(B, Cn, dd * dd, dtype=torch.float32, device=dev) if ctx.needs_input_grad[6 + l] else None for l in range(L)]
-        g_I = torch.empty(dd, dd, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-        g_h = torch.empty(B, Cn, S, dtype=torch.float32, device=dev)
-        Lb = _lib.lib()
-        tarr, garr = _lib.ptr_array(Ts), _lib.ptr_array(g_Ts)
-        fwd = _lib.PropArgs(B, Cn, S, L, dd, _lib.ACT[act], None, h0c.data_ptr(), h0_bs, head.data_ptr(), tail.data_ptr(), idx_bs,
-                            gout.data_ptr(), hs.data_ptr(), tarr, identity.data_ptr(), _lib.ptr(stats), None, 0)
-        if S > 160:
-            # wide states: chain + d T products on the two-term f16 kernels of csrc/prop_hl.hip (block-structured indices: propagate_blocks checked)
-            blk = _index_blocks(head, tail, dd, S, align=16)
-            sws = _split_workspace(fwd, dev)
-            chain = torch.empty(Lb.recon_propagate_bwd_chain_ws_floats(C.byref(fwd)), dtype=torch.float32, device=dev)
-            args = _lib.PropBwdArgs(fwd, gout.data_ptr(), None, g_h.data_ptr(), garr, _lib.ptr(g_I), None, None,
-                                    blk[0].data_ptr(), blk[1].data_ptr(), chain.data_ptr())
-        else:
-            ws = torch.empty(Lb.recon_propagate_identity_ws_floats(dd), dtype=torch.float32, device=dev) if g_I is not None else None
-            args = _lib.PropBwdArgs(fwd, gout.data_ptr(), None, g_h.data_ptr(), garr, _lib.ptr(g_I), _lib.ptr(ws), None)
-        with _lib.on_device(dev):
-            _launch("recon_propagate_bwd", args, "recon_propagate_bwd (block mode)")
-        g_h0 = None
-        if ctx.needs_input_grad[0]:
-            g_h0 = (g_h if h0_bs else g_h.sum(0)).view(h0_shape)
-        return (g_h0, g_I, None, None, None, None) + tuple(g.view(sh) if g is not None else None for g, sh in zip(g_Ts, t_shapes))
+        def fill(nz, args, stats):
+            g_I = nz.new(nz.dd, nz.dd) if ctx.needs_input_grad[1] else None
+            args.g_identity = _lib.ptr(g_I)
+            if stats is None:
+                # the forward asked recon_propagate_form and took no stats: the two-term form of csrc/prop_h.hip does not exist for these
+                # states, and block mode's other backward is the wide-state chain + d T products of csrc/prop_hl.hip (csrc/prop.hip: plan_bwd;
+                # block-structured indices: propagate_blocks checked)
+                return g_I, _chain_workspaces(nz, args)
+            ws = nz.new(_lib.lib().recon_propagate_identity_ws_floats(nz.dd)) if g_I is not None else None
+            args.identity_ws = _lib.ptr(ws)
+            return g_I, ws
+        g_h0, g_I, g_Ts = _backward(ctx, gout, 6, "recon_propagate_bwd", "recon_propagate_bwd (block mode)", fill)
+        return (g_h0, g_I, None, None, None, None) + g_Ts
+
+
+def _blocks_gate(B, n, dd, max_n=None):
+    """What every block-mode form asks of the sizes: 2d = 16, 2 <= n (<= max_n), one launch's worth of graphs.  RECON_PROP_BLOCKS=0, read at
+    every call, sends every call through the adjacency."""
+    return (dd == 16 and n >= 2 and (max_n is None or n <= max_n) and 0 < B <= _lib.MAX_BATCH
+            and os.environ.get("RECON_PROP_BLOCKS", "1") != "0")
 
 
 def _blocks_wide_trainable(B, n, dd, h0, L, head, tail):
-    """10 < n <= 32 with gradients in float32: the forward reads the transition tensors in place (csrc/prop_hl.hip) and the backward's chain /
-    d T products run on its mirror images — for GP-GNN's block-structured gather indices shared by the batch."""
+    """Wide states (10 < n <= 32) with gradients in float32: the forward reads the transition tensors in place (csrc/prop_hl.hip) and the
+    backward's chain / d T products run on its mirror images — for GP-GNN's block-structured gather indices shared by the batch.  The
+    library says whether: the split workspace and the chain workspace exist for exactly these shapes."""
     if head.dim() == 3 and head.shape[0] > 1:
         return False
     Cn, S = n * (n - 1), n * dd
-    if _index_blocks(head.contiguous(), tail.contiguous(), dd, S, align=16) is None:
+    probe = _Call.probe(False, B, Cn, S, max(1, int(L)), dd, h0, wide_blocks=True)
+    if not (probe.split_ws and _lib.lib().recon_propagate_bwd_chain_ws_floats(C.byref(probe)) > 0):
         return False
-    probe = _lib.PropArgs(B, Cn, S, max(1, int(L)), dd, 1, None, h0.data_ptr(), Cn * S if h0.dim() == 4 else 0, None, None, 0, None, None, (C.c_void_p * 1)(),
-                          16, None, None, 0)
-    probe.split_ws_bytes = _lib.lib().recon_propagate_ws_bytes(C.byref(probe))
-    probe.split_ws = 1
-    return probe.split_ws_bytes > 0 and _lib.lib().recon_propagate_bwd_chain_ws_floats(C.byref(probe)) > 0
+    return _index_blocks(head.contiguous(), tail.contiguous(), dd, S, align=16) is not None
 
 
 def blocks_mode_available(B, n, dd, h0, need_grad=True, L=1, T_list=None):
     """Whether propagate_blocks() runs fused (two-term f16 kernels for the forward and, when gradients are wanted, for the backward:
     2d = 16, n <= 9; forward only — inference — for 10 <= n <= 32; B within one launch).  `L` (hops) and `T_list` (the transition tensors:
     16-byte alignment) make the probe exact: the wide form's LDS budget grows with the hop count."""
-    if dd != 16 or n < 2 or n > 32 or B > _lib.MAX_BATCH or B == 0 or os.environ.get("RECON_PROP_BLOCKS", "1") == "0":
+    if not _blocks_gate(B, n, dd, 32):
         return False
     if T_list is not None and any(t.data_ptr() % 16 for t in T_list):
         return False
-    Cn, S = n * (n - 1), n * dd
-    probe = _lib.PropArgs(B, Cn, S, max(1, int(L)), dd, 1, None, h0.data_ptr(), Cn * S if h0.dim() == 4 else 0, None, None, 0, None, None, None, None, None, None, 0)
-    if n > 10:          # wide states: the forward-only form of csrc/prop_hl.hip reads the transition tensors in place too
-        return (not need_grad) and h0.data_ptr() % 16 == 0 and _lib.lib().recon_propagate_ws_bytes(C.byref(probe)) > 0
+    probe = _Call.probe(False, B, n * (n - 1), n * dd, max(1, int(L)), dd, h0)
     form = _lib.lib().recon_propagate_form(C.byref(probe))
-    return form == 3 or (form == 1 and not need_grad)
+    if form:            # the state fits a workgroup's LDS; bit 1: the backward's two-term form exists too
+        return form == 3 or not need_grad
+    # wide states: the forward-only form of csrc/prop_hl.hip reads the transition tensors in place too, where its split workspace exists
+    return (not need_grad) and h0.data_ptr() % 16 == 0 and _lib.lib().recon_propagate_ws_bytes(C.byref(probe)) > 0
 
 
-def _blocks_b16_available(B, n, dd, h0, T_list, identity):
-    if dd != 16 or n < 2 or n > 32 or B > _lib.MAX_BATCH or B == 0 or os.environ.get("RECON_PROP_BLOCKS", "1") == "0":
+# csrc/prop_b16.hip, bwd_b16_check: `8ull * a->S * sizeof(float) > 64 * 1024` is unsupported (its row kernel keeps 8 rows of S floats in LDS).
+# No query answers it without the call's pointers, so the host states it, here alone.
+_B16_BWD_MAX_S = 64 * 1024 // (8 * 4)
+
+
+def _blocks_b16_available(B, n, dd, h0, T_list, identity, need_grad):
+    """Block mode on bfloat16 tensors.  Inference: the kernels with the state in LDS (forms 1 and 3), n <= 32, contiguous transition
+    tensors.  With gradients: any form the bfloat16 kernels take (S = 16 n: always a multiple of 8), states the backward's row kernel holds."""
+    if not _blocks_gate(B, n, dd, None if need_grad else 32):
         return False
-    if h0.data_ptr() % 16 or identity.data_ptr() % 16 or any(T.data_ptr() % 16 or not T.is_contiguous() for T in T_list):
+    if h0.data_ptr() % 16 or identity.data_ptr() % 16 or any(T.data_ptr() % 16 or not (need_grad or T.is_contiguous()) for T in T_list):
         return False
-    probe = _lib.PropB16Args(B, n * (n - 1), n * dd, len(T_list), dd, 1, None, None, 0, None, None, 0, None, None, None, None, None)
-    return _lib.lib().recon_propagate_b16_form(C.byref(probe)) in (1, 3)     # the kernels with the state in LDS read T in place
+    form = _lib.lib().recon_propagate_b16_form(C.byref(_Call.probe(True, B, n * (n - 1), n * dd, len(T_list), dd)))
+    return (form != 0 and n * dd <= _B16_BWD_MAX_S) if need_grad else form in (1, 3)
 
 
 def _propagate_blocks_b16(T_list, identity, n, h0, act, head, tail):
     """Inference: block adjacency + propagation in one launch on bfloat16 tensors; A_l is never written."""
     _lib.require_gpu(h0, identity, head, tail, *T_list, dtype=torch.bfloat16, **_ONE_DTYPE)
-    L, dd, B = len(T_list), identity.shape[0], T_list[0].shape[0]
-    S, Cn = n * dd, n * (n - 1)
-    Ts = [t.contiguous().view(B, Cn, dd * dd) for t in T_list]
-    identity, h0c = identity.contiguous(), h0.contiguous()
-    h0_bs = Cn * S if h0c.dim() == 4 else 0
-    head, tail = head.contiguous(), tail.contiguous()
-    idx_bs = Cn * dd if head.dim() == 3 and head.shape[0] > 1 else 0
-    out = torch.empty(B, Cn, L * dd, dtype=torch.bfloat16, device=h0.device)
-    args = _b16_args(B, Cn, S, L, dd, act, None, h0c, h0_bs, head, tail, idx_bs, out, None, trans=Ts, identity=identity)
-    with _lib.on_device(h0.device):
-        _launch("recon_propagate_b16_fwd", args, "recon_propagate_b16_fwd (block mode)")
-    return out
+    return _forward_b16(None, _Call(h0, act, head, tail, T_list, identity, n), what="recon_propagate_b16_fwd (block mode)")
 
 
 class _PropagateBlocksB16(torch.autograd.Function):
@@ -540,93 +573,48 @@ class _PropagateBlocksB16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h0, identity, act, head, tail, n, want_states, *Ts):
         _lib.require_gpu(h0, identity, head, tail, *Ts, dtype=torch.bfloat16, **_ONE_DTYPE)
-        L, dd, B = len(Ts), identity.shape[0], Ts[0].shape[0]
-        S, Cn = n * dd, n * (n - 1)
-        t_shapes = [tuple(t.shape) for t in Ts]
-        Ts = [t.contiguous().view(B, Cn, dd * dd) for t in Ts]
-        identity, h0c = identity.contiguous(), h0.contiguous()
-        h0_bs = Cn * S if h0c.dim() == 4 else 0
-        head, tail = head.contiguous(), tail.contiguous()
-        idx_bs = Cn * dd if head.dim() == 3 and head.shape[0] > 1 else 0
-        dev = h0.device
-        out = torch.empty(B, Cn, L * dd, dtype=torch.bfloat16, device=dev)
-        hs = torch.empty(L, B, Cn, S, dtype=torch.bfloat16, device=dev)
-        args = _b16_args(B, Cn, S, L, dd, act, None, h0c, h0_bs, head, tail, idx_bs, out, hs, trans=Ts, identity=identity)
-        with _lib.on_device(dev):
-            _launch("recon_propagate_b16_fwd", args, "recon_propagate_b16_fwd (block mode)")
-        ctx.save_for_backward(h0c, identity, head, tail, hs, *Ts)
-        ctx.meta = (B, Cn, S, L, dd, act, h0_bs, idx_bs, tuple(h0.shape), t_shapes)
-        if want_states:
-            ctx.mark_non_differentiable(hs)
-            return out, hs
-        return out
+        return _forward_b16(ctx, _Call(h0, act, head, tail, Ts, identity, n), want_states, "recon_propagate_b16_fwd (block mode)")
 
     @staticmethod
     def backward(ctx, gout, *_unused):
-        h0c, identity, head, tail, hs, *Ts = ctx.saved_tensors
-        B, Cn, S, L, dd, act, h0_bs, idx_bs, h0_shape, t_shapes = ctx.meta
-        dev = gout.device
-        gout = gout.contiguous()
-        if gout.data_ptr() % 16:
-            gout = gout.clone()
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        g_Ts = [torch.empty(B, Cn, dd * dd, **bf) if ctx.needs_input_grad[7 + l] else None for l in range(L)]
-        g_I = torch.empty(dd, dd, **bf) if ctx.needs_input_grad[1] else None
-        g_h, ws = torch.empty(B, Cn, S, **bf), torch.empty(B, Cn, S, **bf)
-        Lb = _lib.lib()
-        fwd = _b16_args(B, Cn, S, L, dd, act, None, h0c, h0_bs, head, tail, idx_bs, gout, hs, trans=Ts, identity=identity)
-        diag = torch.empty(Lb.recon_propagate_b16_bwd_diag_elems(C.byref(fwd)), **bf) if g_I is not None else None
-        iws = torch.empty(Lb.recon_block_adjacency_b16_bwd_workspace_floats(dd), dtype=torch.float32, device=dev) if g_I is not None else None
-        blk_idx = _index_blocks(head, tail, dd, S) if idx_bs == 0 else None
-        args = _lib.PropB16BwdArgs(fwd, gout.data_ptr(), None, g_h.data_ptr(), ws.data_ptr(),
-                                   _lib.ptr(blk_idx[0]) if blk_idx else None, _lib.ptr(blk_idx[1]) if blk_idx else None,
-                                   _lib.ptr_array(g_Ts), _lib.ptr(g_I), _lib.ptr(diag), _lib.ptr(iws))
-        with _lib.on_device(dev):
-            _launch("recon_propagate_b16_bwd", args, "recon_propagate_b16_bwd (block mode)")
-        g_h0 = None
-        if ctx.needs_input_grad[0]:
-            g_h0 = (g_h if h0_bs else g_h.sum(0, dtype=torch.float32).to(torch.bfloat16)).view(h0_shape)
-        return (g_h0, g_I, None, None, None, None, None) + tuple(g.view(sh) if g is not None else None for g, sh in zip(g_Ts, t_shapes))
-
-
-def _blocks_b16_trainable(B, n, dd, h0, T_list, identity):
-    """Block mode with gradients: 2d = 16 and a state size the bfloat16 kernels take (S = 16 n: always a multiple of 8)."""
-    if dd != 16 or n < 2 or B > _lib.MAX_BATCH or B == 0 or os.environ.get("RECON_PROP_BLOCKS", "1") == "0":
-        return False
-    if h0.data_ptr() % 16 or identity.data_ptr() % 16 or any(T.data_ptr() % 16 for T in T_list):
-        return False
-    Cn, S = n * (n - 1), n * dd
-    if Cn * S >= 2 ** 31 or 8 * S * 4 > 64 * 1024:
-        return False
-    probe = _lib.PropB16Args(B, Cn, S, len(T_list), dd, 1, None, None, 0, None, None, 0, None, None, None, None, None)
-    return _lib.lib().recon_propagate_b16_form(C.byref(probe)) != 0
+        def fill(nz, args, stats):
+            g_I = diag = iws = None
+            if ctx.needs_input_grad[1]:
+                Lb = _lib.lib()
+                g_I = nz.new(nz.dd, nz.dd)
+                diag = nz.new(Lb.recon_propagate_b16_bwd_diag_elems(C.byref(args.fwd)))
+                iws = torch.empty(Lb.recon_block_adjacency_b16_bwd_workspace_floats(nz.dd), dtype=torch.float32, device=nz.dev)
+                args.g_identity, args.diag_ws, args.ident_ws = g_I.data_ptr(), diag.data_ptr(), iws.data_ptr()
+            return g_I, (diag, iws, _fill_b16(nz, args))
+        g_h0, g_I, g_Ts = _backward(ctx, gout, 7, "recon_propagate_b16_bwd", "recon_propagate_b16_bwd (block mode)", fill)
+        return (g_h0, g_I, None, None, None, None, None) + g_Ts
 
 
 def propagate_blocks(T_list, identity, n, h0, nonlinearity, head_indices, tail_indices, return_states=False):
     """models/models.py:240-274 in one call: T_list = L transition tensors [B, n(n-1), (2d)^2] (or [B, n-1, n, (2d)^2]) AFTER their
     non-linearity, identity [2d, 2d]; equivalent to
         propagate([build_block_adjacency(T, identity, n) for T in T_list], h0, nonlinearity, head_indices, tail_indices)
-    and computed exactly like that wherever the fused kernels do not apply (2d != 16, n > 10, batches above one launch)."""
+    and computed exactly like that wherever the fused kernels do not apply (2d != 16, n > 32, shapes the library has no in-place form for, batches above one launch)."""
     if nonlinearity not in _lib.ACT:
         raise NotImplementedError(nonlinearity)
-    B, dd = T_list[0].shape[0], identity.shape[0]
+    B, dd, L = T_list[0].shape[0], identity.shape[0], len(T_list)
     need_grad = torch.is_grad_enabled() and (identity.requires_grad or h0.requires_grad or any(T.requires_grad for T in T_list))
     if _float_dtype(h0, identity, *T_list) == torch.bfloat16:
         # bfloat16: the kernels read the transition tensors in place (csrc/prop_b16.hip, block mode) — inference through the fused forms,
         # training through _PropagateBlocksB16 (no adjacency is materialised in either direction); other shapes: block adjacency + propagate
-        if not need_grad and _blocks_b16_available(B, n, dd, h0, T_list, identity):
+        if _blocks_b16_available(B, n, dd, h0, T_list, identity, need_grad):
+            if need_grad:
+                return _PropagateBlocksB16.apply(h0, identity, nonlinearity, head_indices, tail_indices, n, bool(return_states), *T_list)
             return _propagate_blocks_b16(T_list, identity, n, h0, nonlinearity, head_indices, tail_indices)
-        if need_grad and _blocks_b16_trainable(B, n, dd, h0, T_list, identity):
-            return _PropagateBlocksB16.apply(h0, identity, nonlinearity, head_indices, tail_indices, n, bool(return_states), *T_list)
         if return_states:
             raise NotImplementedError("return_states: the bfloat16 training form only")
         return propagate([build_block_adjacency(T, identity, n) for T in T_list], h0, nonlinearity, head_indices, tail_indices)
     if return_states:
         raise NotImplementedError("return_states: bfloat16 tensors only")
-    ok = blocks_mode_available(B, n, dd, h0, need_grad, L=len(T_list), T_list=T_list)
-    if not ok and need_grad and n > 10:
-        ok = (blocks_mode_available(B, n, dd, h0, False, L=len(T_list), T_list=T_list) and identity.data_ptr() % 16 == 0 and
-              _blocks_wide_trainable(B, n, dd, h0, len(T_list), head_indices, tail_indices))
+    ok = blocks_mode_available(B, n, dd, h0, need_grad, L=L, T_list=T_list)
+    if not ok and need_grad:                # no state-in-LDS backward: the wide-state forms, where the library has them for these shapes
+        ok = (blocks_mode_available(B, n, dd, h0, False, L=L, T_list=T_list) and identity.data_ptr() % 16 == 0 and
+              _blocks_wide_trainable(B, n, dd, h0, L, head_indices, tail_indices))
     if not ok:
         return propagate([build_block_adjacency(T, identity, n) for T in T_list], h0, nonlinearity, head_indices, tail_indices)
     return _PropagateBlocks.apply(h0, identity, nonlinearity, head_indices, tail_indices, n, *T_list)

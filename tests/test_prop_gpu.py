@@ -282,6 +282,35 @@ def test_propagate_blocks_many_hops_at_wide_states_falls_back():
     close(out, ref.float(), atol=1e-4, rel_to_max=1e-5, what="blocks n=32 L=8")
 
 
+def test_propagate_blocks_rejects_index_rows_for_part_of_the_batch():
+    """head / tail indices with more than one batch row but fewer than the batch has: the kernels would index them by graph and read past
+    their end for the later graphs.  propagate_blocks() raises what propagate() raises, in every block-mode form, before any launch."""
+    from recon_amd.propagation import (propagate_blocks, trace_instances, blocks_mode_available, _blocks_b16_available, make_start_embedding,
+                                       get_head_indices, get_tail_indices)
+    d_ = dev()
+    n, d, L, B, rows = 4, 8, 2, 5, 3
+    dd, C, S = 16, n * (n - 1), 16 * n
+    g = torch.Generator().manual_seed(3)
+    Ts = [torch.relu(torch.randn(B, C, dd * dd, generator=g)) * 0.1 for _ in range(L)]
+    h0 = torch.randn(B, C, S, 1, generator=g) * torch.from_numpy(make_start_embedding(n, d)).float()
+    head = torch.from_numpy(get_head_indices(n, d, bs=rows)).to(d_)
+    tail = torch.from_numpy(get_tail_indices(n, d, bs=rows)).to(d_)
+    assert head.shape == (rows, C, dd) and 1 < rows < B
+    for dtype, grad in ((torch.float32, False), (torch.float32, True), (torch.bfloat16, True)):
+        Tl = [t.to(device=d_, dtype=dtype).requires_grad_(grad) for t in Ts]
+        ident = torch.eye(dd, device=d_, dtype=dtype).requires_grad_(grad)
+        h = h0.to(device=d_, dtype=dtype).requires_grad_(grad)
+        # the call takes block mode: the route through build_block_adjacency + propagate() raises the same error after an untraced launch
+        if dtype == torch.float32:
+            assert blocks_mode_available(B, n, dd, h, need_grad=grad, L=L, T_list=Tl)
+        else:
+            assert _blocks_b16_available(B, n, dd, h, Tl, ident, grad)
+        with trace_instances() as trace, torch.set_grad_enabled(grad):
+            with pytest.raises(ValueError, match="head/tail indices hold %d batch rows but the batch has %d" % (rows, B)):
+                propagate_blocks(Tl, ident, n, h, "relu", head, tail)
+        assert trace == [], "%s, grad %s: launched %s before the check" % (dtype, grad, trace)
+
+
 def test_start_entity_embeddings_golden():
     from recon_amd.propagation import make_start_entity_embeddings
     g = load_golden("prop3_start_entity")
