@@ -928,6 +928,29 @@ int recon_kgsep_gat_loss_bwd(const int64_t* triples, int64_t n_pos, int32_t reps
                              float* g_Rel, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * E5  RECON's per-relation translation residuals (csrc/rel_trans.hip): models/models.py:939-958,
+ *         out[m][r] = sum_d | tanh(head_m . W_r)_d + rel[r][d] - tanh(tail_m . W_r)_d |,
+ *     head, tail [M][ent_dim] with row strides ld_head, ld_tail in elements (the two halves of one [M][2 ent_dim] tensor are read in place),
+ *     W [n_rel][ent_dim][rel_dim], rel [n_rel][rel_dim], out [M][n_rel], all fp32.  No [M][n_rel][rel_dim] tensor is written.
+ * ------------------------------------------------------------------------------------------*/
+/* Shapes the kernels take (models/models.py:939-958): 1 <= M <= 2^30, 1 <= n_rel <= 65535, 1 <= ent_dim <= 2^20, 1 <= rel_dim <= 256. */
+int recon_rel_translation_supported(int64_t M, int32_t n_rel, int32_t ent_dim, int32_t rel_dim);
+/* Bytes of the buffer the forward leaves for the backward (models/models.py:939-958): sgn of every difference as two bit planes, 2 words
+ * per (relation, pair, 32 columns), 1/16 of an fp32 intermediate at rel_dim % 32 == 0.  8-byte aligned, any contents. */
+size_t recon_rel_translation_saved_bytes(int64_t M, int32_t n_rel, int32_t rel_dim);
+/* Forward (models/models.py:939-958).  Both products of a (64-pair tile, relation) run in one workgroup on v_mfma_f32_32x32x2_f32 (exact
+ * fp32 fma chains, k ascending); tanh, + rel, -, |.| and the sum over rel_dim are the epilogue on the accumulators.  Every sum has one
+ * order and one lane writes each element: bitwise identical from run to run.  saved: recon_rel_translation_saved_bytes() bytes, or NULL
+ * when no backward follows.  Row strides above 2^22 elements: RECON_ERR_UNSUPPORTED.  M == 0: nothing is launched.  One launch. */
+int recon_rel_translation_fwd(const float* head, int64_t ld_head, const float* tail, int64_t ld_tail, const float* W, const float* rel, int64_t M,
+                              int32_t n_rel, int32_t ent_dim, int32_t rel_dim, float* out, void* saved, recon_stream_t stream);
+/* Backward for rel (models/models.py:939-958): g_rel[r][d] = sum_m g_out[m][r] sgn(diff[m][r][d]) with sgn(0) = 0, from the forward's
+ * `saved`; g_out [M][n_rel] contiguous.  Fixed order over m, no atomics: bitwise identical from run to run.  M == 0 writes zeros.
+ * One launch. */
+int recon_rel_translation_bwd(const float* g_out, const void* saved, int64_t M, int32_t n_rel, int32_t rel_dim, float* g_rel,
+                              recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
  *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
  * ------------------------------------------------------------------------------------------*/

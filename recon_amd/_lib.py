@@ -201,6 +201,11 @@ SYMBOLS = [
     ("recon_block_adjacency_b16_bwd", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p]),
     ("recon_rel_rows_mm", C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p] * 2),
     ("recon_rel_rows_mm_wgrad", C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p] * 2),
+    ("recon_rel_translation_supported", C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    ("recon_rel_translation_saved_bytes", C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    ("recon_rel_translation_fwd", C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_f32p,
+                                            C.c_void_p, C.c_void_p]),
+    ("recon_rel_translation_bwd", C.c_int, [c_f32p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, c_f32p, C.c_void_p]),
     ("recon_start_entity_embeddings", C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p,
                                                 C.c_void_p]),
     ("recon_start_entity_embeddings_bwd", C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_void_p, C.c_void_p]),

@@ -236,17 +236,14 @@ class RECON(RECON_EAC):
         self.W_ent2rel = nn.Parameter(W0, requires_grad=False)
 
     def translation_scores(self, nonzero_gat_entity_embeddings):
-        """[M, 2 ent_dim] (head | tail) -> [M, n_out] L1 translation residuals in each output relation's space (:934-953).
-        All relations at once: one [M, ent_dim] x [ent_dim, n_out * rel_dim] product per side on the library-free GEMM."""
-        from .gat_layers import small_mm
+        """[M, 2 ent_dim] (head | tail) -> [M, n_out] L1 translation residuals in each output relation's space (:934-953):
+        `translation_residuals` on the two halves, read in place (one fused launch; W_ent2rel is frozen, the gradient is
+        gat_relation_embeddings')."""
+        from .translation import translation_residuals
         W = self.W_ent2rel
-        n_out, ent_dim, rel_dim = W.shape
         half = nonzero_gat_entity_embeddings.shape[-1] // 2
         emb = nonzero_gat_entity_embeddings.to(device=W.device, dtype=W.dtype)
-        Wf = W.permute(1, 0, 2).reshape(ent_dim, n_out * rel_dim)
-        head = torch.tanh(small_mm(emb[:, :half].contiguous(), Wf)).view(-1, n_out, rel_dim)
-        tail = torch.tanh(small_mm(emb[:, half:].contiguous(), Wf)).view(-1, n_out, rel_dim)
-        return (head + self.gat_relation_embeddings.unsqueeze(0) - tail).abs().sum(-1)
+        return translation_residuals(emb[:, :half], emb[:, half:], W, self.gat_relation_embeddings)
 
     def forward(self, sentence_input, entity_markers, num_entities, unique_entites, entity_indices, context_words, context_chars,
                 context_mask, entities_position, max_occurred_entity_in_batch_pos, nonzero_gat_entity_embeddings, nonzero_entity_pos,
