@@ -3,23 +3,17 @@
 // Plain bf16 operands, fp32 accumulation on v_mfma_f32_16x16x32_bf16, bf16 (or fp32) results: what torch.mm does for bf16
 // tensors, i.e. what the reference's layer (models/layers.py:57-63) computes when its tensors are bfloat16.  With ONE MFMA per
 // 16x16x32 block these products are memory bound (x @ W at cfg 3a: 6.5 GFLOP = 2.6 us of matrix pipe against 40 MB of
-// traffic), so the kernels are the f16 x 2 kernels of gemm_hx2.hip with the second term and its products removed: same
-// 128 x 208 x 32 tiles, A fragments loaded straight from global memory, B through LDS-DMA into a double-buffered image.
+// traffic), so the kernels are the tile of gemm_tile16.h with T = 1 term plane: 128 x 208 x 32 tiles, A fragments loaded
+// straight from global memory, B through LDS-DMA into a double-buffered image.
 //
 //   k-contiguous form   C[M,N] = A[M,K] . Bp[N,Kp]^T      A rows 16-byte aligned (lda % 8 == 0), Bp zero padded to Kp = 32 k
 //   k-major form        C[M,N] = A[K,M]^T . B[K,N]        the weight gradient x^T g_support; split-K partials in fp32
 #include <stdlib.h>
-#include "gemm_common.h"
+#include "gemm_tile16.h"
 
 namespace recon {
 int32_t b16_kp(int32_t K);
 namespace {
-
-constexpr int BM = 128, BN = 208, BK = 32, NT = 256, TN = 13;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using i16x4 = __attribute__((ext_vector_type(4))) short;
 
 struct B16Args {
     const uint16_t* A; const uint16_t* Bp;
@@ -28,13 +22,12 @@ struct B16Args {
     int32_t M, N, K;
 };
 
-__device__ __forceinline__ int lds_off(int row, int kq) { return row * 64 + (((kq + 2 * (row >> 3)) & 3) << 4); }
 __device__ __forceinline__ uint16_t f2bf(float v) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(v)); }
 typedef __bf16 bf16x2_b __attribute__((ext_vector_type(2)));
 typedef float f32x2_b __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack_bf2(float a, float b) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_b{a, b}, bf16x2_b)); }   // one v_cvt_pk_bf16_f32
 
-constexpr int B_TILE_BYTES = BN * 64;                            // 13312
+constexpr int B_TILE_BYTES = B_PLANE;                           // 13312
 constexpr int B_PIECES = B_TILE_BYTES / 1024;                    // 13
 constexpr int B_DMA = (B_PIECES + 3) / 4;                        // 4
 
@@ -53,14 +46,7 @@ __global__ void __launch_bounds__(NT, 2) k_gemm_b16(const B16Args p) {
     for (int i = 0; i < 2; ++i) aptr[i] = p.A + static_cast<int64_t>(min(m0 + mb + 16 * i + li, p.M - 1)) * p.lda + 8 * lq;
     int b_goff[B_DMA];
 #pragma unroll
-    for (int i = 0; i < B_DMA; ++i) {
-        const int s = min(64 * (4 * i + wid) + lane, B_TILE_BYTES / 16 - 1);
-        const int rowL = s >> 2, pslot = s & 3;
-        const int kq = (pslot - 2 * (rowL >> 3)) & 3;                 // inverse of lds_off's rotation
-        const int j = rowL >> 4, rho = rowL & 15;
-        const int col = j < 12 ? 64 * (j >> 2) + 4 * rho + (j & 3) : 192 + rho;      // tile 4q+t <-> columns 64q + 4i + t
-        b_goff[i] = static_cast<int>(static_cast<int64_t>(min(n0 + col, p.N - 1)) * p.ldb + 8 * kq);
-    }
+    for (int i = 0; i < B_DMA; ++i) b_goff[i] = b_image_src<1>(64 * (4 * i + wid) + lane, n0, p.N, 0, p.ldb);
     auto dma_b = [&](int k0, int buf) {
 #pragma unroll
         for (int i = 0; i < B_DMA; ++i)
@@ -166,7 +152,7 @@ __global__ void __launch_bounds__(NT, 2) k_gemm_b16(const B16Args p) {
 }
 
 // ---- k-major form: partial[z][M][N] = A[ks..ke, :M]^T . B[ks..ke, :N]; both tiles by LDS-DMA into row-major images, fragments
-//      through the transposing read (layouts of gemm_hx2.hip / gemm_bx3.hip); rows past the K range come from a page of zeros
+//      through the transposing read (the k-major images of gemm_tile16.h); rows past the K range come from a page of zeros
 constexpr int kKmJobs = 8;                                           // products of one launch (the layers of a GraphConvolution stack)
 struct B16KmArgs {
     const uint16_t* A[kKmJobs]; const uint16_t* B[kKmJobs]; const uint16_t* zeros;
@@ -175,21 +161,13 @@ struct B16KmArgs {
     int32_t M[kKmJobs], N[kKmJobs], m_ld[kKmJobs], n_ld[kKmJobs];
     int32_t K, k_per_split, nsplit;                                    // shared: grid.z = jobs x nsplit
 };
-constexpr int KB_SLOTS = 28;
-constexpr int KA_BYTES = BK * 256, KB_BYTES = BK * KB_SLOTS * 16;                      // 8192, 14336
-constexpr int KA_PIECES = KA_BYTES / 1024, KB_PIECES = KB_BYTES / 1024;               // 8, 14
-__device__ __forceinline__ int ka_h(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base, int off_lo, int off_hi) {
-    const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(base + off_lo));
-    const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(base + off_hi));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
+constexpr int KA_PIECES = KA_PLANE / 1024, KB_PIECES = KB_PLANE / 1024;               // 8, 14
 
 // Three-stage ring of 22-KiB images, copies two K steps ahead, ONE counted wait + a raw barrier per step (round 5; the first form
 // double-buffered behind `vmcnt(0)` + __syncthreads and exposed one L2 -> LDS round trip in every step: 37 steps of a cfg 3a weight
 // gradient were 29 us for 416 cycles of MFMA per step).  The copies are issued as inline asm (dma16_to_lds): through the builtin the
 // compiler drains the request counter in front of the transposing reads.
-constexpr int KM_STAGES = 3, KM_STAGE_BYTES = KA_BYTES + KB_BYTES;
+constexpr int KM_STAGES = 3, KM_STAGE_BYTES = KA_PLANE + KB_PLANE;
 __global__ void __launch_bounds__(NT, 2) k_gemm_b16_kmajor(const B16KmArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char km_sm[];                  // [KM_STAGES][22 KiB]
     const int t = threadIdx.x, lane = t & 63;
@@ -229,7 +207,7 @@ __global__ void __launch_bounds__(NT, 2) k_gemm_b16_kmajor(const B16KmArgs p) {
                 const int pc = 4 * i + wid, k = k0 + d_k[i];
                 const bool isa = pc < KA_PIECES;
                 const uint16_t* q = k < k_end ? (isa ? pA + static_cast<int64_t>(k) * p_lda : pB + static_cast<int64_t>(k) * p_ldb) + d_col[i] : zlane;
-                unsigned char* dst = km_sm + buf * KM_STAGE_BYTES + (isa ? 1024 * pc : KA_BYTES + 1024 * (pc - KA_PIECES));
+                unsigned char* dst = km_sm + buf * KM_STAGE_BYTES + (isa ? 1024 * pc : KA_PLANE + 1024 * (pc - KA_PIECES));
                 dma16_to_lds(q, dst);
             }
     };
@@ -263,13 +241,13 @@ __global__ void __launch_bounds__(NT, 2) k_gemm_b16_kmajor(const B16KmArgs p) {
         asm volatile("" ::: "memory");
         if (k0 + 2 * BK < k_end) dma(k0 + 2 * BK, buf + 2 >= KM_STAGES ? buf + 2 - KM_STAGES : buf + 2);
         const unsigned char* As = km_sm + buf * KM_STAGE_BYTES;
-        const unsigned char* Bs = As + KA_BYTES;
+        const unsigned char* Bs = As + KA_PLANE;
         bf16x8 a[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) a[i] = tr_frag(As, a_off[i][0], a_off[i][1]);
+        for (int i = 0; i < 2; ++i) a[i] = tr_frag<bf16x8>(As, a_off[i][0], a_off[i][1]);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const bf16x8 b = tr_frag(Bs, b_off(j, 0), b_off(j, 1));
+            const bf16x8 b = tr_frag<bf16x8>(Bs, b_off(j, 0), b_off(j, 1));
 #pragma unroll
             for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b, acc[i][j], 0, 0, 0);
         }
@@ -438,7 +416,7 @@ __global__ void __launch_bounds__(1024) k_b16_reduce_multi(const B16ReduceMulti 
 
 }  // namespace
 
-int32_t b16_kp(int32_t K) { return (K + BK - 1) / BK * BK; }
+int32_t b16_kp(int32_t K) { return tile_kp(K); }
 
 int b16_pad_planes(const void* src, int64_t ld, bool transposed, int32_t rows, int32_t K, void* dst, hipStream_t st) {
     if (rows <= 0 || K <= 0) return RECON_OK;
@@ -523,10 +501,9 @@ int gemm_b16_kmajor_multi(int32_t count, const B16KmProduct* pr, int32_t K, cons
     }
     a.zeros = static_cast<const uint16_t*>(zeros); a.K = K;
     const int sk = count == 1 ? b16_kmajor_splits(Mx, Nx, K) : b16_kmajor_splits_multi(Mx, Nx, K, count);
-    int64_t kps = ceil_div64(K > 0 ? K : 1, sk);
-    kps = ceil_div64(kps, BK) * BK;
-    a.k_per_split = static_cast<int32_t>(kps);
-    a.nsplit = static_cast<int32_t>(ceil_div64(K > 0 ? K : 1, kps));
+    const SplitK sp = splitk_plan(K, sk);
+    a.k_per_split = sp.k_per_split;
+    a.nsplit = sp.nsplit;
     if (a.nsplit != sk || static_cast<int64_t>(sk) * count > 65535) return RECON_ERR_INVALID;
     const dim3 grid(static_cast<unsigned>(ceil_div64(Nx, BN)), static_cast<unsigned>(ceil_div64(Mx, BM)), static_cast<unsigned>(sk * count));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_b16_kmajor), hipFuncAttributeMaxDynamicSharedMemorySize, KM_STAGES * KM_STAGE_BYTES);

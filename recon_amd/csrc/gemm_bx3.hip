@@ -13,23 +13,13 @@
 //      to three column tiles, so a pre-split copy would cost more HBM traffic than it saves VALU work);
 //   B  PRE-SPLIT bf16 planes [3][N][Kp] (Kp = K rounded up to 32, zero padded) made once per step by
 //      k_split_planes: B is the small parameter matrix `a` that every row tile re-reads.
-// Block tile 128 x 208 x 32, 4 waves stacked along M, each 32 rows x 208 columns = 2 x 13 MFMA tiles (104
-// accumulators), two workgroups per CU.  LDS holds the three planes of both operands k-contiguous (64-byte rows,
-// the 16-byte slot of k group kq rotated by 2*(row>>3) so that the four lane groups of every ds_read_b128 and the
-// 8-lane groups of every ds_write_b128 hit disjoint banks).  B rows are permuted on the way into LDS (tile 4q+t
-// owns columns {64q + 4i + t}) so that the accumulators of four neighbouring tiles are four consecutive output
-// columns and the epilogue stores float4s.
+// Tile, LDS images (bank rotation, column permutation) and the loops over them: gemm_tile16.h, with T = 3 term planes.
 #include <stdlib.h>
 #include <hip/hip_bf16.h>
-#include "gemm_common.h"
+#include "gemm_tile16.h"
 
 namespace recon {
 namespace {
-
-constexpr int BM = 128, BN = 208, BK = 32, NT = 256, TN = 13;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 
 struct Bx3Args {
     OperandDesc A;                 // fp32, k-contiguous (Dseg >= K), rows through major_off
@@ -40,9 +30,6 @@ struct Bx3Args {
     int32_t epilogue, c_vec4, xcd_remap;
     int64_t a_bs, b_bs, c_bs;      // per-batch element offsets (b_bs in bf16 elements)
 };
-
-// byte offset of (row, k group kq of 8 bf16) inside one plane of an LDS tile
-__device__ __forceinline__ int lds_off(int row, int kq) { return row * 64 + (((kq + 2 * (row >> 3)) & 3) << 4); }
 
 // 8 fp32 -> three packed bf16x8 terms
 __device__ __forceinline__ void split8(const float (&v)[8], u32x4 (&out)[3]) {
@@ -63,83 +50,15 @@ __device__ __forceinline__ void split8(const float (&v)[8], u32x4 (&out)[3]) {
     }
 }
 
-// the six term products of one accumulator, issued for a GROUP of independent accumulators term by term: six
-// back-to-back MFMAs into the same accumulator would each wait for the previous result (dependent-issue latency
-// of the 4-pass MFMA), a group of 4 (2 row tiles x 2 column tiles) keeps 3 independent MFMAs between dependent ones
-template <int NJ>
-__device__ __forceinline__ void bx3_products(f32x4 (&acc)[2][TN], const bf16x8 (&a)[2][3], const bf16x8 (&b)[2][3], int j0) {
-    constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};      // small terms first
-#pragma unroll
-    for (int t = 0; t < 6; ++t)
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-                acc[i][j0 + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][TA[t]], b[jj][TB[t]], acc[i][j0 + jj], 0, 0, 0);
-}
-
-__device__ __forceinline__ void bx3_mma_reg(f32x4 (&acc)[2][TN], const bf16x8 (&a)[2][3], const unsigned char* Bs, int b_rd) {
-    // column tiles in pairs; the fragments of the next pair are read while the 24 MFMAs of this one run (two register
-    // sets pinned with sched_barrier: left alone the scheduler reads into one set and waits for every read)
-    bf16x8 b[2][2][3];
-    auto read_pair = [&](int j0, bf16x8 (&dst)[2][3]) {
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-            if (j0 + jj < TN) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q) dst[jj][q] = *reinterpret_cast<const bf16x8*>(Bs + q * (BN * 64) + b_rd + (j0 + jj) * 1024);
-            }
-    };
-    read_pair(0, b[0]);
-#pragma unroll
-    for (int g = 0; g < (TN + 1) / 2; ++g) {
-        if (2 * g + 2 < TN) read_pair(2 * g + 2, b[(g + 1) & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-        if (2 * g + 1 < TN) bx3_products<2>(acc, a, b[g & 1], 2 * g);
-        else bx3_products<1>(acc, a, b[g & 1], 2 * g);
-        __builtin_amdgcn_sched_barrier(0);
+// the six term pairs of weight >= 2^-16, small terms first (products<> / mma_pairs<> of gemm_tile16.h)
+struct Bx3Terms {
+    using V = bf16x8;
+    static constexpr int T = 3, NP = 6;
+    static __device__ __forceinline__ f32x4 mfma(int t, const V (&a)[3], const V (&b)[3], f32x4 c) {
+        constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[TA[t]], b[TB[t]], c, 0, 0, 0);
     }
-}
-
-// one K tile (32) of the wave's 32 x 208 block with both operands in LDS (k-major kernel): 6 + 39 ds_read_b128, 156 MFMAs
-__device__ __forceinline__ void bx3_mma(f32x4 (&acc)[2][TN], const unsigned char (*As)[BM * 64], const unsigned char (*Bs)[BN * 64],
-                                        const int (&a_rd)[2], int b_rd) {
-    bf16x8 a[2][3];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) a[i][q] = *reinterpret_cast<const bf16x8*>(&As[q][a_rd[i]]);
-    bx3_mma_reg(acc, a, &Bs[0][0], b_rd);
-}
-
-// MFMA C layout col = lane&15, row = (lane>>4)*4 + r; columns through the B row permutation (tile 4q+t <-> columns 64q+4i+t)
-__device__ __forceinline__ void bx3_store(const f32x4 (&acc)[2][TN], const OutputDesc& C, float* base, int M, int N, int m0, int n0,
-                                          int mb, int li, int lq, int epi, int c_vec4) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = m0 + mb + 16 * i + 4 * lq + r;
-            if (row >= M) continue;
-            float* crow = base + out_row_off(C, row);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const int col = n0 + 64 * q + 4 * li;
-                if (c_vec4) {
-                    if (col < N)
-                        *reinterpret_cast<float4*>(crow + minor_off(C.Dseg, C.Sseg, col)) =
-                            make_float4(gemm_epilogue(acc[i][4 * q][r], epi), gemm_epilogue(acc[i][4 * q + 1][r], epi),
-                                        gemm_epilogue(acc[i][4 * q + 2][r], epi), gemm_epilogue(acc[i][4 * q + 3][r], epi));
-                } else {
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj)
-                        if (col + jj < N) crow[minor_off(C.Dseg, C.Sseg, col + jj)] = gemm_epilogue(acc[i][4 * q + jj][r], epi);
-                }
-            }
-            const int col = n0 + 192 + li;
-            if (col < N) crow[minor_off(C.Dseg, C.Sseg, col)] = gemm_epilogue(acc[i][12][r], epi);
-        }
-}
+};
 
 // A never touches LDS: the rows of a wave's 32 x 208 block are private to that wave, so every lane loads its own MFMA
 // fragment (row lane&15, 8 consecutive k) straight from global memory, splits it in registers and keeps the three
@@ -148,7 +67,7 @@ __device__ __forceinline__ void bx3_store(const f32x4 (&acc)[2][TN], const Outpu
 // barrier and both operands of tile t+1 are in flight during the MFMAs of tile t.  The DMA writes lane-linear
 // (wave base + 16 B x lane), so the bank rotation of the image is applied on the SOURCE address: lane -> (plane, row,
 // physical slot) -> the k group that lives there.
-constexpr int B_TILE_BYTES = 3 * BN * 64;                        // 39936: one buffer of the B image
+constexpr int B_TILE_BYTES = 3 * B_PLANE;                        // 39936: one buffer of the B image
 constexpr int B_DMA = (B_TILE_BYTES / 16 + NT - 1) / NT;         // 10 DMA instructions per thread and tile
 
 __global__ void __launch_bounds__(NT, 2) k_gemm_bx3(const Bx3Args p) {
@@ -168,14 +87,7 @@ __global__ void __launch_bounds__(NT, 2) k_gemm_bx3(const Bx3Args p) {
     int b_goff[B_DMA];
     const __bf16* bbase = p.Bp + bz * p.b_bs;
 #pragma unroll
-    for (int i = 0; i < B_DMA; ++i) {
-        const int s = min(64 * (4 * i + wid) + lane, B_TILE_BYTES / 16 - 1);
-        const int plane = s / (BN * 4), rem = s % (BN * 4), rowL = rem >> 2, pslot = rem & 3;
-        const int kq = (pslot - 2 * (rowL >> 3)) & 3;                 // inverse of lds_off's rotation
-        const int j = rowL >> 4, rho = rowL & 15;
-        const int col = j < 12 ? 64 * (j >> 2) + 4 * rho + (j & 3) : 192 + rho;
-        b_goff[i] = static_cast<int>(plane * p.b_plane + static_cast<int64_t>(min(n0 + col, p.N - 1)) * p.b_row + 8 * kq);
-    }
+    for (int i = 0; i < B_DMA; ++i) b_goff[i] = b_image_src<3>(64 * (4 * i + wid) + lane, n0, p.N, p.b_plane, p.b_row);
     auto dma_b = [&](int k0, int buf) {
 #pragma unroll
         for (int i = 0; i < B_DMA; ++i)
@@ -236,25 +148,20 @@ __global__ void __launch_bounds__(NT, 2) k_gemm_bx3(const Bx3Args p) {
         if (k0 + BK < p.K) dma_b(k0 + BK, buf ^ 1);
         load_a(k0 + BK);                                              // unconditional (past K every lane re-reads its row start): no
         __builtin_amdgcn_sched_barrier(0);                            // control-flow join may sit between a load and its use, and
-        bx3_mma_reg(acc, af, Bs[buf], b_rd);                          // the first use (with its s_waitcnt) stays behind the MFMAs
+        mma_pairs<Bx3Terms>(acc, af, KcReader<bf16x8, 3>{Bs[buf], b_rd});          // the first use (with its s_waitcnt) stays behind the MFMAs
         __builtin_amdgcn_sched_barrier(0);
         split_a();
         __syncthreads();
         buf ^= 1;
     }
-    bx3_store(acc, p.C, p.C.base + bz * p.c_bs, p.M, p.N, m0, n0, mb, li, lq, p.epilogue, p.c_vec4);
+    store_permuted<false>(acc, p.C, p.C.base + bz * p.c_bs, p.M, p.N, m0, n0, mb, li, lq, p.epilogue, p.c_vec4, nullptr);
 }
 
 // The same product for k-MAJOR operands — the weight gradient g_a^T = V^T g_h, whose K is the node dimension:
 //   A  fp32 [K][M] (m contiguous), split on the fly;   B  pre-split bf16 planes [3][K][ldb] (n contiguous).
 // Both tiles are staged (A through registers, B by LDS-DMA) into ROW-MAJOR LDS images [k][m] / [k][n] as they lie in memory
 // (A: four float4 -> 3 x ds_write_b64 each; B: ten 16-byte copies), and the MFMA fragments — 8 consecutive k for one
-// m — come out of LDS through the transposing read ds_read_b64_tr_b16 (16 lanes read a [4 k][16 m] block, lane i
-// receives column i), two reads per fragment.  Bank layout: A rows are 256 B = 8 chunks of 32 B, chunk index XORed
-// with (k&3 | (k>>3&1)<<2); B rows are 28 slots of 16 B, shifted by 2 slots when k & 8 — in both images the
-// 8 rows one transposing read touches per 32 lanes land on disjoint bank groups (B: 28 slots per row — two of them
-// padding — rotated by 2 slots when k & 8: found conflict-free for every column tile by exhaustive check; the unpadded
-// 26-slot row with a wrapping rotation left 17 % of the LDS cycles as conflicts).
+// m — come out of LDS through the transposing read, two reads per fragment (the k-major images of gemm_tile16.h).
 // Split-K: every (batch, split) writes its tile to partial[z][M][N]; the caller reduces (and here transposes).
 struct Bx3KmArgs {
     const float* A; const __bf16* Bp;
@@ -263,19 +170,6 @@ struct Bx3KmArgs {
     int32_t M, N, K, k_per_split, nsplit;
     int32_t n_ld;                  // columns present in the planes (multiple of 8, >= N; the excess is zero padding)
 };
-
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using i16x4 = __attribute__((ext_vector_type(4))) short;
-constexpr int KB_SLOTS = 28;                                       // 16-byte slots per B image row: 26 of data + 2 of padding
-constexpr int KA_PLANE = BK * 256, KB_PLANE = BK * KB_SLOTS * 16;  // bytes per plane of the A / B image
-
-__device__ __forceinline__ int ka_h(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base, int off_lo, int off_hi) {
-    const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(base + off_lo));
-    const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(base + off_hi));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 __global__ void __launch_bounds__(NT, 2) k_gemm_bx3_kmajor(const Bx3KmArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char S[3 * KA_PLANE + 3 * KB_PLANE];      // A image | B image
@@ -386,19 +280,19 @@ __global__ void __launch_bounds__(NT, 2) k_gemm_bx3_kmajor(const Bx3KmArgs p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int q = 0; q < 3; ++q) a[i][q] = tr_frag(As + q * KA_PLANE, a_off[i][0], a_off[i][1]);
+            for (int q = 0; q < 3; ++q) a[i][q] = tr_frag<bf16x8>(As + q * KA_PLANE, a_off[i][0], a_off[i][1]);
         bf16x8 b[2][2][3];                                                // column tile j+1 is read while the 12 MFMAs of tile j run ([.][0] only)
         auto read_one = [&](int j, bf16x8 (&dst)[2][3]) {
             const int o0 = b_off(j, 0), o1 = b_off(j, 1);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) dst[0][q] = tr_frag(Bs + q * KB_PLANE, o0, o1);
+            for (int q = 0; q < 3; ++q) dst[0][q] = tr_frag<bf16x8>(Bs + q * KB_PLANE, o0, o1);
         };
         read_one(0, b[0]);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             if (j + 1 < TN) read_one(j + 1, b[(j + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
-            bx3_products<1>(acc, a, b[j & 1], j);
+            products<Bx3Terms, 1>(acc, a, b[j & 1], j);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -457,7 +351,7 @@ __global__ void __launch_bounds__(256) k_split_planes(const float* __restrict__ 
 
 }  // namespace
 
-int32_t bx3_kp(int32_t K) { return (K + BK - 1) / BK * BK; }
+int32_t bx3_kp(int32_t K) { return tile_kp(K); }
 
 int bx3_split_planes(const float* src, int64_t ld, int64_t src_bs, bool transposed, int32_t rows, int32_t K, int32_t batch, void* dst,
                      hipStream_t st) {
@@ -495,8 +389,7 @@ int gemm_bx3_batched(int32_t M, int32_t N, int32_t K, const OperandDesc& A, cons
     a.b_plane = a.b_bs * bt.batch;
     if (3 * a.b_plane >= (1LL << 31)) return RECON_ERR_UNSUPPORTED;    // 32-bit element offsets inside the planes
     a.a_bs = bt.a_bs; a.c_bs = bt.c_bs; a.epilogue = bt.epilogue;
-    a.c_vec4 = (!(N & 3) && !(bt.c_bs & 3) && !(reinterpret_cast<uintptr_t>(C.base) & 15) && !(C.S1 & 3) && !(C.S2 & 3) && !(C.Sseg & 3) &&
-                (C.Dseg >= N || !(C.Dseg & 3))) ? 1 : 0;
+    a.c_vec4 = c_vec4_ok(C, N, bt.c_bs) ? 1 : 0;
     a.xcd_remap = 1;
     const dim3 grid(static_cast<unsigned>(ceil_div64(N, BN)), static_cast<unsigned>(ceil_div64(M, BM)), static_cast<unsigned>(bt.batch));
     hipLaunchKernelGGL(k_gemm_bx3, grid, dim3(NT), 0, st, a);
@@ -548,10 +441,9 @@ int gemm_bx3_kmajor_batched(int32_t M, int32_t N, int32_t K, const float* A, int
     a.A = A; a.Bp = static_cast<const __bf16*>(Bplanes); a.lda = lda; a.ldb = ldb; a.b_plane = b_plane; a.a_bs = a_bs; a.b_bs = b_bs;
     a.partial = partial; a.M = M; a.N = N; a.K = K;
     a.n_ld = (N + 7) / 8 * 8;
-    int64_t kps = ceil_div64(K > 0 ? K : 1, split_k);
-    kps = ceil_div64(kps, BK) * BK;
-    a.k_per_split = static_cast<int32_t>(kps);
-    a.nsplit = static_cast<int32_t>(ceil_div64(K > 0 ? K : 1, kps));
+    const SplitK sp = splitk_plan(K, split_k);
+    a.k_per_split = sp.k_per_split;
+    a.nsplit = sp.nsplit;
     if (a.nsplit != split_k) return RECON_ERR_INVALID;                // callers size `partial` with the same rounding (bx3_kmajor_splits)
     if (static_cast<int64_t>(batch) * split_k > 65535) return RECON_ERR_UNSUPPORTED;
     const dim3 grid(static_cast<unsigned>(ceil_div64(N, BN)), static_cast<unsigned>(ceil_div64(M, BM)), static_cast<unsigned>(batch * split_k));
@@ -562,10 +454,7 @@ int gemm_bx3_kmajor_batched(int32_t M, int32_t N, int32_t K, const float* A, int
 
 // number of splits actually used for a requested split count (K tiles of 32 per split, rounded up)
 int bx3_kmajor_splits(int32_t K, int32_t split_k) {
-    if (split_k < 1) split_k = 1;
-    int64_t kps = ceil_div64(K > 0 ? K : 1, split_k);
-    kps = ceil_div64(kps, BK) * BK;
-    return static_cast<int>(ceil_div64(K > 0 ? K : 1, kps));
+    return splitk_plan(K, split_k < 1 ? 1 : split_k).nsplit;
 }
 
 }  // namespace recon

@@ -17,18 +17,14 @@
 // and the GEMM main loops then contain no conversion work at all — A fragments (k-contiguous form) are 16-byte global
 // loads straight into MFMA operand registers, everything else arrives by LDS-DMA.
 //
-// Tiling is the one of gemm_bx3.hip: block 128 x 208 x 32, 4 waves x (2 x 13) MFMA tiles, two workgroups per CU.
+// Tile, LDS images and the loops over them: gemm_tile16.h, with T = 2 term planes.
 #include <stdlib.h>
-#include "gemm_common.h"
+#include "gemm_tile16.h"
 
 namespace recon {
 namespace {
 
-constexpr int BM = 128, BN = 208, BK = 32, NT = 256, TN = 13, T = 2;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using i16x4 = __attribute__((ext_vector_type(4))) short;
+constexpr int T = 2;
 
 struct Hx2Args {
     const _Float16* Ap; const _Float16* Bp;
@@ -44,54 +40,17 @@ struct Hx2Args {
     int32_t a_span_bytes;          // k_gemm_hx2_r3: bytes from Ap to the end of the last fragment any lane reads (0: not below 2^31, the ring form is not used)
 };
 
-// byte offset of (row, k group kq of 8 halves) inside one plane of the B tile image (see gemm_bx3.hip)
-__device__ __forceinline__ int lds_off(int row, int kq) { return row * 64 + (((kq + 2 * (row >> 3)) & 3) << 4); }
+// the three term pairs of weight >= 2^-11, small terms first (products<> / mma_pairs<> of gemm_tile16.h)
+struct Hx2Terms {
+    using V = f16x8;
+    static constexpr int T = 2, NP = 3;
+    static __device__ __forceinline__ f32x4 mfma(int t, const V (&a)[2], const V (&b)[2], f32x4 c) {
+        constexpr int TA[3] = {0, 1, 0}, TB[3] = {1, 0, 0};
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a[TA[t]], b[TB[t]], c, 0, 0, 0);
+    }
+};
 
-// the three term products for a GROUP of independent accumulators, term by term (small terms first): NJ column tiles x 2
-// row tiles keep 2 NJ - 1 independent MFMAs between two that hit the same accumulator
-template <int NJ>
-__device__ __forceinline__ void hx2_products(f32x4 (&acc)[2][TN], const f16x8 (&a)[2][T], const f16x8 (&b)[2][T], int j0) {
-    constexpr int TA[3] = {0, 1, 0}, TB[3] = {1, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-                acc[i][j0 + jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][TA[t]], b[jj][TB[t]], acc[i][j0 + jj], 0, 0, 0);
-}
-
-// MFMA C layout col = lane&15, row = (lane>>4)*4 + r; columns through the B row permutation (tile 4q+t <-> columns 64q+4i+t)
-__device__ __forceinline__ void hx2_store(const f32x4 (&acc)[2][TN], const OutputDesc& C, float* base, int M, int N, int m0, int n0,
-                                          int mb, int li, int lq, int epi, int c_vec4, const float (&rsc)[2][4]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float scale = rsc[i][r];
-            auto fin = [&](float v) { return gemm_epilogue(v * scale, epi); };
-            const int row = m0 + mb + 16 * i + 4 * lq + r;
-            if (row >= M) continue;
-            float* crow = base + out_row_off(C, row);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const int col = n0 + 64 * q + 4 * li;
-                if (c_vec4) {
-                    if (col < N)
-                        *reinterpret_cast<float4*>(crow + minor_off(C.Dseg, C.Sseg, col)) =
-                            make_float4(fin(acc[i][4 * q][r]), fin(acc[i][4 * q + 1][r]), fin(acc[i][4 * q + 2][r]), fin(acc[i][4 * q + 3][r]));
-                } else {
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj)
-                        if (col + jj < N) crow[minor_off(C.Dseg, C.Sseg, col + jj)] = fin(acc[i][4 * q + jj][r]);
-                }
-            }
-            const int col = n0 + 192 + li;
-            if (col < N) crow[minor_off(C.Dseg, C.Sseg, col)] = fin(acc[i][12][r]);
-        }
-}
-
-// The same for the layer's own outputs — plain rows (no scatter, no segments), float4-aligned, the region below 2 GiB — without any
+// store_permuted for the layer's own outputs — plain rows (no scatter, no segments), float4-aligned, the region below 2 GiB — without any
 // branch: rows past M and columns past N become out-of-range buffer offsets.  The general form above decides scatter / segments / vector width / column bounds per
 // store, a few branches each; a wave spends several hundred cycles per store instruction in it.
 template <int EPI>
@@ -120,7 +79,7 @@ __device__ __forceinline__ void hx2_store_plain(const f32x4 (&acc)[2][TN], float
         }
 }
 
-constexpr int B_TILE_BYTES = T * BN * 64;                        // 26624: one buffer of the B image
+constexpr int B_TILE_BYTES = T * B_PLANE;                        // 26624: one buffer of the B image
 constexpr int B_PIECES = B_TILE_BYTES / 1024;                    // 26 pieces of 1 KiB (one LDS-DMA instruction of one wave each)
 
 // C = act(A . B^T / (s_a s_b)), both operands k-contiguous half planes.  A never touches LDS: the rows of a wave's
@@ -161,14 +120,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) k_gemm_hx2(const Hx2
     int b_goff[B_DMAW];
     const _Float16* bbase = p.Bp + bz * p.b_bs;
 #pragma unroll
-    for (int i = 0; i < B_DMAW; ++i) {
-        const int s = min(64 * (NW * i + wid) + lane, B_TILE_BYTES / 16 - 1);
-        const int plane = s / (BN * 4), rem = s % (BN * 4), rowL = rem >> 2, pslot = rem & 3;
-        const int kq = (pslot - 2 * (rowL >> 3)) & 3;                 // inverse of lds_off's rotation
-        const int j = rowL >> 4, rho = rowL & 15;
-        const int col = j < 12 ? 64 * (j >> 2) + 4 * rho + (j & 3) : 192 + rho;
-        b_goff[i] = static_cast<int>(plane * p.b_plane + static_cast<int64_t>(min(n0 + col, p.N - 1)) * p.b_row + 8 * kq);
-    }
+    for (int i = 0; i < B_DMAW; ++i) b_goff[i] = b_image_src<T>(64 * (NW * i + wid) + lane, n0, p.N, p.b_plane, p.b_row);
     auto dma_b = [&](int k0, int buf) {
 #pragma unroll
         for (int i = 0; i < B_DMAW; ++i)
@@ -210,27 +162,6 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) k_gemm_hx2(const Hx2
     };
     const int b_rd = lds_off(li, lq);
 
-    auto mma = [&](const unsigned char* Bt) {
-        f16x8 b[2][2][T];
-        auto read_pair = [&](int j0, f16x8 (&dst)[2][T]) {
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                if (j0 + jj < TN) {
-#pragma unroll
-                    for (int q = 0; q < T; ++q) dst[jj][q] = *reinterpret_cast<const f16x8*>(Bt + q * (BN * 64) + b_rd + (j0 + jj) * 1024);
-                }
-        };
-        read_pair(0, b[0]);
-#pragma unroll
-        for (int g = 0; g < (TN + 1) / 2; ++g) {
-            if (2 * g + 2 < TN) read_pair(2 * g + 2, b[(g + 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (2 * g + 1 < TN) hx2_products<2>(acc, af, b[g & 1], 2 * g);
-            else hx2_products<1>(acc, af, b[g & 1], 2 * g);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-
     dma_b(0, 0);
     load_a(0);
     // the operands' scales (32 amax slots each): read here, under the first tile's round trip, not in front of the stores
@@ -243,7 +174,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) k_gemm_hx2(const Hx2
         if (k0 + BK < p.K) dma_b(k0 + BK, buf ^ 1);
         load_a(k0 + BK);
         __builtin_amdgcn_sched_barrier(0);
-        mma(Bs[buf]);
+        mma_pairs<Hx2Terms>(acc, af, KcReader<f16x8, T>{Bs[buf], b_rd});
         __builtin_amdgcn_sched_barrier(0);
         take_a();
         __syncthreads();
@@ -261,7 +192,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) k_gemm_hx2(const Hx2
         if (p.epilogue == GEMM_EPI_ELU) hx2_store_plain<GEMM_EPI_ELU>(acc, p.C.base + bz * p.c_bs, p.C.S1, p.M, p.N, m0, n0, mb, li, lq, rsc);
         else hx2_store_plain<GEMM_EPI_NONE>(acc, p.C.base + bz * p.c_bs, p.C.S1, p.M, p.N, m0, n0, mb, li, lq, rsc);
     } else {
-        hx2_store(acc, p.C, p.C.base + bz * p.c_bs, p.M, p.N, m0, n0, mb, li, lq, p.epilogue, p.c_vec4, rsc);
+        store_permuted<true>(acc, p.C, p.C.base + bz * p.c_bs, p.M, p.N, m0, n0, mb, li, lq, p.epilogue, p.c_vec4, rsc);
     }
 }
 
@@ -310,18 +241,11 @@ __global__ void __launch_bounds__(64 * NW, 2) k_gemm_hx2_r3(const Hx2Args p) {
 #pragma unroll
             for (int q = 0; q < T; ++q) dst[i][q] = __builtin_amdgcn_raw_buffer_load_b128(rsA, a_off[i][q] + ko, 0, 0);
     };
-    // ---- B: the copy plan of gemm_hx2 (piece pc = NW i + wave of the tile image), missing pieces go to the scratch KiB
+    // ---- B: the copy plan of k_gemm_hx2 (piece pc = NW i + wave of the tile image), missing pieces go to the scratch KiB
     int b_goff[B_DMAW];
     const _Float16* bbase = p.Bp + bz * p.b_bs;
 #pragma unroll
-    for (int i = 0; i < B_DMAW; ++i) {
-        const int s = min(64 * (NW * i + wid) + lane, B_TILE_BYTES / 16 - 1);
-        const int plane = s / (BN * 4), rem = s % (BN * 4), rowL = rem >> 2, pslot = rem & 3;
-        const int kq = (pslot - 2 * (rowL >> 3)) & 3;                 // inverse of lds_off's rotation
-        const int j = rowL >> 4, rho = rowL & 15;
-        const int col = j < 12 ? 64 * (j >> 2) + 4 * rho + (j & 3) : 192 + rho;
-        b_goff[i] = static_cast<int>(plane * p.b_plane + static_cast<int64_t>(min(n0 + col, p.N - 1)) * p.b_row + 8 * kq);
-    }
+    for (int i = 0; i < B_DMAW; ++i) b_goff[i] = b_image_src<T>(64 * (NW * i + wid) + lane, n0, p.N, p.b_plane, p.b_row);
     auto dma_b = [&](int kt, int buf) {                              // kt past the end: the last tile again, into scratch
         const bool real = kt < KT;
         const int k0 = min(kt, KT - 1) * BK;
@@ -356,7 +280,7 @@ __global__ void __launch_bounds__(64 * NW, 2) k_gemm_hx2_r3(const Hx2Args p) {
             for (int jj = 0; jj < 2; ++jj)
                 if (j0 + jj < TN) {
 #pragma unroll
-                    for (int q = 0; q < T; ++q) dst[jj][q] = *reinterpret_cast<const f16x8*>(Bt + q * (BN * 64) + b_rd + (j0 + jj) * 1024);
+                    for (int q = 0; q < T; ++q) dst[jj][q] = *reinterpret_cast<const f16x8*>(Bt + q * B_PLANE + b_rd + (j0 + jj) * 1024);
                 }
         };
         read_pair(0, b[0]);
@@ -364,8 +288,8 @@ __global__ void __launch_bounds__(64 * NW, 2) k_gemm_hx2_r3(const Hx2Args p) {
         for (int g = 0; g < (TN + 1) / 2; ++g) {
             if (2 * g + 2 < TN) read_pair(2 * g + 2, b[(g + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
-            if (2 * g + 1 < TN) hx2_products<2>(acc, af, b[g & 1], 2 * g);
-            else hx2_products<1>(acc, af, b[g & 1], 2 * g);
+            if (2 * g + 1 < TN) products<Hx2Terms, 2>(acc, af, b[g & 1], 2 * g);
+            else products<Hx2Terms, 1>(acc, af, b[g & 1], 2 * g);
             __builtin_amdgcn_sched_barrier(0);
             if (g == 0) {                                             // behind the first group: the tile's requests (B first: it is needed first)
                 dma_b(kt + 1, (kt + 1) & 1);
@@ -401,17 +325,16 @@ __global__ void __launch_bounds__(64 * NW, 2) k_gemm_hx2_r3(const Hx2Args p) {
         if (p.epilogue == GEMM_EPI_ELU) hx2_store_plain<GEMM_EPI_ELU>(acc, p.C.base + bz * p.c_bs, p.C.S1, p.M, p.N, m0, n0, mb, li, lq, rsc);
         else hx2_store_plain<GEMM_EPI_NONE>(acc, p.C.base + bz * p.c_bs, p.C.S1, p.M, p.N, m0, n0, mb, li, lq, rsc);
     } else {
-        hx2_store(acc, p.C, p.C.base + bz * p.c_bs, p.M, p.N, m0, n0, mb, li, lq, p.epilogue, p.c_vec4, rsc);
+        store_permuted<true>(acc, p.C, p.C.base + bz * p.c_bs, p.M, p.N, m0, n0, mb, li, lq, p.epilogue, p.c_vec4, rsc);
     }
 }
 
 // The same product for k-MAJOR operands — the weight gradient g_a^T = V^T g_h, whose K is the node dimension:
 //   A half planes [2][K][lda] (m contiguous),  B half planes [2][K][ldb] (n contiguous).
 // Both tiles arrive by LDS-DMA in ROW-MAJOR images [k][m] / [k][n] as they lie in memory and the MFMA fragments — 8
-// consecutive k for one m — come out of LDS through the transposing read ds_read_b64_tr_b16 (two per fragment).  Bank
-// layout as in gemm_bx3.hip: A rows are 256 B = 8 chunks of 32 B, chunk index XORed with (k&3 | (k>>3&1)<<2); B rows
-// are 28 slots of 16 B (26 of data), rotated by 2 slots when k & 8; both rotations are applied on the DMA's SOURCE
-// address.  Rows past the split's K range are read from a page of zeros (there is no register stage to mask them in).
+// consecutive k for one m — come out of LDS through the transposing read (the k-major images of gemm_tile16.h); both
+// rotations are applied on the DMA's SOURCE address.  Rows past the split's K range are read from a page of zeros
+// (there is no register stage to mask them in).
 // Split-K: every (batch, split) writes its scaled-back tile to partial[z][M][N]; the caller reduces (and transposes).
 struct Hx2KmArgs {
     const _Float16* Ap; const _Float16* Bp; const _Float16* zeros;    // zeros: >= 1 KiB of zero bytes, 16-byte aligned
@@ -424,18 +347,8 @@ struct Hx2KmArgs {
     const float* k_inv; int64_t k_inv_bs;          // per-k inverse scales of B's rows (see gemm_hx2_kmajor_batched) or null
 };
 
-constexpr int KB_SLOTS = 28;
-constexpr int KA_PLANE = BK * 256, KB_PLANE = BK * KB_SLOTS * 16;
 constexpr int KA_PIECES = T * (KA_PLANE / 1024), KA_DMA = KA_PIECES / 4;               // 16, 4
 constexpr int KB_PIECES = T * (KB_PLANE / 1024), KB_DMA = (KB_PIECES + 3) / 4;         // 28, 7
-
-__device__ __forceinline__ int ka_h(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-
-__device__ __forceinline__ f16x8 tr_frag(const unsigned char* base, int off_lo, int off_hi) {
-    const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(base + off_lo));
-    const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(base + off_hi));
-    return __builtin_bit_cast(f16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 template <int OCC, bool KSC>
 __global__ void __launch_bounds__(NT, OCC) k_gemm_hx2_kmajor(const Hx2KmArgs p) {
@@ -529,7 +442,7 @@ __global__ void __launch_bounds__(NT, OCC) k_gemm_hx2_kmajor(const Hx2KmArgs p) 
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int q = 0; q < T; ++q) a[i][q] = tr_frag(As + q * KA_PLANE, a_off[i][0], a_off[i][1]);
+            for (int q = 0; q < T; ++q) a[i][q] = tr_frag<f16x8>(As + q * KA_PLANE, a_off[i][0], a_off[i][1]);
         if constexpr (KSC) {
             const float f[8] = {kin[0].x, kin[0].y, kin[0].z, kin[0].w, kin[1].x, kin[1].y, kin[1].z, kin[1].w};
             f16x8 kf;
@@ -540,25 +453,11 @@ __global__ void __launch_bounds__(NT, OCC) k_gemm_hx2_kmajor(const Hx2KmArgs p) 
 #pragma unroll
                 for (int q = 0; q < T; ++q) a[i][q] = a[i][q] * kf;
         }
-        f16x8 b[2][2][T];
-        auto read_pair = [&](int j0, f16x8 (&dst)[2][T]) {
+        mma_pairs<Hx2Terms>(acc, a, [&](int j, f16x8 (&dst)[T]) {
+            const int o0 = b_off(j, 0), o1 = b_off(j, 1);
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                if (j0 + jj < TN) {
-                    const int o0 = b_off(j0 + jj, 0), o1 = b_off(j0 + jj, 1);
-#pragma unroll
-                    for (int q = 0; q < T; ++q) dst[jj][q] = tr_frag(Bs + q * KB_PLANE, o0, o1);
-                }
-        };
-        read_pair(0, b[0]);
-#pragma unroll
-        for (int gp = 0; gp < (TN + 1) / 2; ++gp) {
-            if (2 * gp + 2 < TN) read_pair(2 * gp + 2, b[(gp + 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (2 * gp + 1 < TN) hx2_products<2>(acc, a, b[gp & 1], 2 * gp);
-            else hx2_products<1>(acc, a, b[gp & 1], 2 * gp);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+            for (int q = 0; q < T; ++q) dst[q] = tr_frag<f16x8>(Bs + q * KB_PLANE, o0, o1);
+        });
     };
 
     // ONE buffer per operand: the DMA of tile t+1 starts once every wave is done with tile t; the co-resident workgroups'
@@ -664,7 +563,7 @@ __global__ void __launch_bounds__(NTHREADS) k_hx2_amax(const float* __restrict__
 
 }  // namespace
 
-int32_t hx2_kp(int32_t K) { return (K + BK - 1) / BK * BK; }
+int32_t hx2_kp(int32_t K) { return tile_kp(K); }
 
 int hx2_amax(const float* src, int64_t rows, int32_t cols, int64_t ld, uint32_t* slot, hipStream_t st) {
     if (rows <= 0 || cols <= 0) return RECON_OK;
@@ -737,8 +636,7 @@ int gemm_hx2_batched(int32_t M, int32_t N, int32_t K, const void* Ap, int64_t a_
     a.b_plane = a.b_bs * bt.batch;
     if (T * a.b_plane >= (1LL << 31)) return RECON_ERR_UNSUPPORTED;    // 32-bit element offsets inside the B planes
     a.C = C; a.c_bs = bt.c_bs; a.M = M; a.N = N; a.K = K; a.epilogue = bt.epilogue;
-    a.c_vec4 = (!(N & 3) && !(bt.c_bs & 3) && !(reinterpret_cast<uintptr_t>(C.base) & 15) && !(C.S1 & 3) && !(C.S2 & 3) && !(C.Sseg & 3) &&
-                (C.Dseg >= N || !(C.Dseg & 3))) ? 1 : 0;
+    a.c_vec4 = c_vec4_ok(C, N, bt.c_bs) ? 1 : 0;
     a.xcd_remap = 1;
     if (a_shared_k < 0 || (a_shared_k & 7) || (a_shared_k && a_bs * bt.batch >= (1LL << 31))) return RECON_ERR_INVALID;
     a.a_shared_k = a_shared_k;
@@ -783,10 +681,9 @@ int gemm_hx2_kmajor_batched(int32_t M, int32_t N, int32_t K, const void* Ap, int
     a.lda = lda; a.ldb = ldb; a.a_plane = a_plane; a.b_plane = b_plane; a.a_bs = a_bs; a.b_bs = b_bs;
     a.partial = partial; a.M = M; a.N = N; a.K = K;
     a.m_ld = (M + 7) / 8 * 8; a.n_ld = (N + 7) / 8 * 8;
-    int64_t kps = ceil_div64(K > 0 ? K : 1, split_k);
-    kps = ceil_div64(kps, BK) * BK;
-    a.k_per_split = static_cast<int32_t>(kps);
-    a.nsplit = static_cast<int32_t>(ceil_div64(K > 0 ? K : 1, kps));
+    const SplitK sp = splitk_plan(K, split_k);
+    a.k_per_split = sp.k_per_split;
+    a.nsplit = sp.nsplit;
     if (a.nsplit != split_k) return RECON_ERR_INVALID;
     if (static_cast<int64_t>(batch) * split_k > 65535) return RECON_ERR_UNSUPPORTED;
     a.sa = sa; a.sb = sb;

@@ -205,13 +205,20 @@ def _hx2_ws(nbytes):
     return ws, ws.data_ptr() + off
 
 
-@pytest.mark.parametrize("scale", [1.0, 1e-6, 3e4])
-@pytest.mark.parametrize("M,N,K", [(128, 208, 32), (200, 72, 56), (33, 257, 24), (700, 200, 600), (513, 600, 200),
-                                   (300, 204, 40), (1000, 25, 8), (4100, 3300, 1032)])     # the last: the 256-row workgroup form (K >= 1024, >= 256 tiles)
-def test_sgemm_hx2(M, N, K, scale):
+_HX2_SHAPES = [(128, 208, 32), (200, 72, 56), (33, 257, 24), (700, 200, 600), (513, 600, 200),
+               (300, 204, 40), (1000, 25, 8), (4100, 3300, 1032)]     # the last: the 256-row workgroup form (K >= 1024, >= 256 tiles)
+
+
+# RECON_HX2_RING: "1" the three-deep A ring (k_gemm_hx2_r3, the default), "0" the two-stage form (k_gemm_hx2<4>) at the three
+# smallest shapes: one tile and one K step; row tail + a second column tile of one column + K tail; two K steps with a tail
+@pytest.mark.parametrize("M,N,K,scale,ring",
+                         [pytest.param(M, N, K, scale, "1", id="%d-%d-%d-%s" % (M, N, K, scale)) for scale in (1.0, 1e-6, 3e4) for M, N, K in _HX2_SHAPES] +
+                         [pytest.param(M, N, K, 1.0, "0", id="%d-%d-%d-1.0-ring0" % (M, N, K)) for M, N, K in _HX2_SHAPES[:3]])
+def test_sgemm_hx2(M, N, K, scale, ring, recon_config):
     """Split-precision (2 x f16, per-tensor power-of-two scale) MFMA GEMM: fp32-class accuracy against an fp64 product, at
     magnitudes far outside half's own range."""
     from recon_amd import _lib
+    recon_config("RECON_HX2_RING", ring)
     g = torch.Generator().manual_seed(M + N + K)
     A = torch.randn(M, K, generator=g) * torch.exp(2.0 * torch.randn(M, 1, generator=g)) * scale     # rows of very different scale
     B = torch.randn(N, K, generator=g) / scale
