@@ -684,10 +684,12 @@ int recon_gcn_b16_transposed_planes(const void* weight, int32_t in_features, int
 int recon_sgemm(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, const float* B, int32_t ldb,
                 int32_t b_is_nk, float* C, int32_t ldc, recon_stream_t stream);
 
-/* The same kernels with either operand in either orientation — A is [M,K] (a_is_km == 0) or [K,M]; B is [K,N] (b_is_nk == 0) or [N,K] —
+/* The same kernels with the operands in three of the four orientations — A is [M,K] (a_is_km == 0) or [K,M]; B is [K,N] (b_is_nk == 0)
+ * or [N,K]; A [K,M] together with B [N,K] has no kernel and answers RECON_ERR_UNSUPPORTED (nothing is written) —
  * and split-K (fixed-order second pass) when `workspace` (recon_sgemm_ex_workspace_floats() floats, may be 0) is given: what the
  * models' dense products outside the attention layer run on (`entity_embeddings.mm(self.W_entities)`, GAT/models.py:177, and the
- * gradients of it), in place of the library GEMM behind torch.mm. */
+ * gradients of it), in place of the library GEMM behind torch.mm.  Any lda / ldb / ldc and any base alignment: 16-byte loads and
+ * stores are used where every stride, base and contiguous extent allows them, single floats otherwise. */
 size_t recon_sgemm_ex_workspace_floats(int32_t M, int32_t N, int32_t K);
 int recon_sgemm_ex(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, int32_t a_is_km, const float* B, int32_t ldb,
                    int32_t b_is_nk, float* C, int32_t ldc, float* workspace, recon_stream_t stream);
@@ -697,7 +699,9 @@ int recon_sgemm_ex(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda,
  * Replaces `relation_embed.mm(self.W)` (GAT/models.py:75) and its two gradient products, which are launch / latency bound on tile GEMMs. */
 size_t recon_sgemm_small_workspace_floats(int32_t M, int32_t N, int32_t K);  /* 0: no workspace needed */
 /* workspace: recon_sgemm_small_workspace_floats() floats, or NULL.  With it, products with few output tiles and a long K (weight
- * gradients: 50 x 200 over K = 14 541 rows) also cut K over workgroups and add the parts in fixed order. */
+ * gradients: 50 x 200 over K = 14 541 rows) also cut K over workgroups and add the parts in fixed order.  A leading dimension below
+ * its operand's row length (lda < K resp. M, ldb < N resp. K, ldc < N): RECON_ERR_INVALID.  M == 0 or N == 0: RECON_OK, nothing is
+ * launched.  K == 0: C's M x N elements are set to zero. */
 int recon_sgemm_small(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, int32_t a_is_km, const float* B, int32_t ldb,
                       int32_t b_is_nk, float* C, int32_t ldc, float* workspace, recon_stream_t stream);
 
@@ -721,7 +725,8 @@ int recon_sgemm_bx3_tn(int32_t M, int32_t N, int32_t K, const float* A, int32_t 
  * half's 5 exponent bits suffice, and pre-split into two half planes; fp32-class accuracy at half the MFMA work of
  * the bf16 x 3 form.  These stand-alone entries measure (amax) and split both operands into `workspace` (256-byte
  * aligned) first; the *_presplit forms re-run only the GEMM on the planes a previous call left there (benchmarks).
- * Requires K % 8 == 0 (k-contiguous form); any M, N for the k-major form.  In the GAT layer the planes are written by
+ * Requires K % 8 == 0 (k-contiguous form; RECON_ERR_UNSUPPORTED otherwise); any M, N for the k-major form.  A workspace that is not
+ * 256-byte aligned is an argument error (RECON_ERR_INVALID), like a null one.  In the GAT layer the planes are written by
  * the kernels that produce the operands (edge aggregation: V; ELU-gradient pass: g_h). */
 size_t recon_hx2_aux_bytes(void);      /* size of recon_gat_atp_args.aux */
 size_t recon_sgemm_hx2_workspace_bytes(int32_t M, int32_t N, int32_t K);
