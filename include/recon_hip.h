@@ -997,6 +997,44 @@ int recon_convkb_train_bwd(const void* triples, int32_t index_bytes, int64_t M, 
                            int32_t D, const float* w2, float slope, const float* z, const float* g_scores, const float* g_scale, float* dW1,
                            float* db1, float* dw2, float* db2, float* workspace, size_t workspace_floats, recon_stream_t stream);
 
+/* --------------------------------------------------------------------------------------------
+ * E6  Parameter updates (csrc/optim.hip): the optimizer steps of the three training programs as multi-tensor launches.
+ *     A step is a list of n_segments segments: host arrays of DEVICE pointers (parameter, gradient, state), one entry per segment, and a
+ *     host array numel of element counts.  Everything is fp32 and contiguous; a pointer needs 4-byte alignment only (segments whose
+ *     pointers are all 16-byte aligned move 16 bytes per lane, the others 4); the buffers of a segment must not overlap.  The segment
+ *     descriptors travel in the kernel arguments: the host arrays are read during the call and may be reused as soon as it returns, and
+ *     no device table exists.  One launch takes recon_optim_max_segments() segments (and a segment above 2^30 elements counts as one per
+ *     2^30); longer lists are spread over several launches.  Each workgroup owns one run of recon_optim_chunk_elems() elements.
+ *     Every entry point: RECON_ERR_INVALID for n_segments < 0, a negative count, or a NULL array or NULL segment pointer where there are
+ *     elements; RECON_OK with nothing launched and nothing written for n_segments == 0 or all counts 0.
+ * ------------------------------------------------------------------------------------------*/
+int32_t recon_optim_max_segments(void);
+int32_t recon_optim_chunk_elems(void);
+/* Bytes of recon_optim_grad_sumsq's workspace for a step of n_segments gradients with total_elems elements in all: 16 bytes of results
+ * and one 8-byte word per workgroup.  16-byte aligned, ZERO-FILLED before its first use (the arrival counter; every call leaves it at 0). */
+size_t recon_optim_workspace_bytes(int64_t total_elems, int32_t n_segments);
+/* clip_grad_norm(parameters, max_norm) without the scaling pass (train.py:314-315; torch.nn.utils.clip_grad_norm_, norm_type 2):
+ * workspace float [0] = total_norm = sqrt(sum over every element of every gradient of g^2), float [1] = the scale
+ * min(1, max_norm / (total_norm + 1e-6)) that recon_optim_sgd / recon_optim_adam take as clip_scale.  The gradients are not modified.
+ * Squares and sums in fp64; every workgroup leaves its sum in its own word, the one that arrives last adds all words in index order:
+ * bitwise identical from run to run.  A non-finite gradient gives a non-finite norm and scale (error_if_nonfinite=False).  The host
+ * never waits: both values stay on the device.  One launch per recon_optim_max_segments() segments. */
+int recon_optim_grad_sumsq(const void* const* grads, const int64_t* numel, int32_t n_segments, float max_norm, void* workspace,
+                           size_t workspace_bytes, recon_stream_t stream);
+/* torch.optim.SGD(lr, weight_decay).step() (GAT/main.py:445-449; no momentum): g' = s g + weight_decay p, p <- p - lr g', with s = *clip_scale
+ * (device; NULL: 1).  One launch per recon_optim_max_segments() segments. */
+int recon_optim_sgd(void* const* params, const void* const* grads, const int64_t* numel, int32_t n_segments, double lr, double weight_decay,
+                    const float* clip_scale, recon_stream_t stream);
+/* torch.optim.Adam(lr, betas, eps, weight_decay).step() (GAT/main.py:747-751, train.py:234; L2 decay folded into the gradient, not AdamW,
+ * no amsgrad): g' = s g + weight_decay p, m <- beta1 m + (1 - beta1) g', v <- beta2 v + (1 - beta2) g'^2,
+ * p <- p - (lr / bias_correction1) m / (sqrt(v) / sqrt(bias_correction2) + eps), with bias_correction_i = 1 - beta_i^t for the step count t
+ * AFTER this step, computed by the caller in double precision (both > 0, else RECON_ERR_INVALID), and s = *clip_scale (device; NULL: 1).
+ * Evaluated in fp32 in the operation order of torch's single-tensor implementation (m by lerp: m + (1 - beta1) (g' - m)), rounding for
+ * rounding.  Every segment of a call shares t.  One launch per recon_optim_max_segments() segments. */
+int recon_optim_adam(void* const* params, const void* const* grads, void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel,
+                     int32_t n_segments, double lr, double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
+                     double bias_correction2, const float* clip_scale, recon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

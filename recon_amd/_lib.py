@@ -289,6 +289,12 @@ SYMBOLS = [
     ("recon_sgemm_hx2_tn", C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
     ("recon_sgemm_hx2_tn_presplit", C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("recon_optim_max_segments", C.c_int32, []),
+    ("recon_optim_chunk_elems", C.c_int32, []),
+    ("recon_optim_workspace_bytes", C.c_size_t, [C.c_int64, C.c_int32]),
+    ("recon_optim_grad_sumsq", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("recon_optim_sgd", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, c_f32p, C.c_void_p]),
+    ("recon_optim_adam", C.c_int, [C.c_void_p] * 5 + [C.c_int32] + [C.c_double] * 7 + [c_f32p, C.c_void_p]),
 ]
 
 _lib = None

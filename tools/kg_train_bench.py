@@ -11,7 +11,7 @@ valid_invalid_ratio_conv 40: 5 184 rows per iteration; synthetic tables), four l
 Each sample times --iters back-to-back iterations between two device events (no sync inside, as in a training loop without .item());
 the median over --repeats samples is reported per iteration, and an epoch (4 252 iterations) is extrapolated.  Prints one JSON line.
 
-    python tools/kg_train_bench.py [--repeats 7] [--iters 20]
+    python tools/kg_train_bench.py [--repeats 7] [--iters 20] [--optimizer {torch,recon}]
 """
 import argparse
 import json
@@ -84,6 +84,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--host-iters", type=int, default=2)
+    ap.add_argument("--optimizer", choices=["torch", "recon"], default="torch", help="leg (d)'s Adam: torch.optim.Adam or recon_amd.optim.Adam (one launch)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
@@ -107,7 +108,11 @@ def main():
         m.final_entity_embeddings.requires_grad_(False)
         m.final_relation_embeddings.requires_grad_(False)
         models.append(m)
-        opts.append(torch.optim.Adam(m.parameters(), lr=1e-3, weight_decay=1e-5))
+        if a.optimizer == "recon" and len(opts) == 1:                       # models[1] / opts[1] are leg (d)'s
+            from recon_amd.optim import Adam
+            opts.append(Adam(m.parameters(), lr=1e-3, weight_decay=1e-5))
+        else:
+            opts.append(torch.optim.Adam(m.parameters(), lr=1e-3, weight_decay=1e-5))
     batch = kg_train.iteration_batch(train_d, ones, 0, B, filt, RATIO)
     idx, val = batch
 
@@ -153,7 +158,7 @@ def main():
         "epoch_s_reference_path": round((med["a"] + med["c"]) * ITERS_PER_EPOCH / 1e3, 2),
         "epoch_s_device_path": round((med["b"] + med["d"]) * ITERS_PER_EPOCH / 1e3, 2),
         "samples_ms": {k: [round(x, 4) for x in v] for k, v in times.items()},
-        "param_max_abs_diff_c_vs_d": drift,
+        "param_max_abs_diff_c_vs_d": drift, "optimizer_leg_d": a.optimizer,
     }))
 
 

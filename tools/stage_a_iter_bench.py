@@ -8,7 +8,7 @@ degrees), 128 entities per batch (`--entities_per_batch` of the reference's run 
 Nothing keyed on tensor identity survives an iteration in this regime ("fresh").  For comparison the same iteration with ONE batch
 re-used every time ("cached": what tools/kg_scale_bench.py --kbgat measures) and the batch assembly alone.  Prints one JSON line.
 
-  python tools/stage_a_iter_bench.py [--iters 30] [--entities 128] [--no-2hop]
+  python tools/stage_a_iter_bench.py [--iters 30] [--entities 128] [--no-2hop] [--optimizer {torch,recon}]
 """
 import argparse
 import json
@@ -75,6 +75,7 @@ def main(argv=None):
     ap.add_argument("--loss-rows", choices=["torch", "recon"], default="torch", help="table[index] (the reference's loss code) or recon_amd.gat_layers.gather_rows")
     ap.add_argument("--profile", action="store_true", help="cProfile of the host side of fresh iterations (top functions by own time)")
     ap.add_argument("--launches", action="store_true", help="also count the device launches of a fresh iteration (torch.profiler)")
+    ap.add_argument("--optimizer", choices=["torch", "recon"], default="torch", help="torch.optim.SGD (the reference's) or recon_amd.optim.SGD (one launch)")
     args = ap.parse_args(argv)
     dv = torch.device("cuda:0")
     torch.autograd.set_multithreading_enabled(False)
@@ -84,7 +85,11 @@ def main(argv=None):
     torch.manual_seed(0)
     model = SpKBGATModified(torch.randn(N, 50), torch.randn(nrel, 50), [100, 200], [100, 200], 0.3, 0.2, [2, 2]).to(dv)
     model.train()
-    opt = torch.optim.SGD(model.parameters(), lr=1e-3)
+    if args.optimizer == "recon":
+        from recon_amd.optim import SGD
+        opt = SGD(model.parameters(), lr=1e-3)
+    else:
+        opt = torch.optim.SGD(model.parameters(), lr=1e-3)
     loss_fn = torch.nn.MarginRankingLoss(margin=1.0)
     g = torch.Generator().manual_seed(1)
     sources_all = torch.unique(adj_idx[1])
@@ -175,7 +180,7 @@ def main(argv=None):
     E1, E2 = one[1][0].shape[1], (0 if args.no_2hop else one[2].shape[0])
     launches = count_launches(lambda: train_iter(make_batch())) if args.launches else None
     res = ({"workload": "stage-A iteration (GAT/main.py:478-525): sampler batch -> SpKBGATModified fwd -> margin loss -> bwd -> SGD, FB15k-237-sized synthetic KG",
-                      "entities_per_batch": args.entities, "loss_rows": args.loss_rows, "edges_1hop": E1, "quads_2hop": E2,
+                      "entities_per_batch": args.entities, "loss_rows": args.loss_rows, "optimizer": args.optimizer, "edges_1hop": E1, "quads_2hop": E2,
                       "batch_assembly_ms": t_batch, "iteration_cached_batch_ms": t_cached, "iteration_cached_median_ms": float(np.median(each_cached)),
                       "iteration_fresh_batch_ms": t_fresh,
                       "iteration_fresh_median_ms": float(np.median(each_fresh)), "iteration_fresh_max_ms": float(max(each_fresh)),
