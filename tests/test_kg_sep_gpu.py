@@ -118,7 +118,7 @@ def test_kg_sep_shell_trains():
     assert gat.W_ent2rel.grad[2].abs().sum() == 0                                  # relation 2 is in no triple
 
 
-@pytest.mark.parametrize("D", [1, 37, 200, 257, 512])
+@pytest.mark.parametrize("D", [1, 37, 144, 145, 200, 257, 304, 305, 512])       # 144 | 145, 304 | 305: the row-block switches of k_kgs_tables
 def test_kg_sep_tables_fp64_band_and_deterministic(D):
     from recon_amd import kg_sep
     n_ent, n_rel = 101, 5

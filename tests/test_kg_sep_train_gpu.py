@@ -114,7 +114,7 @@ def _t64(m, gat, tri):
     return torch.tanh(X), 2 * ((E.shape[1] + 2) * EPS32 * Xa + 8 * EPS32)
 
 
-@pytest.mark.parametrize("D", [1, 37, 200, 257, 512])
+@pytest.mark.parametrize("D", [1, 37, 144, 145, 200, 257, 304, 305, 512])       # 304 | 305: the row-block switch of k_kgs_ent2rel; 144 | 145: that of the tables
 def test_ent2rel_rows_within_fp64_band(D):
     from recon_amd import kg_sep_train
     m, gat, tri, _ = _case(D, D)

@@ -113,8 +113,9 @@ def _fp64(E, Rel, W, tri, n_pos, reps, margin):
     return T, tau, x, tau_x, norm, tau_n, v, tau_v
 
 
-def _two_step(E, Rel, W, tri, n_pos, reps, margin, g_up=1.0, runs=1):
-    """The whole check of one case; returns the gradients of the last run."""
+def _two_step(E, Rel, W, tri, n_pos, reps, margin, g_up=1.0, runs=1, keep_w=False):
+    """The whole check of one case; returns the gradients of the last run.  keep_w: the leaf of W's gradient is W's own memory (a detached
+    alias) instead of a clone, which would sit at the allocator's alignment whatever W's is."""
     from recon_amd.sep_space import batch_gat_loss, gat_loss_parts
     M, D, P = tri.shape[0], E.shape[1], n_pos * reps
     T64, tau, x64, tau_x, n64, tau_n, v64, tau_v = _fp64(E, Rel, W, tri, n_pos, reps, margin)
@@ -138,6 +139,9 @@ def _two_step(E, Rel, W, tri, n_pos, reps, margin, g_up=1.0, runs=1):
         assert bool((A[v_dec] == (v64 > 0)[v_dec]).all())
         # step 2: the fp64 linear backward under these decisions, with fp32 bands
         Ed, Rd, Wd = (t.clone().requires_grad_(True) for t in (E, Rel, W))
+        if keep_w:
+            Wd = W.detach().requires_grad_(True)
+            assert Wd.data_ptr() == W.data_ptr() and Wd.is_contiguous()
         l = batch_gat_loss(torch.nn.MarginRankingLoss(margin=margin), tri, Ed, Rd, _gat(Wd), valid_invalid_ratio_gat=reps // 2)
         assert torch.equal(l.detach().view(torch.int32), loss.view(torch.int32))
         (l * g_up).backward()
@@ -174,13 +178,33 @@ def _two_step(E, Rel, W, tri, n_pos, reps, margin, g_up=1.0, runs=1):
     return out
 
 
-@pytest.mark.parametrize("D,ratio", [(1, 1), (37, 2), (200, 3), (257, 1), (512, 2)])
-def test_sep_loss_two_step_check_within_fp64_bands(D, ratio):
+@pytest.mark.parametrize("D,ratio,w_scale", [(1, 1, 1.0), (37, 2, 1.0), (200, 3, 1.0), (257, 1, 1.0), (331, 3, 0.5), (512, 2, 0.2)],
+                         ids=["1-1", "37-2", "200-3", "257-1", "331-3", "512-2"])
+def test_sep_loss_two_step_check_within_fp64_bands(D, ratio, w_scale):
     # the worst-case band grows with D times the size of the products.  At D = 512 pre-activations of unit standard deviation leave 1.4e-3 of the
     # elements and 6 % of the 140 pairs undecided in fp64, more than the check admits, 0.5 still 2.1 % of the pairs; 0.2 leaves 5.5e-4 and 0.7 %
-    # (measured on the fp64 side alone, before any device run)
-    E, Rel, W, tri, n_pos, reps, margin = _case(D, 100 + D, ratio, w_scale=0.2 if D > 500 else 1.0)
+    # (measured on the fp64 side alone, before any device run).  D = 331 (304 < D <= 512, D % 4 != 0: k_kgsl_rows<2, false>) at 0.5 leaves
+    # 4.3e-4 and 0.67 %
+    E, Rel, W, tri, n_pos, reps, margin = _case(D, 100 + D, ratio, w_scale=w_scale)
     _two_step(E, Rel, W, tri, n_pos, reps, margin, g_up=1.5, runs=2)
+
+
+@pytest.mark.parametrize("D,ratio,w_scale", [(200, 3, 1.0), (308, 2, 0.2)])
+def test_sep_loss_w_ent2rel_one_float_into_a_larger_buffer(D, ratio, w_scale):
+    """W_ent2rel as a contiguous view 4 bytes into a buffer: D % 4 == 0 but no 16-byte alignment, so the row-gradient kernel takes its scalar
+    loads (k_kgsl_rows<4, false> at D = 200, <2, false> at D = 308; 0.2 leaves 2.0e-4 of the elements and no pair undecided in fp64 there).
+    The two-step check holds, and the float4 and the scalar loads feed the same MFMA chain: the loss and all three gradients equal the run
+    on the aligned copy bit for bit."""
+    E, Rel, W, tri, n_pos, reps, margin = _case(D, 100 + D, ratio, w_scale=w_scale)
+    buf = torch.full((W.numel() + 8,), float("nan"), device=DEV)
+    Wo = buf[1:1 + W.numel()].view(W.shape)
+    Wo.copy_(W)
+    assert Wo.is_contiguous() and Wo.data_ptr() % 16 == 4 and W.data_ptr() % 16 == 0
+    off = _two_step(E, Rel, Wo, tri, n_pos, reps, margin, g_up=1.5, keep_w=True)
+    ali = _two_step(E, Rel, W, tri, n_pos, reps, margin, g_up=1.5)
+    for name, a, b in zip(("loss", "g_E", "g_Rel", "g_W"), off, ali):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), name
+    assert bool(torch.isnan(buf[0])) and bool(torch.isnan(buf[1 + W.numel():]).all())
 
 
 def test_sep_loss_stage_a_size_twice():
