@@ -956,6 +956,38 @@ int recon_rel_translation_bwd(const float* g_out, const void* saved, int64_t M, 
                               recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * E7  The entity-context encoder's character CNN (csrc/char_cnn.hip): models/models.py:57-61,
+ *         pre[s][t][o] = conv_b[o] + sum_k sum_c emb[chars[s][t + k]][c] conv_w[o][c][k],
+ *         out[s][w][o] = tanh(max over t in [w span, (w + 1) span) of pre[s][t][o]),
+ *     chars [S][cfs - 1 + W span] int32 or int64 (index_bytes = 4 or 8; row stride ld_chars in elements, read in place), emb [V][C],
+ *     conv_w [Fo][C][cfs], conv_b [Fo], out [S][W][Fo], all fp32 and contiguous.  No [S][Lc][.] tensor is written: the convolution of
+ *     an embedding is cfs table lookups, T[k] = emb . conv_w[:, :, k]^T.  Ids outside [0, V) are clamped into the table.
+ * ------------------------------------------------------------------------------------------*/
+/* Shapes the kernels take (models/models.py:57-61): S, W, C >= 1, 1 <= span <= 255, 1 <= cfs <= 16, span + cfs - 1 <= 64 (one lane per
+ * id of a word), 1 <= Fo <= 256, cfs V Fo <= 2^22, S W Fo <= 2^40. */
+int recon_char_features_supported(int64_t S, int32_t W, int32_t span, int32_t cfs, int32_t V, int32_t C, int32_t Fo);
+/* Bytes of the workspace (models/models.py:57-61) of the forward (backward = 0: the cfs tables) or of the backward (backward = 1: one
+ * private dT [cfs][V][Fo] + d_bias [Fo] per workgroup, at most 512 of them, and their sum).  16-byte aligned, any contents; 0 for a
+ * shape recon_char_features_supported refuses. */
+size_t recon_char_features_workspace_bytes(int64_t S, int32_t W, int32_t span, int32_t cfs, int32_t V, int32_t C, int32_t Fo, int32_t backward);
+/* Forward (models/models.py:57-61).  One wave per word, lane = output channel; the tables lie in LDS up to 144 KiB and are read through
+ * L2 above.  The FIRST maximum of a window wins, as torch's max_pool1d picks it; arg_pos [S][W][Fo] (one byte each, or NULL when no
+ * backward follows) receives its position in the window.  keep (dropout factors [S][Lc][C]) must be NULL: the masked form is not built,
+ * RECON_ERR_UNSUPPORTED otherwise.  S == 0: nothing is launched.  Two launches (tables, words). */
+int recon_char_features_fwd(const void* chars, int32_t index_bytes, int64_t ld_chars, const float* emb, const float* conv_w, const float* conv_b,
+                            const float* keep, int64_t S, int32_t W, int32_t span, int32_t cfs, int32_t V, int32_t C, int32_t Fo, float* out,
+                            uint8_t* arg_pos, void* workspace, size_t workspace_bytes, recon_stream_t stream);
+/* Backward (models/models.py:57-61) from the forward's out and arg_pos: d_pre = g_out (1 - out^2) goes to dT[k][chars[t* + k]][o] and to
+ * g_conv_b; g_emb = sum_k dT[k] . conv_w[:, :, k] with row padding_idx zero (nn.Embedding's padding_idx; < 0: none), g_conv_w[:, :, k] =
+ * dT[k]^T . emb.  g_out [S][W][Fo] contiguous.  No floating-point atomics: every workgroup owns a fixed run of words and a private dT
+ * with one writer per cell, the workgroups are added in index order: bitwise identical from run to run.  keep must be NULL.  S == 0
+ * writes zeros.  Three launches (and one memset when the private dT does not fit in LDS). */
+int recon_char_features_bwd(const void* chars, int32_t index_bytes, int64_t ld_chars, const float* emb, const float* conv_w, const float* keep,
+                            const float* g_out, const float* out, const uint8_t* arg_pos, int64_t S, int32_t W, int32_t span, int32_t cfs,
+                            int32_t V, int32_t C, int32_t Fo, int32_t padding_idx, float* g_emb, float* g_conv_w, float* g_conv_b, void* workspace,
+                            size_t workspace_bytes, recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
  *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
  * ------------------------------------------------------------------------------------------*/

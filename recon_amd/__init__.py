@@ -3,3 +3,4 @@ propagation), behind the reference's own nn.Module surface.  See DESIGN.md / INT
 __version__ = "0.1.0"
 
 from .translation import translation_residuals  # noqa: E402,F401
+from .char_features import char_word_features  # noqa: E402,F401

@@ -206,6 +206,12 @@ SYMBOLS = [
     ("recon_rel_translation_fwd", C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_f32p,
                                             C.c_void_p, C.c_void_p]),
     ("recon_rel_translation_bwd", C.c_int, [c_f32p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, c_f32p, C.c_void_p]),
+    ("recon_char_features_supported", C.c_int, [C.c_int64] + [C.c_int32] * 6),
+    ("recon_char_features_workspace_bytes", C.c_size_t, [C.c_int64] + [C.c_int32] * 7),
+    ("recon_char_features_fwd", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64] + [C.c_int32] * 6
+                                         + [c_f32p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("recon_char_features_bwd", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int64]
+                                         + [C.c_int32] * 7 + [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("recon_start_entity_embeddings", C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p,
                                                 C.c_void_p]),
     ("recon_start_entity_embeddings_bwd", C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_void_p, C.c_void_p]),

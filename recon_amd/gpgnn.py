@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 from .propagation import (build_block_adjacency, propagate, propagate_blocks, make_start_embedding, make_start_entity_embeddings, get_head_indices,
                           get_tail_indices)
+from .char_features import char_word_features
 
 
 class GPGNN(nn.Module):
@@ -96,13 +97,20 @@ class CharEmbeddings(nn.Module):
     def forward(self, chars):
         return self.dropout(self.embeddings(chars))
 
+    def draw_keep(self, S, Lc, C, device):
+        """Dropout factors for the [S, Lc, C] gathered embedding, drawn as `forward` draws them (one nn.Dropout call on a tensor of that
+        shape); None in eval mode or at p = 0.  `char_word_features` multiplies them in, so recorded factors can be replayed."""
+        if self.training and self.dropout.p > 0:
+            return self.dropout(torch.ones(S, Lc, C, dtype=self.embeddings.weight.dtype, device=device))
+        return None
+
 
 class EntityEmbedding(nn.Module):
     """Entity attribute context encoder, models/models.py:26-83: every context line of an entity is a word sequence (word
     vectors + char-CNN features) run through an LSTM; the final states of all lines of one entity are convolved and max-pooled
-    over the unmasked lines into one vector per entity.  Stock PyTorch-ROCm ops (MIOpen LSTM / convolution): this is the
-    encoder in front of the propagation path, not the path.  Keys: word_embeddings.weight (the caller's table, shared),
-    char_embeddings.embeddings.weight, lstm.*, conv1d.*, conv1d_entity.*."""
+    over the unmasked lines into one vector per entity.  The char-CNN is `char_word_features` (csrc/char_cnn.hip); the LSTM and the
+    entity-level convolution are stock PyTorch-ROCm ops (MIOpen): this is the encoder in front of the propagation path, not the path.
+    Keys: word_embeddings.weight (the caller's table, shared), char_embeddings.embeddings.weight, lstm.*, conv1d.*, conv1d_entity.*."""
 
     def __init__(self, input_dim, hidden_dim, layers, is_bidirectional, drop_out_rate, entity_embed_dim, conv_filter_size,
                  entity_conv_filter_size, word_embeddings, char_embed_dim, max_word_len_entity, char_vocab, char_feature_size):
@@ -123,8 +131,10 @@ class EntityEmbedding(nn.Module):
         words = words.reshape(U * lines, words.shape[2])
         chars = chars.reshape(U * lines, chars.shape[2])
         word_vec = self.word_embeddings(words)
-        char_vec = self.char_embeddings(chars).permute(0, 2, 1)
-        char_feat = torch.tanh(F.max_pool1d(self.conv1d(char_vec), self.word_span, self.word_span)).permute(0, 2, 1)
+        emb = self.char_embeddings
+        keep = emb.draw_keep(chars.shape[0], chars.shape[1], emb.embeddings.embedding_dim, chars.device)
+        char_feat = char_word_features(chars, emb.embeddings.weight, self.conv1d.weight, self.conv1d.bias, self.word_span, keep=keep,
+                                       padding_idx=emb.embeddings.padding_idx)                                              # :57-61
         _, (h_n, _) = self.lstm(torch.cat((word_vec, char_feat), -1))
         # last layer, both directions side by side (the reference reshapes to (layers, 2, batch, hidden): bidirectional only)
         h_n = h_n.view(self.layers, 2, U * lines, self.hidden_dim)[-1].permute(1, 0, 2).reshape(U, lines, 2 * self.hidden_dim)

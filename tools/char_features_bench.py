@@ -1,0 +1,118 @@
+"""recon_amd.char_word_features (csrc/char_cnn.hip) against the stock sequence it replaced in EntityEmbedding.forward, timed in one process.
+
+    python tools/char_features_bench.py [--rounds 5] [--out profiles/char_features_bench.jsonl]
+
+One JSON line per (entities U, mode): S = 32 U sequences of 32 words at the reference's widths (model_params.json: char_embed_dim 50,
+char_feature_size 50, conv_filter_size 3, max_char_len 10; 90 characters).  Modes: eval (no dropout: the table form) and train (p = 0.5:
+the stock path is dropout(embedding(chars)); the op's path draws the factors on a ones tensor, as CharEmbeddings.draw_keep does, and
+hands them over as `keep`, which runs the stock chain as long as the masked form has no kernel).  Per path: median and minimum milliseconds
+of the forward alone and of forward + backward (device events), the launches of one forward + backward (kernels, memsets and copies the
+profiler sees on the device) and torch.cuda.max_memory_allocated above the inputs.  The two paths alternate round by round on the same
+data.  Lines are appended to --out."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+ENTITIES = [45, 450]
+LINES, WORDS, MAX_CHAR, CFS, C, FO, V, P = 32, 32, 10, 3, 50, 50, 90, 0.5
+
+
+def timed(fn, g_out):
+    """(forward ms, forward + backward ms, peak bytes above what was allocated before) of fn() and its backward."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    e[0].record()
+    out = fn()
+    e[1].record()
+    out.backward(g_out)
+    e[2].record()
+    torch.cuda.synchronize()
+    return e[0].elapsed_time(e[1]), e[0].elapsed_time(e[2]), torch.cuda.max_memory_allocated() - base
+
+
+def launches(fn, g_out):
+    """Device-side events (kernels, memsets, copies) of one forward + backward, or None where the profiler is not available."""
+    try:
+        from torch.autograd import DeviceType
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn().backward(g_out)
+            torch.cuda.synchronize()
+        return sum(1 for ev in prof.events() if ev.device_type == DeviceType.CUDA)
+    except Exception:                                                      # the count is a by-product: the timings do not depend on it
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from recon_amd import _lib, char_word_features
+    d = torch.device("cuda:0")
+    span = MAX_CHAR + CFS - 1
+    lines = []
+    for U in ENTITIES:
+        S = LINES * U
+        g = torch.Generator().manual_seed(U)
+        lens = torch.randint(1, MAX_CHAR + 1, (S, WORDS), generator=g)
+        live = (torch.arange(span)[None, None, :] < lens[:, :, None]) & (torch.arange(WORDS)[None, :, None] < torch.randint(0, WORDS + 1, (S, 1, 1), generator=g))
+        chars = torch.zeros(S, CFS - 1 + WORDS * span, dtype=torch.int64)
+        chars[:, :WORDS * span] = (torch.randint(1, V, (S, WORDS, span), generator=g) * live).view(S, -1)
+        chars = chars.to(d)
+        E = torch.randn(V, C, generator=g)
+        E[0] = 0
+        E = E.to(d).requires_grad_(True)
+        Wc = (torch.randn(FO, C, CFS, generator=g) * (2.0 / (C * CFS + FO * CFS)) ** 0.5).to(d).requires_grad_(True)
+        b = (0.1 * torch.randn(FO, generator=g)).to(d).requires_grad_(True)
+        g_out = torch.randn(S, WORDS, FO, generator=g).to(d)
+        Lc = chars.shape[1]
+
+        def stock(train):
+            x = F.dropout(F.embedding(chars, E, padding_idx=0), P, train).permute(0, 2, 1)
+            return torch.tanh(F.max_pool1d(F.conv1d(x, Wc, b), span, span)).permute(0, 2, 1)
+
+        def op(train):
+            keep = F.dropout(torch.ones(S, Lc, C, device=d), P, True) if train else None
+            return char_word_features(chars, E, Wc, b, span, keep=keep)
+
+        for mode in ("eval", "train"):
+            paths = {"op": lambda: op(mode == "train"), "chain": lambda: stock(mode == "train")}
+            res = {k: [] for k in paths}
+            for rnd in range(a.rounds + 1):                               # round 0 warms up
+                for k, fn in paths.items():
+                    E.grad = Wc.grad = b.grad = None
+                    r = timed(fn, g_out)
+                    if rnd:
+                        res[k].append(r)
+            geo = (S, WORDS, span, CFS, V, C, FO)
+            line = {"entities": U, "S": S, "words": WORDS, "mode": mode, "rounds": a.rounds,
+                    "compulsory_bytes": chars.numel() * 8 + S * WORDS * FO * 4, "gathered_embedding_bytes": S * Lc * C * 4,
+                    "workspace_bytes_fwd": _lib.lib().recon_char_features_workspace_bytes(*geo, 0),
+                    "workspace_bytes_bwd": _lib.lib().recon_char_features_workspace_bytes(*geo, 1)}
+            for k, rs in res.items():
+                for i, name in enumerate(("fwd_ms", "fwd_bwd_ms")):
+                    line["%s_%s_median" % (k, name)] = round(statistics.median(r[i] for r in rs), 4)
+                    line["%s_%s_min" % (k, name)] = round(min(r[i] for r in rs), 4)
+                line["%s_peak_bytes" % k] = max(r[2] for r in rs)
+                E.grad = Wc.grad = b.grad = None
+                line["%s_launches_fwd_bwd" % k] = launches(paths[k], g_out)
+            line["speedup_fwd_bwd_median"] = round(line["chain_fwd_bwd_ms_median"] / line["op_fwd_bwd_ms_median"], 3)
+            lines.append(json.dumps(line))
+            print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
