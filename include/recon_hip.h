@@ -972,8 +972,8 @@ int recon_char_features_supported(int64_t S, int32_t W, int32_t span, int32_t cf
 size_t recon_char_features_workspace_bytes(int64_t S, int32_t W, int32_t span, int32_t cfs, int32_t V, int32_t C, int32_t Fo, int32_t backward);
 /* Forward (models/models.py:57-61).  One wave per word, lane = output channel; the tables lie in LDS up to 144 KiB and are read through
  * L2 above.  The FIRST maximum of a window wins, as torch's max_pool1d picks it; arg_pos [S][W][Fo] (one byte each, or NULL when no
- * backward follows) receives its position in the window.  keep (dropout factors [S][Lc][C]) must be NULL: the masked form is not built,
- * RECON_ERR_UNSUPPORTED otherwise.  S == 0: nothing is launched.  Two launches (tables, words). */
+ * backward follows) receives its position in the window.  keep (dropout factors [S][Lc][C]) must be NULL, RECON_ERR_UNSUPPORTED otherwise:
+ * the masked form takes packed bits (recon_char_masked_fwd).  S == 0: nothing is launched.  Two launches (tables, words). */
 int recon_char_features_fwd(const void* chars, int32_t index_bytes, int64_t ld_chars, const float* emb, const float* conv_w, const float* conv_b,
                             const float* keep, int64_t S, int32_t W, int32_t span, int32_t cfs, int32_t V, int32_t C, int32_t Fo, float* out,
                             uint8_t* arg_pos, void* workspace, size_t workspace_bytes, recon_stream_t stream);
@@ -986,6 +986,45 @@ int recon_char_features_bwd(const void* chars, int32_t index_bytes, int64_t ld_c
                             const float* g_out, const float* out, const uint8_t* arg_pos, int64_t S, int32_t W, int32_t span, int32_t cfs,
                             int32_t V, int32_t C, int32_t Fo, int32_t padding_idx, float* g_emb, float* g_conv_w, float* g_conv_b, void* workspace,
                             size_t workspace_bytes, recon_stream_t stream);
+
+/* The same char-CNN WITH dropout factors on the gathered embedding (csrc/char_mask.hip; models/models.py:57-61 in training mode), the
+ * factors packed: bits [S][Lc][KW] int32, KW = ceil(C / 32), Lc = cfs - 1 + W span, contiguous; factor (s, j, c) = scale if bit c % 32 of
+ * word c / 32 is set, else 0.  Bits at and above C in the last word are ignored.
+ *         X[j][c] = bit(s, j, c) ? emb[chars[s][j]][c] : 0,   pre[s][t][o] = conv_b[o] + scale sum_k sum_c X[t + k][c] conv_w[o][c][k].
+ * A real fp32 convolution (v_mfma_f32_16x16x4_f32: an fp32 fma chain, no reduced-precision operand); nothing of size S Lc C is written.
+ * Status codes, ids (int32 / int64, read in place through ld_chars, clamped into [0, V)) and the 16-byte workspace alignment are the
+ * table form's. */
+/* Shapes the masked kernels take (models/models.py:57-61): the table form's limits (S, W >= 1, 1 <= span <= 255, 1 <= cfs <= 16,
+ * span + cfs - 1 <= 64, 1 <= Fo <= 256, S W Fo <= 2^40) and 1 <= C <= 64 (one lane per embedding channel in the backward, KW <= 2),
+ * V C + Fo C cfs + Fo <= 2^22 (one private accumulator set of the backward). */
+int recon_char_masked_supported(int64_t S, int32_t W, int32_t span, int32_t cfs, int32_t V, int32_t C, int32_t Fo);
+/* Bytes of the workspace (models/models.py:57-61) of the masked forward (backward = 0: the filter bank as the MFMA's B operand) or
+ * backward (backward = 1: one private dE [V][C] + dW [Fo][cfs][C] + db [Fo] per workgroup, at most 256 of them).  16-byte aligned, any
+ * contents; 0 for a shape recon_char_masked_supported refuses. */
+size_t recon_char_masked_workspace_bytes(int64_t S, int32_t W, int32_t span, int32_t cfs, int32_t V, int32_t C, int32_t Fo, int32_t backward);
+/* Draws the bits of n_positions = S Lc character positions (the dropout of models/models.py:57-61 as packed bits) into bits
+ * [n_positions][ceil(C / 32)].  Philox4x32-10 with key (low, high half of seed); position q owns the Gp = ceil(C / 4) counters
+ * offset + q Gp + g (a 64-bit value: counter words 0 and 1, words 2 and 3 zero); channel c takes output word c % 4 of counter g = c / 4
+ * and its bit is set iff word >= threshold, threshold = min(2^32 - 1, floor(p 2^32)) for a drop probability p.  Bits at and above C are
+ * written as 0.  1 <= C <= 2^16.  One launch; n_positions == 0: none. */
+int recon_char_keep_bits_draw(int32_t* bits, int64_t n_positions, int32_t C, uint32_t threshold_u32, uint64_t seed_u64, uint64_t offset_u64,
+                              recon_stream_t stream);
+/* Masked forward (models/models.py:57-61).  One wave per word: the word's masked rows are staged in LDS once and multiplied with the
+ * filter bank on the fp32 MFMA; emb and the filter bank lie in LDS up to 144 KiB and are read through L2 above.  The FIRST maximum of a
+ * window wins; a window whose taps are all masked or padding gives exactly tanh(conv_b[o]).  arg_pos as in recon_char_features_fwd
+ * (NULL when no backward follows).  S == 0: nothing is launched.  Two launches (operand layout, words). */
+int recon_char_masked_fwd(const void* chars, int32_t index_bytes, int64_t ld_chars, const float* emb, const float* conv_w, const float* conv_b,
+                          const int32_t* bits, float scale, int64_t S, int32_t W, int32_t span, int32_t cfs, int32_t V, int32_t C, int32_t Fo,
+                          float* out, uint8_t* arg_pos, void* workspace, size_t workspace_bytes, recon_stream_t stream);
+/* Masked backward (models/models.py:57-61) from the forward's out and arg_pos: d_pre = g_out (1 - out^2) at the saved position t*,
+ * g_conv_w[o][c][k] += d_pre scale X[t* + k][c], dX[t* + k][c] += d_pre scale conv_w[o][c][k], g_emb[chars[j]][c] += bit dX[j][c] (row
+ * padding_idx zero; < 0: none), g_conv_b[o] += d_pre.  No floating-point atomics: every workgroup owns a fixed run of words and private
+ * accumulators with one writer per cell (LDS up to 144 KiB, else its slab of the workspace), the workgroups are added in index order:
+ * bitwise identical from run to run.  S == 0 writes zeros.  Two launches (and one memset when the accumulators do not fit in LDS). */
+int recon_char_masked_bwd(const void* chars, int32_t index_bytes, int64_t ld_chars, const float* emb, const float* conv_w, const int32_t* bits,
+                          float scale, const float* g_out, const float* out, const uint8_t* arg_pos, int64_t S, int32_t W, int32_t span,
+                          int32_t cfs, int32_t V, int32_t C, int32_t Fo, int32_t padding_idx, float* g_emb, float* g_conv_w, float* g_conv_b,
+                          void* workspace, size_t workspace_bytes, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.

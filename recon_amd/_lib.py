@@ -212,6 +212,13 @@ SYMBOLS = [
                                          + [c_f32p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("recon_char_features_bwd", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int64]
                                          + [C.c_int32] * 7 + [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("recon_char_masked_supported", C.c_int, [C.c_int64] + [C.c_int32] * 6),
+    ("recon_char_masked_workspace_bytes", C.c_size_t, [C.c_int64] + [C.c_int32] * 7),
+    ("recon_char_keep_bits_draw", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
+    ("recon_char_masked_fwd", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_float, C.c_int64]
+                                       + [C.c_int32] * 6 + [c_f32p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("recon_char_masked_bwd", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, c_f32p, c_f32p, C.c_void_p, C.c_float, c_f32p, c_f32p, C.c_void_p,
+                                        C.c_int64] + [C.c_int32] * 7 + [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("recon_start_entity_embeddings", C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p,
                                                 C.c_void_p]),
     ("recon_start_entity_embeddings_bwd", C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_void_p, C.c_void_p]),

@@ -10,7 +10,7 @@ import torch.nn.functional as F
 
 from .propagation import (build_block_adjacency, propagate, propagate_blocks, make_start_embedding, make_start_entity_embeddings, get_head_indices,
                           get_tail_indices)
-from .char_features import char_word_features
+from .char_features import char_word_features, draw_packed_keep
 
 
 class GPGNN(nn.Module):
@@ -104,13 +104,26 @@ class CharEmbeddings(nn.Module):
             return self.dropout(torch.ones(S, Lc, C, dtype=self.embeddings.weight.dtype, device=device))
         return None
 
+    def draw_packed_keep(self, S, Lc, C, device):
+        """The same factors one bit each (`char_features.draw_packed_keep`: Bernoulli(1 - p) from a counter-based draw governed by
+        torch.manual_seed, NOT the stream nn.Dropout consumes), which `char_word_features` takes into its masked kernels; None in eval
+        mode or at p = 0."""
+        if self.training and self.dropout.p > 0:
+            return draw_packed_keep(S, Lc, C, self.dropout.p, device)
+        return None
+
 
 class EntityEmbedding(nn.Module):
     """Entity attribute context encoder, models/models.py:26-83: every context line of an entity is a word sequence (word
     vectors + char-CNN features) run through an LSTM; the final states of all lines of one entity are convolved and max-pooled
     over the unmasked lines into one vector per entity.  The char-CNN is `char_word_features` (csrc/char_cnn.hip); the LSTM and the
     entity-level convolution are stock PyTorch-ROCm ops (MIOpen): this is the encoder in front of the propagation path, not the path.
-    Keys: word_embeddings.weight (the caller's table, shared), char_embeddings.embeddings.weight, lstm.*, conv1d.*, conv1d_entity.*."""
+    Keys: word_embeddings.weight (the caller's table, shared), char_embeddings.embeddings.weight, lstm.*, conv1d.*, conv1d_entity.*.
+    packed_char_dropout (default False): draw the char embedding's dropout as packed bits (`CharEmbeddings.draw_packed_keep`), so that
+    training batches run the masked char-CNN kernels instead of the op chain.  Same distribution, another random stream than the
+    reference's nn.Dropout call: an opt-in, like `iid_keep_draws` of models.SpKBGATModified."""
+
+    packed_char_dropout = False
 
     def __init__(self, input_dim, hidden_dim, layers, is_bidirectional, drop_out_rate, entity_embed_dim, conv_filter_size,
                  entity_conv_filter_size, word_embeddings, char_embed_dim, max_word_len_entity, char_vocab, char_feature_size):
@@ -132,7 +145,8 @@ class EntityEmbedding(nn.Module):
         chars = chars.reshape(U * lines, chars.shape[2])
         word_vec = self.word_embeddings(words)
         emb = self.char_embeddings
-        keep = emb.draw_keep(chars.shape[0], chars.shape[1], emb.embeddings.embedding_dim, chars.device)
+        draw = emb.draw_packed_keep if self.packed_char_dropout else emb.draw_keep
+        keep = draw(chars.shape[0], chars.shape[1], emb.embeddings.embedding_dim, chars.device)
         char_feat = char_word_features(chars, emb.embeddings.weight, self.conv1d.weight, self.conv1d.bias, self.word_span, keep=keep,
                                        padding_idx=emb.embeddings.padding_idx)                                              # :57-61
         _, (h_n, _) = self.lstm(torch.cat((word_vec, char_feat), -1))

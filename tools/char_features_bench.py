@@ -5,10 +5,11 @@
 One JSON line per (entities U, mode): S = 32 U sequences of 32 words at the reference's widths (model_params.json: char_embed_dim 50,
 char_feature_size 50, conv_filter_size 3, max_char_len 10; 90 characters).  Modes: eval (no dropout: the table form) and train (p = 0.5:
 the stock path is dropout(embedding(chars)); the op's path draws the factors on a ones tensor, as CharEmbeddings.draw_keep does, and
-hands them over as `keep`, which runs the stock chain as long as the masked form has no kernel).  Per path: median and minimum milliseconds
-of the forward alone and of forward + backward (device events), the launches of one forward + backward (kernels, memsets and copies the
-profiler sees on the device) and torch.cuda.max_memory_allocated above the inputs.  The two paths alternate round by round on the same
-data.  Lines are appended to --out."""
+hands them over as `keep`, which runs the stock chain; a third path, op_packed, draws packed bits with draw_packed_keep, the draw inside
+the timed region, and runs the masked kernels of csrc/char_mask.hip).  Per path: median and minimum milliseconds of the forward alone and
+of forward + backward (device events), the launches of one forward + backward (kernels, memsets and copies the profiler sees on the
+device) and torch.cuda.max_memory_allocated above the inputs; for op_packed also the draw alone.  The paths alternate round by round on
+the same data.  Lines are appended to --out."""
 import argparse
 import json
 import os
@@ -58,6 +59,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from recon_amd import _lib, char_word_features
+    from recon_amd.char_features import draw_packed_keep
     d = torch.device("cuda:0")
     span = MAX_CHAR + CFS - 1
     lines = []
@@ -85,8 +87,22 @@ def main():
             keep = F.dropout(torch.ones(S, Lc, C, device=d), P, True) if train else None
             return char_word_features(chars, E, Wc, b, span, keep=keep)
 
+        def op_packed():
+            return char_word_features(chars, E, Wc, b, span, keep=draw_packed_keep(S, Lc, C, P, d))
+
+        def draw_ms():
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            torch.cuda.synchronize()
+            e[0].record()
+            draw_packed_keep(S, Lc, C, P, d)
+            e[1].record()
+            torch.cuda.synchronize()
+            return e[0].elapsed_time(e[1])
+
         for mode in ("eval", "train"):
             paths = {"op": lambda: op(mode == "train"), "chain": lambda: stock(mode == "train")}
+            if mode == "train":
+                paths["op_packed"] = op_packed
             res = {k: [] for k in paths}
             for rnd in range(a.rounds + 1):                               # round 0 warms up
                 for k, fn in paths.items():
@@ -107,6 +123,12 @@ def main():
                 E.grad = Wc.grad = b.grad = None
                 line["%s_launches_fwd_bwd" % k] = launches(paths[k], g_out)
             line["speedup_fwd_bwd_median"] = round(line["chain_fwd_bwd_ms_median"] / line["op_fwd_bwd_ms_median"], 3)
+            if mode == "train":
+                geo_m = _lib.lib().recon_char_masked_workspace_bytes
+                line.update({"packed_bits_bytes": S * Lc * ((C + 31) // 32) * 4, "packed_workspace_bytes_fwd": geo_m(*geo, 0),
+                             "packed_workspace_bytes_bwd": geo_m(*geo, 1),
+                             "op_packed_draw_ms_median": round(statistics.median(draw_ms() for _ in range(a.rounds + 1)), 4),
+                             "speedup_packed_fwd_bwd_median": round(line["chain_fwd_bwd_ms_median"] / line["op_packed_fwd_bwd_ms_median"], 3)})
             lines.append(json.dumps(line))
             print(lines[-1], flush=True)
     if a.out:
