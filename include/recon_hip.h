@@ -199,9 +199,19 @@ typedef struct {
 
 int recon_gat_fwd(const recon_graph* g, const recon_gat_fwd_args* args, recon_stream_t stream);
 
-/* the two stages of recon_gat_fwd, exported for profiling / tests */
+/* the two stages of recon_gat_fwd, exported for profiling / tests.
+ * recon_gat_edge_fwd reads P, Q, a_2 (and keep) and writes out (and sigma, Z); x, a (and edge_embed where E > 0) must be non-NULL
+ * but are not read.
+ * Load width: VEC = 4 floats where D % 4 == 0, P, Q, a_2 and out are 16-byte aligned and ld_out % 4 == 0; VEC = 2 where the same holds
+ * for D % 2, 8 bytes and ld_out % 2; else VEC = 1 (recon_gat_bwd: also grad_out, ld_gout, Gm, gP and partial).  A (node, head) row is
+ * held by at most 64 lanes x 8 register rows of VEC floats: D <= 2048 / 1024 / 512 at VEC 4 / 2 / 1, RECON_ERR_UNSUPPORTED above
+ * (nothing is launched, nothing written). */
 int recon_gat_project(const recon_graph* g, const recon_gat_fwd_args* args, recon_stream_t stream); /* K4: MFMA */
 int recon_gat_edge_fwd(const recon_graph* g, const recon_gat_fwd_args* args, recon_stream_t stream); /* K1: HBM  */
+/* the edge kernel instance (csrc/gat.hip: k_gat_edge_fwd / k_gat_edge_bwd / k_gat_src_gather<VEC, G, KR>) a head width selects:
+ * vec * 10000 + g * 100 + kr (vec: load width, g: lanes per (node, head) group, kr: register rows per lane), -1 where none exists.
+ * align_floats is 4, 2 or 1: what the pointers and leading dimensions of the call allow (see above).  Host only. */
+int32_t recon_gat_edge_instance(int32_t D, int32_t align_floats);
 
 /* --------------------------------------------------------------------------------------------
  * K2  backward of recon_gat_fwd (autograd of GAT/layers.py:111-178 incl. the custom backward at

@@ -166,6 +166,7 @@ SYMBOLS = [
     ("recon_gat_fwd", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatFwdArgs), C.c_void_p]),
     ("recon_gat_project", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatFwdArgs), C.c_void_p]),
     ("recon_gat_edge_fwd", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatFwdArgs), C.c_void_p]),
+    ("recon_gat_edge_instance", C.c_int32, [C.c_int32] * 2),
     ("recon_gat_bwd_partial_floats", C.c_size_t, [C.c_int32] * 6),
     ("recon_gat_bwd", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatBwdArgs), C.c_void_p]),
     ("recon_gat_atp_supported", C.c_int, [C.c_int32] * 6),

@@ -432,6 +432,13 @@ extern "C" int recon_gat_project(const recon_graph* g, const recon_gat_fwd_args*
     return RECON_OK;
 }
 
+extern "C" int32_t recon_gat_edge_instance(int32_t D, int32_t align_floats) {
+    Shape s;
+    if (D <= 0 || (align_floats != 4 && align_floats != 2 && align_floats != 1)) return -1;
+    if (!pick_shape(D, align_floats >= 4, align_floats >= 2, &s)) return -1;
+    return s.vec * 10000 + s.g * 100 + s.kr;
+}
+
 extern "C" int recon_gat_edge_fwd(const recon_graph* g, const recon_gat_fwd_args* a, recon_stream_t stream) {
     int rc = check_fwd(g, a);
     if (rc != RECON_OK) return rc;
