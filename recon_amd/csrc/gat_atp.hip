@@ -1657,14 +1657,15 @@ struct AtpSrcK {
     float* hubP;
     const int32_t* node_row;    // row compaction (recon_graph.node_row): gxd is indexed by ROW; a node without a row (-1) has no destination part.  NULL: gxd[node]
 };
+// (block bx of nbx: the walk's own launch, or the blocks in front of a launch it shares — k_gat_atp_src_skinny)
 template <int VEC, int KR>
-__global__ void __launch_bounds__(kBlock) k_gat_atp_src(const AtpSrcK p) {
+__device__ __forceinline__ void atp_src_wave(const AtpSrcK& p, int bx, int nbx) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int npb = (p.n_piece + kBlock / 64 - 1) / (kBlock / 64);       // piece blocks first, dealt round the XCDs (see k_gat_atp_fwd)
-    const int widx = blockIdx.x * (kBlock / 64) + wave;
-    const bool is_piece = static_cast<int>(blockIdx.x) < npb;
-    int node = xcd_block(blockIdx.x - npb, gridDim.x - npb) * (kBlock / 64) + wave;
+    const int widx = bx * (kBlock / 64) + wave;
+    const bool is_piece = bx < npb;
+    int node = xcd_block(bx - npb, nbx - npb) * (kBlock / 64) + wave;
     int beg, end;
     if (is_piece) {
         if (widx >= p.n_piece) return;
@@ -1763,6 +1764,9 @@ __global__ void __launch_bounds__(kBlock) k_gat_atp_src(const AtpSrcK p) {
     }
 }
 
+template <int VEC, int KR>
+__global__ void __launch_bounds__(kBlock) k_gat_atp_src(const AtpSrcK p) { atp_src_wave<VEC, KR>(p, blockIdx.x, gridDim.x); }
+
 // The second half of a source hub: wave = one (hub, 64-column stripe); g_x row = its direct part + the pieces' rows in table order,
 // Gs_src likewise (by the wave of stripe 0).
 __global__ void __launch_bounds__(kBlock) k_gat_atp_hub_src(const AtpSrcK p, const int32_t* __restrict__ hub_node, const int32_t* __restrict__ hub_ptr,
@@ -1790,23 +1794,41 @@ __global__ void __launch_bounds__(kBlock) k_gat_atp_hub_src(const AtpSrcK p, con
 // Tall-skinny transposed product with fixed-order reduction (replaces 128x128-tile GEMMs whose M is 8..32):
 //   out[j][c] = sum_r G[r*ldg + j] * X[row(r)*K + c],   j < NJ (<= 16), c < K,  row(r) = gather ? gather[r] : r
 // pass 1: block b sums its slice of rows into partial[b][j][c]; pass 2 adds the slices in order.
-// Up to two independent products per launch (blocks [0, j0.nb) run job 0, the rest job 1), like k_row_dots.
+// Up to three independent products per launch (blocks [0, j0.nb) run job 0, the next j1.nb job 1, the rest job 2), like k_row_dots.
 struct SkinnyJob { const float* G; const float* X; const int32_t* gather; float* partial; int32_t ldg, nj, rows, K, rpb, nb; };
-template <int NJ, bool B16 = false>
-__global__ void __launch_bounds__(256) k_skinny_tn_partial(const SkinnyJob j0, const SkinnyJob j1, const SkinnyJob j2) {
-    // 4 waves split the block's rows; lane l owns columns 4l..4l+3 of a 256-column stripe; fixed-order LDS combine
-    __shared__ float red[3][NJ][256];
-    const int which = static_cast<int>(blockIdx.x) < j0.nb ? 0 : (static_cast<int>(blockIdx.x) < j0.nb + j1.nb ? 1 : 2);
-    const SkinnyJob& jb = which == 0 ? j0 : (which == 1 ? j1 : j2);
+// A job whose coefficients are the per-source sums of g_sigma (G[j][h] = Gs_src[j][h]) can form them itself: the same in-order walk
+// of g_sigma over slot_by_src[rowptr_src[j] .. rowptr_src[j + 1]) that k_gat_atp_src does, so the same floats — and no wait for that kernel.
+struct SkinnySrc { const int32_t* rowptr_src; const int32_t* slot_by_src; const float* gsigma; };
+template <int NJ, bool B16, bool SRC>
+__device__ __forceinline__ void skinny_block(const SkinnyJob& jb, int bid, float (&red)[NJ][256], float* __restrict__ gsl, const SkinnySrc& sr, bool src) {
+    // 4 waves split the block's rows, RPI rows per wave and iteration; lane l owns columns 4l..4l+3 of a 256-column stripe;
+    // fixed-order LDS combine, wave 0 + wave 1 + wave 2 + wave 3 through one buffer
+    constexpr int RPI = 4;                                               // RPI * NJ <= 64: one coefficient per lane (8 rows at NJ = 8: 85 registers for 72, no faster)
     const float* __restrict__ G = jb.G;
     const float* __restrict__ X = jb.X;
     const int32_t* __restrict__ gather = jb.gather;
     float* __restrict__ partial = jb.partial;
     const int ldg = jb.ldg, nj = jb.nj, rows = jb.rows, K = jb.K, rows_per_block = jb.rpb;
-    const int bid = blockIdx.x - (which == 0 ? 0 : (which == 1 ? j0.nb : j0.nb + j1.nb));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r0 = bid * rows_per_block;
     const int r1 = min(rows, r0 + rows_per_block);
+    if (SRC && src) {                                                    // uniform.  gsl[(r - r0) * nj + h] (the launch reserves rpb * nj floats)
+        const int n = (r1 - r0) * nj;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int rr = i / nj, h = i - rr * nj;
+            const int beg = sr.rowptr_src[r0 + rr], end = sr.rowptr_src[r0 + rr + 1];
+            float gs = 0.f;
+            for (int c0 = beg; c0 < end; c0 += 4) {                      // four positions requested together, added in position order
+                float g4[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) g4[u] = sr.gsigma[static_cast<int64_t>(sr.slot_by_src[min(c0 + u, end - 1)]) * nj + h];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) if (c0 + u < end) gs += g4[u];
+            }
+            gsl[i] = gs;
+        }
+        __syncthreads();
+    }
     for (int c0 = 0; c0 < K; c0 += 256) {
         const int c = c0 + 4 * lane;
         float acc[NJ][4];
@@ -1815,20 +1837,20 @@ __global__ void __launch_bounds__(256) k_skinny_tn_partial(const SkinnyJob j0, c
         // gathered row ids are fetched one iteration ahead (lane q holds the id of row rb+q), so the row loads do not
         // wait behind an index load
         int gi = 0;
-        if (gather && lane < 4 && r0 + wave * 4 + lane < r1) gi = gather[r0 + wave * 4 + lane];
-        for (int rb = r0 + wave * 4; rb < r1; rb += 16) {
+        if (gather && lane < RPI && r0 + wave * RPI + lane < r1) gi = gather[r0 + wave * RPI + lane];
+        for (int rb = r0 + wave * RPI; rb < r1; rb += 4 * RPI) {
             int gnext = 0;
-            if (gather && lane < 4 && rb + 16 + lane < r1) gnext = gather[rb + 16 + lane];
-            float xv[4][4];
-            // the 4 x NJ coefficients of this iteration arrive with ONE load (lane q*NJ + j holds G[rb+q][j]) and are
+            if (gather && lane < RPI && rb + 4 * RPI + lane < r1) gnext = gather[rb + 4 * RPI + lane];
+            float xv[RPI][4];
+            // the RPI x NJ coefficients of this iteration arrive with ONE load (lane q*NJ + j holds G[rb+q][j]) and are
             // broadcast per use; one scalar-address load per coefficient made the kernel issue bound
             float gl = 0.f;
             {
                 const int q = lane / NJ, j = lane % NJ;
-                if (q < 4 && rb + q < r1 && j < nj) gl = G[static_cast<int64_t>(rb + q) * ldg + j];
+                if (q < RPI && rb + q < r1 && j < nj) gl = (SRC && src) ? gsl[(rb + q - r0) * nj + j] : G[static_cast<int64_t>(rb + q) * ldg + j];
             }
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
+            for (int q = 0; q < RPI; ++q) {
                 const int r = rb + q;
                 xv[q][0] = xv[q][1] = xv[q][2] = xv[q][3] = 0.f;
                 if (r < r1) {
@@ -1842,41 +1864,69 @@ __global__ void __launch_bounds__(256) k_skinny_tn_partial(const SkinnyJob j0, c
                 }
             }
             gi = gnext;
-            float gv[4][NJ];
 #pragma unroll
-            for (int q = 0; q < 4; ++q)
+            for (int q = 0; q < RPI; ++q)
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) gv[q][j] = (q * NJ + j < 64) ? lane_bcast(gl, (q * NJ + j) & 63) : 0.f;
+                for (int j = 0; j < NJ; ++j) {
+                    const float gv = lane_bcast(gl, q * NJ + j);
 #pragma unroll
-            for (int q = 0; q < 4; ++q)
+                    for (int v = 0; v < 4; ++v) acc[j][v] = fmaf(gv, xv[q][v], acc[j][v]);
+                }
+        }
+        for (int w = 1; w < 4; ++w) {
+            __syncthreads();
+            if (wave == w) {
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) acc[j][v] = fmaf(gv[q][j], xv[q][v], acc[j][v]);
-        }
-        __syncthreads();
-        if (wave > 0) {
+                    for (int v = 0; v < 4; ++v) red[j][4 * lane + v] = acc[j][v];
+            }
+            __syncthreads();
+            if (wave == 0) {
 #pragma unroll
-            for (int j = 0; j < NJ; ++j)
+                for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                for (int v = 0; v < 4; ++v) red[wave - 1][j][4 * lane + v] = acc[j][v];
+                    for (int v = 0; v < 4; ++v) acc[j][v] += red[j][4 * lane + v];
+            }
         }
-        __syncthreads();
         if (wave == 0) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
                 if (j < nj)
 #pragma unroll
                     for (int v = 0; v < 4; ++v)
-                        if (c + v < K)
-                            partial[(static_cast<int64_t>(bid) * nj + j) * K + c + v] =
-                                ((acc[j][v] + red[0][j][4 * lane + v]) + red[1][j][4 * lane + v]) + red[2][j][4 * lane + v];
+                        if (c + v < K) partial[(static_cast<int64_t>(bid) * nj + j) * K + c + v] = acc[j][v];
         }
     }
+}
+template <int NJ, bool B16 = false>
+__global__ void __launch_bounds__(256) k_skinny_tn_partial(const SkinnyJob j0, const SkinnyJob j1, const SkinnyJob j2) {
+    __shared__ float red[NJ][256];
+    const int which = static_cast<int>(blockIdx.x) < j0.nb ? 0 : (static_cast<int>(blockIdx.x) < j0.nb + j1.nb ? 1 : 2);
+    const SkinnyJob& jb = which == 0 ? j0 : (which == 1 ? j1 : j2);
+    skinny_block<NJ, B16, false>(jb, blockIdx.x - (which == 0 ? 0 : (which == 1 ? j0.nb : j0.nb + j1.nb)), red, nullptr, SkinnySrc{nullptr, nullptr, nullptr}, false);
 }
 // (A matrix-core form of these partial products — v_mfma_f32_16x16x4_f32 with the contraction over the rows, both H-column halves
 // of the node-side product in one pass over x — was measured at cfg 2: 17.7 - 18.9 us against 16.7 for this kernel.  Like the
 // score dots it is a few tens of MB behind a ~5 us kernel turn-around: the arithmetic is not what it waits for.)
+
+// The source walk and the three skinny products of up to 8 heads in ONE launch (no source-side hub pieces): blocks [0, nsrc) are
+// k_gat_atp_src's, the rest k_skinny_tn_partial<8>'s with job 1 (the source sums' product) forming its coefficients itself (SkinnySrc),
+// so that neither half waits for the other: both only read what the edge pass left.  Dynamic LDS: j1.rpb * j1.nj floats.
+template <int VEC, int KR, bool B16>
+__global__ void __launch_bounds__(kBlock) k_gat_atp_src_skinny(const AtpSrcK p, int32_t nsrc, const SkinnyJob j0, const SkinnyJob j1, const SkinnyJob j2,
+                                                               const SkinnySrc sr) {
+    static_assert(kBlock == 256, "skinny_block: 4 waves");
+    __shared__ float red[8][256];
+    extern __shared__ __attribute__((aligned(16))) float gsl[];
+    const int bx = blockIdx.x;
+    if (bx < nsrc) { atp_src_wave<VEC, KR>(p, bx, nsrc); return; }
+    const int b = bx - nsrc;
+    const int which = b < j0.nb ? 0 : (b < j0.nb + j1.nb ? 1 : 2);
+    const SkinnyJob& jb = which == 0 ? j0 : (which == 1 ? j1 : j2);
+    skinny_block<8, B16, true>(jb, b - (which == 0 ? 0 : (which == 1 ? j0.nb : j0.nb + j1.nb)), red, gsl, sr, which == 1);
+}
+
 // out[(j % P)*S1 + (j / P)*S2 + c] = sum_b partial[b][j][c]   (16 elements x 64 slice groups per block, fixed order)
 struct SkinnyRedJob { const float* partial; float* out; int64_t S1, S2; int32_t nb, nj, K, P, nblocks; };
 __global__ void __launch_bounds__(1024) k_skinny_reduce(const SkinnyRedJob j0, const SkinnyRedJob j1, const SkinnyRedJob j2) {
@@ -2286,7 +2336,19 @@ extern "C" size_t recon_gat_atp_bwd_partial_floats(int32_t N, int32_t E, int32_t
 
 // scratch of the skinny score-gradient products (<= kSkinnySlices row slices x 16 columns); separate from `partial` so that
 // the weight-gradient GEMM may run concurrently on another stream
-constexpr int kSkinnySlices = 1024;                              // row slices of the skinny products (first pass blocks)
+// kSkinnySlices: row slices of a skinny product (first pass blocks), rpb = max(32, rows / kSkinnySlices) rows each — two iterations of 4
+// waves x 4 rows at cfg 2.  Many short blocks, on purpose: a wave has no loads in flight across iterations, so the products stream only
+// while several blocks share a CU.  Measured at cfg 2 (profiles/atp_tail_bench.jsonl) with 48 | 48 | 96 slices of 192 / 352 rows and 8
+// rows per wave and iteration — partials of 1.2 MB instead of 9.8 MB, small enough for k_atp_weights_finish to sum them in place of
+// k_skinny_reduce: the launch shared with the source walk took 69 us against 26.5, k_atp_weights_finish 38 us against 17 (48 or 96
+// L2 reads in a row per element of g_u, in every block that needs the element), the step 0.444 ms against 0.396; 64 | 64 | 128 slices:
+// 0.437, 32 | 32 | 64: 0.462.  512 slices measured like 1024.
+constexpr int kSkinnySlices = 1024;
+constexpr size_t kSkinnySrcLdsMax = 32 * 1024;                   // k_gat_atp_src_skinny: the source job's coefficients, rpb x H floats
+static int skinny_rpb(int64_t rows) {
+    const int rpb = static_cast<int>(ceil_div64(rows, kSkinnySlices));
+    return rpb < 32 ? 32 : rpb;                                  // >= 8 rows per wave
+}
 extern "C" size_t recon_gat_atp_bwd_partial2_floats(int32_t N, int32_t E, int32_t F, int32_t R, int32_t D, int32_t H) {
     (void)N; (void)E; (void)D; (void)H;
     const size_t mx = static_cast<size_t>(F > R ? F : R);
@@ -2419,7 +2481,9 @@ extern "C" int recon_gat_atp_bwd_phase(const recon_graph* g, const recon_gat_atp
         }
         RECON_CHECK_LAUNCH();
     }
-    // (3) source-side sums over the CSC view
+    // (3) source-side sums over the CSC view, and (5) g_u = [Gs_dst | Gs_src]^T x   and   gsigma^T edge_embed[eid]   (skinny products,
+    //     fixed-order reduce).  Up to 8 heads and no source-side hub pieces: ONE launch for the walk and the products' partial sums
+    //     (k_gat_atp_src_skinny).
     {
         AtpSrcK p;
         p.rowptr_src = g->rowptr_src; p.slot_by_src = g->slot_by_src; p.Gxs = b->Gxs; p.gxd = b->gxd; p.gsigma = b->g_sigma;
@@ -2429,23 +2493,93 @@ extern "C" int recon_gat_atp_bwd_phase(const recon_graph* g, const recon_gat_atp
         if (hubs && static_cast<size_t>(g->hub_ws_floats) < recon_graph_hub_ws_floats(g, F, R, H)) return RECON_ERR_WORKSPACE;
         p.hub_chunk = hubs ? g->hub_chunk : 0; p.n_piece = hubs ? g->n_piece_src : 0;
         p.piece = reinterpret_cast<const int4*>(g->piece_src); p.hubP = g->hub_ws;
-        dim3 grid(static_cast<unsigned>(ceil_div64(N, kBlock / 64) + ceil_div64(p.n_piece, kBlock / 64)));
-        const int key = s.vec * 10 + s.kr;
-        switch (key) {
-            case 41: hipLaunchKernelGGL((k_gat_atp_src<4, 1>), grid, dim3(kBlock), 0, st, p); break;
-            case 42: hipLaunchKernelGGL((k_gat_atp_src<4, 2>), grid, dim3(kBlock), 0, st, p); break;
-            case 44: hipLaunchKernelGGL((k_gat_atp_src<4, 4>), grid, dim3(kBlock), 0, st, p); break;
-            case 48: hipLaunchKernelGGL((k_gat_atp_src<4, 8>), grid, dim3(kBlock), 0, st, p); break;
-            case 21: hipLaunchKernelGGL((k_gat_atp_src<2, 1>), grid, dim3(kBlock), 0, st, p); break;
-            case 22: hipLaunchKernelGGL((k_gat_atp_src<2, 2>), grid, dim3(kBlock), 0, st, p); break;
-            case 24: hipLaunchKernelGGL((k_gat_atp_src<2, 4>), grid, dim3(kBlock), 0, st, p); break;
-            default: hipLaunchKernelGGL((k_gat_atp_src<2, 8>), grid, dim3(kBlock), 0, st, p); break;
+        const bool want_u = b->g_a || b->g_a_2;
+        if (want_u && !b->g_a) return RECON_ERR_INVALID;                  // g_a_2 is produced together with g_a
+        const size_t lds_src = static_cast<size_t>(skinny_rpb(N)) * H * sizeof(float);
+        const bool share = want_u && H <= 8 && !hubs && lds_src <= kSkinnySrcLdsMax && (!a->io_bf16 || s.vec == 4);
+        const int nsrc = static_cast<int>(ceil_div64(N, kBlock / 64) + ceil_div64(p.n_piece, kBlock / 64));
+        SkinnyJob sj[3];
+        int nb_total = 0;                                                // of the jobs in sj
+        // the launch: the walk alone, or (share) the walk in front of the blocks of sj[0..2]
+        auto launch_src = [&]() -> int {
+            const dim3 grid(static_cast<unsigned>(nsrc + (share ? nb_total : 0)));
+            const SkinnySrc sr{g->rowptr_src, g->slot_by_src, b->g_sigma};
+#define CALL_SRC(V_, K_) do { if (!share) hipLaunchKernelGGL((k_gat_atp_src<V_, K_>), grid, dim3(kBlock), 0, st, p);                                          \
+                              else if (V_ == 4 && a->io_bf16) hipLaunchKernelGGL((k_gat_atp_src_skinny<4, K_, true>), grid, dim3(kBlock), lds_src, st, p, nsrc, sj[0], sj[1], sj[2], sr); \
+                              else hipLaunchKernelGGL((k_gat_atp_src_skinny<V_, K_, false>), grid, dim3(kBlock), lds_src, st, p, nsrc, sj[0], sj[1], sj[2], sr); } while (0)
+            switch (s.vec * 10 + s.kr) {
+                case 41: CALL_SRC(4, 1); break; case 42: CALL_SRC(4, 2); break; case 44: CALL_SRC(4, 4); break; case 48: CALL_SRC(4, 8); break;
+                case 21: CALL_SRC(2, 1); break; case 22: CALL_SRC(2, 2); break; case 24: CALL_SRC(2, 4); break; default: CALL_SRC(2, 8); break;
+            }
+#undef CALL_SRC
+            if (hubs) hipLaunchKernelGGL(k_gat_atp_hub_src, dim3(static_cast<unsigned>(ceil_div64(1LL * g->n_hub_src * ceil_div64(F, 64), kBlock / 64))), dim3(kBlock), 0, st, p,
+                                         g->hub_node_src, g->hub_ptr_src, g->n_hub_src);
+            return RECON_OK;
+        };
+        if (!share) launch_src();
+        if (want_u) {
+            // Each product: out[(j % P)*S1 + (j / P)*S2 + :] = sum_r G[r][j] * X[row(r)][:].  Up to THREE products share one
+            // launch for the partial sums and one for the fixed-order reduce (these kernels are a few MB each and latency
+            // bound: every launch saved is ~5 us); each third of `partial2` serves one product.
+            struct Prod { const float* G; int ldg, nj; const float* X; const int32_t* gather; int rows, K, P; int64_t S1, S2; float* out; };
+            const int32_t* ee_gather = a->ee_index ? a->ee_index : g->eid;
+            const size_t third = recon_gat_atp_bwd_partial2_floats(N, E, F, R, D, H) / 3;
+            auto run_jobs = [&](const Prod* pr, int count) {
+                SkinnyRedJob rj[3];
+                int nj_max = 0, nr_total = 0;
+                nb_total = 0;
+                for (int i = 0; i < 3; ++i) {
+                    sj[i] = SkinnyJob{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 1, 0};
+                    rj[i] = SkinnyRedJob{nullptr, nullptr, 0, 0, 0, 0, 0, 1, 0};
+                    if (i >= count) continue;
+                    const Prod& q = pr[i];
+                    if (q.rows <= 0) {
+                        for (int j = 0; j < q.nj; ++j) (void)hipMemsetAsync(q.out + (j % q.P) * q.S1 + (j / q.P) * q.S2, 0, sizeof(float) * q.K, st);
+                        continue;
+                    }
+                    const int rpb = skinny_rpb(q.rows);
+                    const int nb = static_cast<int>(ceil_div64(q.rows, rpb));
+                    float* part = b->partial2 + i * third;
+                    sj[i] = SkinnyJob{q.G, q.X, q.gather, part, q.ldg, q.nj, q.rows, q.K, rpb, nb};
+                    rj[i] = SkinnyRedJob{part, q.out, q.S1, q.S2, nb, q.nj, q.K, q.P, static_cast<int32_t>(ceil_div64(1LL * q.nj * q.K, 16))};
+                    if (q.nj > nj_max) nj_max = q.nj;
+                    nb_total += nb; nr_total += rj[i].nblocks;
+                }
+                if (share) { launch_src(); if (nb_total == 0) return; }
+                else {
+                    if (nb_total == 0) return;
+                    const dim3 gp(static_cast<unsigned>(nb_total));
+                    if (a->io_bf16) {                                    // (at most 8 heads there: recon_gat_atp_bf16_io_supported)
+                        if (nj_max <= 8) hipLaunchKernelGGL((k_skinny_tn_partial<8, true>), gp, dim3(256), 0, st, sj[0], sj[1], sj[2]);
+                        else hipLaunchKernelGGL((k_skinny_tn_partial<16, true>), gp, dim3(256), 0, st, sj[0], sj[1], sj[2]);
+                    } else if (nj_max <= 8) hipLaunchKernelGGL((k_skinny_tn_partial<8>), gp, dim3(256), 0, st, sj[0], sj[1], sj[2]);
+                    else hipLaunchKernelGGL((k_skinny_tn_partial<16>), gp, dim3(256), 0, st, sj[0], sj[1], sj[2]);
+                }
+                hipLaunchKernelGGL(k_skinny_reduce, dim3(static_cast<unsigned>(nr_total)), dim3(1024), 0, st, rj[0], rj[1], rj[2]);
+            };
+            if (H <= 8) {
+                // the common case, all three in one <8> launch: node-side products (Gs is [N][2H], dst sums | src sums: column
+                // (s, h) lands in g_u[h][s*F ...]) as two H-column jobs, and the edge-side product g_sigma^T edge_embed[eid]
+                const Prod pr[3] = {{b->Gs, 2 * H, H, a->x, rw.row_node, NR, F, H, W, 0, b->g_u},      // destination sums go by row: x through row_node
+                                    {b->Gs + H, 2 * H, H, a->x, nullptr, N, F, H, W, 0, b->g_u + F},
+                                    {b->g_sigma, H, H, a->edge_embed, ee_gather, E, R, H, W, 0, b->g_u + 2 * F}};
+                run_jobs(pr, 3);
+            } else {
+                for (int j = 0; j < 2 * H; ++j) {                        // more than 8 heads: one column at a time keeps the map simple
+                    const Prod one = {b->Gs + j, 2 * H, 1, a->x, j < H ? rw.row_node : nullptr, j < H ? NR : N, F, 1, W, 0,
+                                      b->g_u + static_cast<int64_t>(j % H) * W + (j / H) * F};
+                    run_jobs(&one, 1);
+                }
+                for (int h0 = 0; h0 < H; h0 += 16) {
+                    const int nh = H - h0 < 16 ? H - h0 : 16;
+                    const Prod one = {b->g_sigma + h0, H, nh, a->edge_embed, ee_gather, E, R, nh, W, 0, b->g_u + static_cast<int64_t>(h0) * W + 2 * F};
+                    run_jobs(&one, 1);
+                }
+            }
         }
-        if (hubs) hipLaunchKernelGGL(k_gat_atp_hub_src, dim3(static_cast<unsigned>(ceil_div64(1LL * g->n_hub_src * ceil_div64(F, 64), kBlock / 64))), dim3(kBlock), 0, st, p,
-                                     g->hub_node_src, g->hub_ptr_src, g->n_hub_src);
         RECON_CHECK_LAUNCH();
     }
-    }   // INPUTS (its score-gradient products follow below)
+    }   // INPUTS
     if (b->g_a || b->g_a_2) {
         if (!b->g_a) return RECON_ERR_INVALID;                          // g_a_2 is produced together with g_a
         // (4) g_a[h] = g_h[:, h, :]^T . V[:, h, :], computed as its transpose V^T g_h so that D (<= 208 at cfg 2) is the
@@ -2473,66 +2607,6 @@ extern "C" int recon_gat_atp_bwd_phase(const recon_graph* g, const recon_gat_atp
                 rc = gemm_f32_batched(W, D, NR, A, false, B, false, C, bw, sk, b->partial, st);
             }
             if (rc != RECON_OK) return rc;
-        }
-        // (5) g_u = [Gs_dst | Gs_src]^T x   and   gsigma^T edge_embed[eid]   (skinny products, fixed-order reduce)
-        if (phases & RECON_ATP_BWD_INPUTS) {
-            // Each product: out[(j % P)*S1 + (j / P)*S2 + :] = sum_r G[r][j] * X[row(r)][:].  Up to THREE products share one
-            // launch for the partial sums and one for the fixed-order reduce (these kernels are a few MB each and latency
-            // bound: every launch saved is ~10 us); each third of `partial2` serves one product.
-            struct Prod { const float* G; int ldg, nj; const float* X; const int32_t* gather; int rows, K, P; int64_t S1, S2; float* out; };
-            const int32_t* ee_gather = a->ee_index ? a->ee_index : g->eid;
-            const size_t third = recon_gat_atp_bwd_partial2_floats(N, E, F, R, D, H) / 3;
-            auto run_jobs = [&](const Prod* pr, int count) {
-                SkinnyJob sj[3];
-                SkinnyRedJob rj[3];
-                int nj_max = 0, nb_total = 0, nr_total = 0;
-                for (int i = 0; i < 3; ++i) {
-                    sj[i] = SkinnyJob{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 1, 0};
-                    rj[i] = SkinnyRedJob{nullptr, nullptr, 0, 0, 0, 0, 0, 1, 0};
-                    if (i >= count) continue;
-                    const Prod& q = pr[i];
-                    if (q.rows <= 0) {
-                        for (int j = 0; j < q.nj; ++j) (void)hipMemsetAsync(q.out + (j % q.P) * q.S1 + (j / q.P) * q.S2, 0, sizeof(float) * q.K, st);
-                        continue;
-                    }
-                    int rpb = static_cast<int>(ceil_div64(q.rows, kSkinnySlices));
-                    if (rpb < 32) rpb = 32;                             // >= 8 rows per wave
-                    const int nb = static_cast<int>(ceil_div64(q.rows, rpb));
-                    float* part = b->partial2 + i * third;
-                    sj[i] = SkinnyJob{q.G, q.X, q.gather, part, q.ldg, q.nj, q.rows, q.K, rpb, nb};
-                    rj[i] = SkinnyRedJob{part, q.out, q.S1, q.S2, nb, q.nj, q.K, q.P, static_cast<int32_t>(ceil_div64(1LL * q.nj * q.K, 16))};
-                    if (q.nj > nj_max) nj_max = q.nj;
-                    nb_total += nb; nr_total += rj[i].nblocks;
-                }
-                if (nb_total == 0) return;
-                const dim3 gp(static_cast<unsigned>(nb_total));
-                if (a->io_bf16) {                                        // (at most 8 heads there: recon_gat_atp_bf16_io_supported)
-                    if (nj_max <= 8) hipLaunchKernelGGL((k_skinny_tn_partial<8, true>), gp, dim3(256), 0, st, sj[0], sj[1], sj[2]);
-                    else hipLaunchKernelGGL((k_skinny_tn_partial<16, true>), gp, dim3(256), 0, st, sj[0], sj[1], sj[2]);
-                } else if (nj_max <= 8) hipLaunchKernelGGL((k_skinny_tn_partial<8>), gp, dim3(256), 0, st, sj[0], sj[1], sj[2]);
-                else hipLaunchKernelGGL((k_skinny_tn_partial<16>), gp, dim3(256), 0, st, sj[0], sj[1], sj[2]);
-                hipLaunchKernelGGL(k_skinny_reduce, dim3(static_cast<unsigned>(nr_total)), dim3(1024), 0, st, rj[0], rj[1], rj[2]);
-            };
-            if (H <= 8) {
-                // the common case, all three in one <8> launch: node-side products (Gs is [N][2H], dst sums | src sums: column
-                // (s, h) lands in g_u[h][s*F ...]) as two H-column jobs, and the edge-side product g_sigma^T edge_embed[eid]
-                const Prod pr[3] = {{b->Gs, 2 * H, H, a->x, rw.row_node, NR, F, H, W, 0, b->g_u},      // destination sums go by row: x through row_node
-                                    {b->Gs + H, 2 * H, H, a->x, nullptr, N, F, H, W, 0, b->g_u + F},
-                                    {b->g_sigma, H, H, a->edge_embed, ee_gather, E, R, H, W, 0, b->g_u + 2 * F}};
-                run_jobs(pr, 3);
-            } else {
-                for (int j = 0; j < 2 * H; ++j) {                        // more than 8 heads: one column at a time keeps the map simple
-                    const Prod one = {b->Gs + j, 2 * H, 1, a->x, j < H ? rw.row_node : nullptr, j < H ? NR : N, F, 1, W, 0,
-                                      b->g_u + static_cast<int64_t>(j % H) * W + (j / H) * F};
-                    run_jobs(&one, 1);
-                }
-                for (int h0 = 0; h0 < H; h0 += 16) {
-                    const int nh = H - h0 < 16 ? H - h0 : 16;
-                    const Prod one = {b->g_sigma + h0, H, nh, a->edge_embed, ee_gather, E, R, nh, W, 0, b->g_u + static_cast<int64_t>(h0) * W + 2 * F};
-                    run_jobs(&one, 1);
-                }
-            }
-            RECON_CHECK_LAUNCH();
         }
         // (6) through u = a_2^T a
         if ((phases & RECON_ATP_BWD_FINISH) && hx2 && !(phases & RECON_ATP_BWD_EARLY_SUM)) {
