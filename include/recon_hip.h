@@ -1037,6 +1037,49 @@ int recon_char_masked_bwd(const void* chars, int32_t index_bytes, int64_t ld_cha
                           void* workspace, size_t workspace_bytes, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * E8  The entity-context line LSTM (csrc/ctx_lstm.hip): models/models.py:56-70, one layer, two directions, batch_first, over S
+ *     independent sequences of exactly T steps (no length masking: padding positions are steps like any other), h0 = c0 = 0, nn.LSTM's
+ *     definition (gate order i, f, g, o; both biases added; the reverse direction walks t = T - 1 .. 0).  Only the final states are kept:
+ *         out[s] = (h_fwd after t = T - 1 | h_rev after t = 0),   out [S][2 H].
+ *     The input row of step t is given in two parts and never written: word_table[words[s][t]] (Dw floats; words [S][T] int32 or int64,
+ *     index_bytes = 4 or 8, row stride ld_words in elements, ids outside [0, Vw) clamped into the table; Dw = 0: no such part, words and
+ *     word_table may be NULL) and feat[(s T + t) ld_feat .. + Fc] (read in place, ld_feat >= Fc).  I = Dw + Fc.  w_ih [4H][I], w_hh [4H][H],
+ *     b_ih, b_hh [4H] per direction (the *_rev arguments: the reverse direction's), fp32 and contiguous.  Everything is fp32 on
+ *     v_mfma_f32_16x16x4_f32 (an fp32 fma chain, no reduced-precision operand).  Status codes and the 16-byte alignment of workspace and
+ *     saved are those of the E7 entries.
+ * ------------------------------------------------------------------------------------------*/
+/* Shapes the kernels take (models/models.py:56-70): S, T, Fc >= 1, Dw >= 0, 1 <= H <= 64 (four waves of 16 hidden units), Dw + Fc <= 256,
+ * T <= 2^20, and the weights of one direction (4 H (I + H) floats in the MFMA's operand layout) plus the tiles of 16 sequences within
+ * 144 KiB of LDS; at most 192 16 x 16 tiles in (4 H) x (I + H + 1).  The caller runs the stock ops for anything else. */
+int recon_ctx_lstm_supported(int64_t S, int32_t T, int32_t Dw, int32_t Fc, int32_t H);
+/* Bytes of the workspace (models/models.py:56-70) of the forward (backward = 0: both directions' weights as the B operand, and the
+ * bias sums) or of the backward (backward = 1: one private (d_w_ih | d_w_hh | d_b) per direction and workgroup, at most 128 workgroups,
+ * each owning ceil(S / 128) sequences).  16-byte aligned, any contents; 0 for a shape recon_ctx_lstm_supported refuses. */
+size_t recon_ctx_lstm_workspace_bytes(int64_t S, int32_t T, int32_t Dw, int32_t Fc, int32_t H, int32_t backward);
+/* Bytes of the opaque buffer the forward leaves for the backward (models/models.py:56-70): the post-activation gates and the cell
+ * state, 5 H floats per direction, sequence and step.  0 for a shape recon_ctx_lstm_supported refuses. */
+size_t recon_ctx_lstm_saved_bytes(int64_t S, int32_t T, int32_t Dw, int32_t Fc, int32_t H);
+/* Forward (models/models.py:56-70).  A workgroup owns one direction and walks tiles of 16 sequences with the direction's weights in
+ * LDS; the cell state never leaves registers.  saved = NULL (no backward follows): out is the only thing written.  S == 0: nothing is
+ * launched.  Two launches (operand layout, sequences). */
+int recon_ctx_lstm_fwd(const void* words, int32_t index_bytes, int64_t ld_words, const float* word_table, int32_t Vw, const float* feat,
+                       int64_t ld_feat, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* w_ih_rev,
+                       const float* w_hh_rev, const float* b_ih_rev, const float* b_hh_rev, int64_t S, int32_t T, int32_t Dw, int32_t Fc,
+                       int32_t H, float* out, void* saved, void* workspace, size_t workspace_bytes, recon_stream_t stream);
+/* Backward (models/models.py:56-70) from the forward's saved buffer, which it CONSUMES (the gate gradients and h replace the gates and
+ * c: one backward per forward).  g_out [S][2 H] contiguous.  d_feat [S][T][Fc] and d_word_vec [S][T][Dw] (the gradient of the gathered
+ * rows, for the embedding's own backward) are contiguous; either may be NULL and is then not written.  g_b_ih and g_b_hh receive the same
+ * sums.  No floating-point atomics: a pass per direction walks the steps backwards tile by tile of 16 sequences (the reverse direction's
+ * launch adds its d_x to the forward direction's); then workgroup g adds
+ * d_a^T (x | h | 1) over its own run of ceil(S / 128) sequences and the workgroups are added in index order: bitwise identical from
+ * run to run.  S == 0 writes zeros to the eight parameter gradients and launches no kernel.  Four launches. */
+int recon_ctx_lstm_bwd(const void* words, int32_t index_bytes, int64_t ld_words, const float* word_table, int32_t Vw, const float* feat,
+                       int64_t ld_feat, const float* w_ih, const float* w_hh, const float* w_ih_rev, const float* w_hh_rev, const float* g_out,
+                       void* saved, int64_t S, int32_t T, int32_t Dw, int32_t Fc, int32_t H, float* d_feat, float* d_word_vec, float* g_w_ih,
+                       float* g_w_hh, float* g_b_ih, float* g_b_hh, float* g_w_ih_rev, float* g_w_hh_rev, float* g_b_ih_rev, float* g_b_hh_rev,
+                       void* workspace, size_t workspace_bytes, recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
  *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
  * ------------------------------------------------------------------------------------------*/

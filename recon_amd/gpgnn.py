@@ -11,6 +11,7 @@ import torch.nn.functional as F
 from .propagation import (build_block_adjacency, propagate, propagate_blocks, make_start_embedding, make_start_entity_embeddings, get_head_indices,
                           get_tail_indices)
 from .char_features import char_word_features, draw_packed_keep
+from .context_lstm import context_line_states
 
 
 class GPGNN(nn.Module):
@@ -116,8 +117,9 @@ class CharEmbeddings(nn.Module):
 class EntityEmbedding(nn.Module):
     """Entity attribute context encoder, models/models.py:26-83: every context line of an entity is a word sequence (word
     vectors + char-CNN features) run through an LSTM; the final states of all lines of one entity are convolved and max-pooled
-    over the unmasked lines into one vector per entity.  The char-CNN is `char_word_features` (csrc/char_cnn.hip); the LSTM and the
-    entity-level convolution are stock PyTorch-ROCm ops (MIOpen): this is the encoder in front of the propagation path, not the path.
+    over the unmasked lines into one vector per entity.  The char-CNN is `char_word_features` (csrc/char_cnn.hip), the word gather and
+    the LSTM are `context_line_states` (csrc/ctx_lstm.hip; the stock ops when word_embeddings is not a plain nn.Embedding); the entity-level
+    convolution is a stock PyTorch-ROCm op: this is the encoder in front of the propagation path, not the path.
     Keys: word_embeddings.weight (the caller's table, shared), char_embeddings.embeddings.weight, lstm.*, conv1d.*, conv1d_entity.*.
     packed_char_dropout (default False): draw the char embedding's dropout as packed bits (`CharEmbeddings.draw_packed_keep`), so that
     training batches run the masked char-CNN kernels instead of the op chain.  Same distribution, another random stream than the
@@ -143,15 +145,20 @@ class EntityEmbedding(nn.Module):
         U, lines = words.shape[0], words.shape[1]
         words = words.reshape(U * lines, words.shape[2])
         chars = chars.reshape(U * lines, chars.shape[2])
-        word_vec = self.word_embeddings(words)
+        we = self.word_embeddings
+        plain = type(we) is nn.Embedding and we.max_norm is None and not we.sparse and not we.scale_grad_by_freq
+        word_vec = None if plain else we(words)
         emb = self.char_embeddings
         draw = emb.draw_packed_keep if self.packed_char_dropout else emb.draw_keep
         keep = draw(chars.shape[0], chars.shape[1], emb.embeddings.embedding_dim, chars.device)
         char_feat = char_word_features(chars, emb.embeddings.weight, self.conv1d.weight, self.conv1d.bias, self.word_span, keep=keep,
                                        padding_idx=emb.embeddings.padding_idx)                                              # :57-61
-        _, (h_n, _) = self.lstm(torch.cat((word_vec, char_feat), -1))
-        # last layer, both directions side by side (the reference reshapes to (layers, 2, batch, hidden): bidirectional only)
-        h_n = h_n.view(self.layers, 2, U * lines, self.hidden_dim)[-1].permute(1, 0, 2).reshape(U, lines, 2 * self.hidden_dim)
+        if plain:        # gather, cat, LSTM and the h_n reshape as one op (csrc/ctx_lstm.hip; the stock ops where its kernels do not apply)   # :62-70
+            h_n = context_line_states(self.lstm, char_feat, words, we.weight, padding_idx=we.padding_idx).reshape(U, lines, 2 * self.hidden_dim)
+        else:
+            _, (h_n, _) = self.lstm(torch.cat((word_vec, char_feat), -1))
+            # last layer, both directions side by side (the reference reshapes to (layers, 2, batch, hidden): bidirectional only)
+            h_n = h_n.view(self.layers, 2, U * lines, self.hidden_dim)[-1].permute(1, 0, 2).reshape(U, lines, 2 * self.hidden_dim)
         conv = self.conv1d_entity(h_n.permute(0, 2, 1))
         conv = conv.masked_fill(conv_mask.unsqueeze(1), -float('inf'))
         return conv.max(dim=2).values
