@@ -389,6 +389,35 @@ def ptr(t):
     return t if (t is None or isinstance(t, int)) else t.data_ptr()
 
 
+def workspace(nbytes, device):
+    """Uninitialised scratch for one call of an entry that takes (workspace, workspace_bytes); never empty, so that its pointer is never null."""
+    import torch
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+def rows_in_place(t, inner, max_ld=None):
+    """t as a kernel reads it in place, else a contiguous copy; and its row stride.  In place: unit last stride and rows of `inner` elements
+    that do not overlap ([R, inner]), or ONE row stride over all S T rows ([S, T, inner]); with max_ld, a stride up to it.  A single row's
+    stride is arbitrary: `inner` is given for it."""
+    if t.dim() == 2:
+        ld = t.stride(0) if t.shape[0] > 1 else inner
+        ok = t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) >= inner)
+    else:
+        S, T = t.shape[0], t.shape[1]
+        ld = t.stride(1) if T > 1 else (t.stride(0) if S > 1 else inner)
+        ok = t.stride(2) == 1 and ld >= inner and (S == 1 or T == 1 or t.stride(0) == T * ld)
+    return (t, ld) if ok and (max_ld is None or ld <= max_ld) else (t.contiguous(), inner)
+
+
+def recompute_grads(rerun, inputs, need, g_out, create_graph):
+    """A backward through the stock ops, for when the kernels' own cannot serve (create_graph: the gradient itself must be differentiable).
+    rerun() recomputes the output from `inputs`; returns one gradient per input, None where `need` is false."""
+    import torch
+    with torch.enable_grad():
+        grads = iter(torch.autograd.grad(rerun(), [t for t, n in zip(inputs, need) if n], g_out, create_graph=create_graph))
+    return tuple(next(grads) if n else None for n in need)
+
+
 def ptr_array(tensors):
     """c_void_p array of the tensors' device pointers (None: a null entry); the caller keeps it alive across the launch."""
     arr = (C.c_void_p * len(tensors))()

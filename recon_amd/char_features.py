@@ -16,6 +16,8 @@ Neither writes an [S, Lc, .] tensor; tanh(max) and one position byte per output 
 tensors, another dtype, a shape outside the kernels', `keep` an fp32 [S, Lc, C] tensor, or a backward under create_graph — the call runs
 `_chain`, the op sequence `EntityEmbedding.forward` used to be: value and gradients stay correct.  DESIGN.md section 18.
 """
+import collections
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -35,59 +37,6 @@ def _chain(chars, emb_weight, conv_weight, conv_bias, word_span, keep=None, padd
 def _geometry(chars, emb_weight, conv_weight, word_span):
     (S, Lc), (V, C), (Fo, _, cfs) = chars.shape, emb_weight.shape, conv_weight.shape
     return S, (Lc - (cfs - 1)) // word_span, word_span, cfs, V, C, Fo
-
-
-def _workspace(nbytes, device):
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-
-
-class _CharWordFeatures(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, chars, emb_weight, conv_weight, conv_bias, word_span, padding_idx):
-        E, Wc, b = emb_weight.detach().contiguous(), conv_weight.detach().contiguous(), conv_bias.detach().contiguous()
-        ids = chars if chars.stride(1) == 1 and (chars.shape[0] == 1 or chars.stride(0) >= chars.shape[1]) else chars.contiguous()
-        geo = _geometry(ids, E, Wc, word_span)
-        S, W, Fo = geo[0], geo[1], geo[6]
-        L = _lib.lib()
-        wants = any(ctx.needs_input_grad[1:4])
-        out = torch.empty(S, W, Fo, dtype=torch.float32, device=E.device)
-        arg = torch.empty(S, W, Fo, dtype=torch.uint8, device=E.device) if wants else None
-        ws = _workspace(L.recon_char_features_workspace_bytes(*geo, 0), E.device)
-        ld = ids.stride(0) if S > 1 else ids.shape[1]                       # (a single row's stride is arbitrary)
-        with _lib.on_device(E.device):
-            _lib.check(L.recon_char_features_fwd(ids.data_ptr(), ids.element_size(), ld, E.data_ptr(), Wc.data_ptr(), b.data_ptr(), None, *geo,
-                                                 out.data_ptr(), _lib.ptr(arg), ws.data_ptr(), ws.numel(), _lib.current_stream()),
-                       "recon_char_features_fwd")
-        if wants:
-            ctx.save_for_backward(ids, emb_weight, conv_weight, conv_bias, out, arg)
-            ctx.geo, ctx.ld, ctx.word_span, ctx.padding_idx = geo, ld, word_span, padding_idx
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        ids, emb_weight, conv_weight, conv_bias, out, arg = ctx.saved_tensors
-        need = ctx.needs_input_grad[1:4]
-        if torch.is_grad_enabled():                                          # create_graph: the gradient itself must be differentiable
-            with torch.enable_grad():
-                y = _chain(ids, emb_weight, conv_weight, conv_bias, ctx.word_span, None, ctx.padding_idx)
-                params = [p for p, n in zip((emb_weight, conv_weight, conv_bias), need) if n]
-                grads = list(torch.autograd.grad(y, params, g_out, create_graph=True))
-            return (None,) + tuple(grads.pop(0) if n else None for n in need) + (None, None)
-        geo = ctx.geo
-        cfs, V, C, Fo = geo[3], geo[4], geo[5], geo[6]
-        L = _lib.lib()
-        E, Wc = emb_weight.detach().contiguous(), conv_weight.detach().contiguous()
-        g = g_out.contiguous().to(torch.float32)
-        g_emb = torch.empty(V, C, dtype=torch.float32, device=g.device)
-        g_w = torch.empty(Fo, C, cfs, dtype=torch.float32, device=g.device)
-        g_b = torch.empty(Fo, dtype=torch.float32, device=g.device)
-        ws = _workspace(L.recon_char_features_workspace_bytes(*geo, 1), g.device)
-        pad = -1 if ctx.padding_idx is None else int(ctx.padding_idx)
-        with _lib.on_device(g.device):
-            _lib.check(L.recon_char_features_bwd(ids.data_ptr(), ids.element_size(), ctx.ld, E.data_ptr(), Wc.data_ptr(), None, g.data_ptr(),
-                                                 out.data_ptr(), arg.data_ptr(), *geo, pad, g_emb.data_ptr(), g_w.data_ptr(), g_b.data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), _lib.current_stream()), "recon_char_features_bwd")
-        return None, (g_emb if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None), None, None
 
 
 class PackedKeep:
@@ -191,70 +140,85 @@ def draw_packed_keep(S, Lc, C, p, device, generator=None):
     return PackedKeep(draw_keep_bits(S, Lc, C, keep_threshold(p), seed, offset, device), 1.0 / (1.0 - p), C)
 
 
-class _CharWordFeaturesMasked(torch.autograd.Function):
-    """The masked form (csrc/char_mask.hip): saves ids, parameters, out, the position bytes and the bits — nothing of size S Lc C."""
+# A kernel form of the op: the stem of its C entries (_supported, _workspace_bytes, _fwd, _bwd); how many of the arguments its Function takes
+# behind padding_idx are tensors to save (they come first); what goes where the entries take the mask; the factors `_chain` takes for it.
+_Form = collections.namedtuple("_Form", "stem n_saved call_extra keep")
+_TABLE = _Form("recon_char_features", 0, lambda: (None,), lambda C, dtype: None)                         # csrc/char_cnn.hip
+_MASKED = _Form("recon_char_masked", 1, lambda bits, scale: (bits.data_ptr(), scale),                     # csrc/char_mask.hip
+                lambda C, dtype, bits, scale: PackedKeep(bits, scale, C).factors(dtype))
 
+
+def _forward(form, ctx, chars, emb_weight, conv_weight, conv_bias, word_span, padding_idx, *extra):
+    """Saves ids, parameters, out, the position bytes and the form's tensors (the masked form's bits) — nothing of size S Lc C."""
+    E, Wc, b = emb_weight.detach().contiguous(), conv_weight.detach().contiguous(), conv_bias.detach().contiguous()
+    ids, ld = _lib.rows_in_place(chars, chars.shape[1])
+    geo = _geometry(ids, E, Wc, word_span)
+    S, W, Fo = geo[0], geo[1], geo[6]
+    L = _lib.lib()
+    wants = any(ctx.needs_input_grad[1:4])
+    out = torch.empty(S, W, Fo, dtype=torch.float32, device=E.device)
+    arg = torch.empty(S, W, Fo, dtype=torch.uint8, device=E.device) if wants else None
+    ws = _lib.workspace(getattr(L, form.stem + "_workspace_bytes")(*geo, 0), E.device)
+    with _lib.on_device(E.device):
+        _lib.check(getattr(L, form.stem + "_fwd")(ids.data_ptr(), ids.element_size(), ld, E.data_ptr(), Wc.data_ptr(), b.data_ptr(),
+                                                  *form.call_extra(*extra), *geo, out.data_ptr(), _lib.ptr(arg), ws.data_ptr(), ws.numel(),
+                                                  _lib.current_stream()), form.stem + "_fwd")
+    if wants:
+        ctx.save_for_backward(ids, emb_weight, conv_weight, conv_bias, out, arg, *extra[:form.n_saved])
+        ctx.geo, ctx.ld, ctx.word_span, ctx.padding_idx, ctx.plain = geo, ld, word_span, padding_idx, extra[form.n_saved:]
+    return out
+
+
+def _backward(form, ctx, g_out):
+    ids, emb_weight, conv_weight, conv_bias, out, arg, *extra = ctx.saved_tensors
+    extra = tuple(extra) + ctx.plain
+    need = ctx.needs_input_grad[1:4]
+    geo = ctx.geo
+    cfs, V, C, Fo = geo[3], geo[4], geo[5], geo[6]
+    if torch.is_grad_enabled():                                              # create_graph: the gradient itself must be differentiable
+        grads = _lib.recompute_grads(lambda: _chain(ids, emb_weight, conv_weight, conv_bias, ctx.word_span,
+                                                    form.keep(C, emb_weight.dtype, *extra), ctx.padding_idx),
+                                     (emb_weight, conv_weight, conv_bias), need, g_out, True)
+        return (None,) + grads + (None,) * (2 + len(extra))
+    L = _lib.lib()
+    E, Wc = emb_weight.detach().contiguous(), conv_weight.detach().contiguous()
+    g = g_out.contiguous().to(torch.float32)
+    g_emb = torch.empty(V, C, dtype=torch.float32, device=g.device)
+    g_w = torch.empty(Fo, C, cfs, dtype=torch.float32, device=g.device)
+    g_b = torch.empty(Fo, dtype=torch.float32, device=g.device)
+    ws = _lib.workspace(getattr(L, form.stem + "_workspace_bytes")(*geo, 1), g.device)
+    pad = -1 if ctx.padding_idx is None else int(ctx.padding_idx)
+    with _lib.on_device(g.device):
+        _lib.check(getattr(L, form.stem + "_bwd")(ids.data_ptr(), ids.element_size(), ctx.ld, E.data_ptr(), Wc.data_ptr(), *form.call_extra(*extra),
+                                                  g.data_ptr(), out.data_ptr(), arg.data_ptr(), *geo, pad, g_emb.data_ptr(), g_w.data_ptr(),
+                                                  g_b.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream()), form.stem + "_bwd")
+    return (None, (g_emb if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None)) + (None,) * (2 + len(extra))
+
+
+class _CharWordFeatures(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, chars, emb_weight, conv_weight, conv_bias, word_span, padding_idx, bits, scale):
-        E, Wc, b = emb_weight.detach().contiguous(), conv_weight.detach().contiguous(), conv_bias.detach().contiguous()
-        ids = chars if chars.stride(1) == 1 and (chars.shape[0] == 1 or chars.stride(0) >= chars.shape[1]) else chars.contiguous()
-        geo = _geometry(ids, E, Wc, word_span)
-        S, W, Fo = geo[0], geo[1], geo[6]
-        L = _lib.lib()
-        wants = any(ctx.needs_input_grad[1:4])
-        out = torch.empty(S, W, Fo, dtype=torch.float32, device=E.device)
-        arg = torch.empty(S, W, Fo, dtype=torch.uint8, device=E.device) if wants else None
-        ws = _workspace(L.recon_char_masked_workspace_bytes(*geo, 0), E.device)
-        ld = ids.stride(0) if S > 1 else ids.shape[1]
-        with _lib.on_device(E.device):
-            _lib.check(L.recon_char_masked_fwd(ids.data_ptr(), ids.element_size(), ld, E.data_ptr(), Wc.data_ptr(), b.data_ptr(), bits.data_ptr(),
-                                               scale, *geo, out.data_ptr(), _lib.ptr(arg), ws.data_ptr(), ws.numel(), _lib.current_stream()),
-                       "recon_char_masked_fwd")
-        if wants:
-            ctx.save_for_backward(ids, emb_weight, conv_weight, conv_bias, out, arg, bits)
-            ctx.geo, ctx.ld, ctx.word_span, ctx.padding_idx, ctx.scale = geo, ld, word_span, padding_idx, scale
-        return out
+    def forward(ctx, chars, emb_weight, conv_weight, conv_bias, word_span, padding_idx):
+        return _forward(_TABLE, ctx, chars, emb_weight, conv_weight, conv_bias, word_span, padding_idx)
 
     @staticmethod
     def backward(ctx, g_out):
-        ids, emb_weight, conv_weight, conv_bias, out, arg, bits = ctx.saved_tensors
-        need = ctx.needs_input_grad[1:4]
-        geo = ctx.geo
-        cfs, V, C, Fo = geo[3], geo[4], geo[5], geo[6]
-        if torch.is_grad_enabled():                                          # create_graph: the gradient itself must be differentiable
-            with torch.enable_grad():
-                keep = PackedKeep(bits, ctx.scale, C).factors(emb_weight.dtype)
-                y = _chain(ids, emb_weight, conv_weight, conv_bias, ctx.word_span, keep, ctx.padding_idx)
-                params = [p for p, n in zip((emb_weight, conv_weight, conv_bias), need) if n]
-                grads = list(torch.autograd.grad(y, params, g_out, create_graph=True))
-            return (None,) + tuple(grads.pop(0) if n else None for n in need) + (None, None, None, None)
-        L = _lib.lib()
-        E, Wc = emb_weight.detach().contiguous(), conv_weight.detach().contiguous()
-        g = g_out.contiguous().to(torch.float32)
-        g_emb = torch.empty(V, C, dtype=torch.float32, device=g.device)
-        g_w = torch.empty(Fo, C, cfs, dtype=torch.float32, device=g.device)
-        g_b = torch.empty(Fo, dtype=torch.float32, device=g.device)
-        ws = _workspace(L.recon_char_masked_workspace_bytes(*geo, 1), g.device)
-        pad = -1 if ctx.padding_idx is None else int(ctx.padding_idx)
-        with _lib.on_device(g.device):
-            _lib.check(L.recon_char_masked_bwd(ids.data_ptr(), ids.element_size(), ctx.ld, E.data_ptr(), Wc.data_ptr(), bits.data_ptr(), ctx.scale,
-                                               g.data_ptr(), out.data_ptr(), arg.data_ptr(), *geo, pad, g_emb.data_ptr(), g_w.data_ptr(),
-                                               g_b.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream()), "recon_char_masked_bwd")
-        return None, (g_emb if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None), None, None, None, None
+        return _backward(_TABLE, ctx, g_out)
 
 
-def _masked(chars, emb_weight, conv_weight, conv_bias, word_span):
+class _CharWordFeaturesMasked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, chars, emb_weight, conv_weight, conv_bias, word_span, padding_idx, bits, scale):
+        return _forward(_MASKED, ctx, chars, emb_weight, conv_weight, conv_bias, word_span, padding_idx, bits, scale)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        return _backward(_MASKED, ctx, g_out)
+
+
+def _runs(form, chars, emb_weight, conv_weight, conv_bias, word_span):
     if not chars.is_cuda or not (emb_weight.dtype == conv_weight.dtype == conv_bias.dtype == torch.float32):
         return False
-    return bool(_lib.lib().recon_char_masked_supported(*_geometry(chars, emb_weight, conv_weight, word_span)))
-
-
-def _fused(chars, emb_weight, conv_weight, conv_bias, word_span, keep):
-    if keep is not None or not chars.is_cuda:
-        return False
-    if not (emb_weight.dtype == conv_weight.dtype == conv_bias.dtype == torch.float32):
-        return False
-    return bool(_lib.lib().recon_char_features_supported(*_geometry(chars, emb_weight, conv_weight, word_span)))
+    return bool(getattr(_lib.lib(), form.stem + "_supported")(*_geometry(chars, emb_weight, conv_weight, word_span)))
 
 
 def char_word_features(chars, emb_weight, conv_weight, conv_bias, word_span, keep=None, padding_idx=0):
@@ -292,9 +256,9 @@ def char_word_features(chars, emb_weight, conv_weight, conv_bias, word_span, kee
     if chars.shape[0] == 0:
         return torch.empty(0, W, conv_weight.shape[0], dtype=emb_weight.dtype, device=emb_weight.device)
     if packed:
-        if _masked(chars, emb_weight, conv_weight, conv_bias, word_span):
+        if _runs(_MASKED, chars, emb_weight, conv_weight, conv_bias, word_span):
             return _CharWordFeaturesMasked.apply(chars, emb_weight, conv_weight, conv_bias, word_span, padding_idx, keep.bits, keep.scale)
         keep = keep.factors(emb_weight.dtype)
-    if _fused(chars, emb_weight, conv_weight, conv_bias, word_span, keep):
+    if keep is None and _runs(_TABLE, chars, emb_weight, conv_weight, conv_bias, word_span):
         return _CharWordFeatures.apply(chars, emb_weight, conv_weight, conv_bias, word_span, padding_idx)
     return _chain(chars, emb_weight, conv_weight, conv_bias, word_span, keep, padding_idx)

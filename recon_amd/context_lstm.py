@@ -35,40 +35,25 @@ def _chain(lstm, feat, words=None, word_table=None, padding_idx=None):
     return h_n.permute(1, 0, 2).reshape(x.shape[0], -1)
 
 
-def _workspace(nbytes, device):
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-
-
-def _rows(t, inner):
-    """t as it can be read in place ([S, inner] rows or [S, T, inner] with one row stride), else a contiguous copy; and the row stride."""
-    if t.dim() == 2:
-        ok = t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) >= inner)
-        return (t, t.stride(0) if t.shape[0] > 1 else inner) if ok else (t.contiguous(), inner)
-    S, T = t.shape[0], t.shape[1]
-    ld = t.stride(1) if T > 1 else (t.stride(0) if S > 1 else inner)
-    ok = t.stride(2) == 1 and ld >= inner and (S == 1 or T == 1 or t.stride(0) == T * ld)
-    return (t, ld) if ok else (t.contiguous(), inner)
-
-
 class _ContextLineStates(torch.autograd.Function):
     """csrc/ctx_lstm.hip: saves the ids, references to the inputs, out and the saved-state buffer — nothing of size S T I."""
 
     @staticmethod
     def forward(ctx, lstm, padding_idx, wants, feat, words, word_table, *params):
         L = _lib.lib()
-        x, ld_feat = _rows(feat.detach(), feat.shape[2])
+        x, ld_feat = _lib.rows_in_place(feat.detach(), feat.shape[2])
         S, T, Fc = x.shape
         H = params[1].shape[1]
         Dw = 0 if words is None else word_table.shape[1]
         ids, ld_words, table = None, 0, None
         if words is not None:
-            ids, ld_words = _rows(words, T)
+            ids, ld_words = _lib.rows_in_place(words, T)
             table = word_table.detach().contiguous()
         p = [q.detach().contiguous() for q in params]
         geo = (S, T, Dw, Fc, H)
         out = torch.empty(S, 2 * H, dtype=torch.float32, device=x.device)
         saved = torch.empty(L.recon_ctx_lstm_saved_bytes(*geo), dtype=torch.uint8, device=x.device) if wants else None
-        ws = _workspace(L.recon_ctx_lstm_workspace_bytes(*geo, 0), x.device)
+        ws = _lib.workspace(L.recon_ctx_lstm_workspace_bytes(*geo, 0), x.device)
         with _lib.on_device(x.device):
             _lib.check(L.recon_ctx_lstm_fwd(_lib.ptr(ids), ids.element_size() if ids is not None else 8, ld_words, _lib.ptr(table),
                                             table.shape[0] if table is not None else 0, x.data_ptr(), ld_feat, *[q.data_ptr() for q in p],
@@ -88,20 +73,17 @@ class _ContextLineStates(torch.autograd.Function):
             # create_graph (the gradient itself must be differentiable; MIOpen's RNN backward is not) or a second backward over a retained
             # graph (the first consumed the saved state): recompute through the stock ops, the native ones, which differentiate twice and
             # run a backward in eval mode too
-            twice = torch.is_grad_enabled()
-            with torch.enable_grad(), torch.backends.cudnn.flags(enabled=False):
-                safe = None if ids is None else ids.clamp(0, word_table.shape[0] - 1)           # as the kernels clamp them
-                y = _chain(ctx.lstm, feat, safe, word_table, ctx.padding_idx)
-                wanted = [t for t, n in zip((feat, None, word_table) + tuple(params), need[3:]) if n]
-                grads = list(torch.autograd.grad(y, wanted, g_out, create_graph=twice))
-            return (None, None, None) + tuple(grads.pop(0) if n else None for n in need[3:])
+            safe = None if ids is None else ids.clamp(0, word_table.shape[0] - 1)               # as the kernels clamp them
+            with torch.backends.cudnn.flags(enabled=False):
+                return (None, None, None) + _lib.recompute_grads(lambda: _chain(ctx.lstm, feat, safe, word_table, ctx.padding_idx),
+                                                                 (feat, None, word_table) + tuple(params), need[3:], g_out, torch.is_grad_enabled())
         ctx.consumed = True
         L = _lib.lib()
-        x, ld_feat = _rows(feat.detach(), Fc)
+        x, ld_feat = _lib.rows_in_place(feat.detach(), Fc)
         ld_words = 0
         table = None
         if ids is not None:
-            ids, ld_words = _rows(ids, T)
+            ids, ld_words = _lib.rows_in_place(ids, T)
             table = word_table.detach().contiguous()
         p = [q.detach().contiguous() for q in params]
         g = g_out.contiguous().to(torch.float32)
@@ -109,7 +91,7 @@ class _ContextLineStates(torch.autograd.Function):
         d_feat = torch.empty(S, T, Fc, dtype=torch.float32, device=dev) if need[3] else None
         d_wv = torch.empty(S, T, Dw, dtype=torch.float32, device=dev) if (ids is not None and need[5]) else None
         gp = [torch.empty_like(q) for q in p]
-        ws = _workspace(L.recon_ctx_lstm_workspace_bytes(*ctx.geo, 1), dev)
+        ws = _lib.workspace(L.recon_ctx_lstm_workspace_bytes(*ctx.geo, 1), dev)
         with _lib.on_device(dev):
             _lib.check(L.recon_ctx_lstm_bwd(_lib.ptr(ids), ids.element_size() if ids is not None else 8, ld_words, _lib.ptr(table),
                                             table.shape[0] if table is not None else 0, x.data_ptr(), ld_feat, p[0].data_ptr(), p[1].data_ptr(),

@@ -17,7 +17,7 @@
 //   words in order.  k_char_reduce adds the slabs in workgroup order; k_char_param_grads forms dE = sum_k dT[k] . W[:, :, k] (padding row
 //   zero) and dW[:, :, k] = dT[k]^T . E.  Every sum has one order: bitwise identical from run to run.
 #include <math.h>
-#include "recon_common.h"
+#include "ctx_enc_common.h"
 
 namespace recon {
 namespace {
@@ -27,8 +27,6 @@ constexpr int kCcMaxTaps = 16;
 constexpr int kCcLdsBytes = 144 * 1024;       // tables / private dT up to this size live in LDS
 constexpr int kCcBwdBatch = 8;                // words whose loads are in flight together in the backward
 constexpr int64_t kCcMaxTable = 1 << 22;      // cfs V Fo floats
-
-__host__ __device__ inline int64_t cc_min64(int64_t a, int64_t b) { return a < b ? a : b; }
 
 __global__ void __launch_bounds__(256) k_char_tables(const float* __restrict__ E, const float* __restrict__ Wc, int32_t cfs, int32_t V, int32_t C,
                                                      int32_t Fo, float* __restrict__ T) {
@@ -40,14 +38,6 @@ __global__ void __launch_bounds__(256) k_char_tables(const float* __restrict__ E
     float acc = 0.f;
     for (int c = 0; c < C; ++c) acc = fmaf(e[c], w[static_cast<int64_t>(c) * cfs], acc);
     T[i] = acc;
-}
-
-// id j of the word at `cp` in lane j (j < n), clamped into the table: an id outside [0, V) is the caller's error, never an access outside
-template <typename IdT>
-__device__ __forceinline__ int word_ids(const IdT* cp, int lane, int n, int V) {
-    int64_t v = 0;
-    if (lane < n) v = static_cast<int64_t>(cp[lane]);
-    return static_cast<int>(v < 0 ? 0 : (v >= V ? V - 1 : v));
 }
 
 template <bool LDS, typename IdT>
@@ -108,7 +98,7 @@ __global__ void __launch_bounds__(256) k_char_table_bwd(const IdT* __restrict__ 
         acc = cc_lds;
     }
     const int n_ids = span + cfs - 1;
-    const int64_t w0 = static_cast<int64_t>(blockIdx.x) * words_per_wg, w1 = cc_min64(w0 + words_per_wg, n_words);
+    const int64_t w0 = static_cast<int64_t>(blockIdx.x) * words_per_wg, w1 = min64(w0 + words_per_wg, n_words);
     for (int ob = 0; ob < Fo; ob += 64) {
         const bool live = ob + lane < Fo;
         const int o = live ? ob + lane : Fo - 1;
@@ -118,7 +108,7 @@ __global__ void __launch_bounds__(256) k_char_table_bwd(const IdT* __restrict__ 
             int ts[kCcBwdBatch], idv[kCcBwdBatch];
 #pragma unroll
             for (int u = 0; u < kCcBwdBatch; ++u) {                       // every load of the batch is issued before the first use
-                const int64_t word = cc_min64(wb + u, w1 - 1);
+                const int64_t word = min64(wb + u, w1 - 1);
                 const int64_t s = word / W;
                 const int w = static_cast<int>(word - s * W);
                 idv[u] = word_ids(chars + s * ld_chars + static_cast<int64_t>(w) * span, lane, n_ids, V);
@@ -185,19 +175,10 @@ __global__ void __launch_bounds__(256) k_char_param_grads(const float* __restric
 
 inline int64_t cc_table_floats(int32_t cfs, int32_t V, int32_t Fo) { return static_cast<int64_t>(cfs) * V * Fo; }
 
-// workgroups of the backward and the words each owns: a function of the shape alone (the summation order must not change between runs)
+// workgroups of the backward and the words each owns
 inline void cc_bwd_split(int64_t n_words, int64_t table_bytes, int64_t* words_per_wg, int32_t* G) {
     const int64_t max_wg = 2 * table_bytes <= 160 * 1024 ? 512 : 256;    // two workgroups per CU while two private dT fit in its LDS
-    int64_t per = ceil_div64(n_words, max_wg);
-    if (per < 2 * kCcBwdBatch) per = 2 * kCcBwdBatch;
-    *words_per_wg = per;
-    *G = static_cast<int32_t>(ceil_div64(n_words, per));
-}
-
-template <typename K>
-bool cc_allow_lds(K kern, size_t lds) {
-    return lds <= 48 * 1024 ||
-           hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) == hipSuccess;
+    split_rows(n_words, max_wg, 2 * kCcBwdBatch, words_per_wg, G);
 }
 
 template <bool LDS, typename IdT>
@@ -205,8 +186,8 @@ int cc_launch_fwd(const void* chars, int64_t ld_chars, const float* T, const flo
                   int32_t V, int32_t Fo, float* out, uint8_t* arg, hipStream_t st) {
     const size_t lds = LDS ? static_cast<size_t>(cc_table_floats(cfs, V, Fo)) * 4 : 0;
     auto kern = &k_char_table_fwd<LDS, IdT>;
-    if (!cc_allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
-    const int64_t blocks = LDS ? cc_min64(ceil_div64(n_words, 32), 512) : cc_min64(ceil_div64(n_words, 4), 4096);
+    if (!allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
+    const int64_t blocks = LDS ? min64(ceil_div64(n_words, 32), 512) : min64(ceil_div64(n_words, 4), 4096);
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(256), lds, st, static_cast<const IdT*>(chars), ld_chars, T, bias, n_words, W,
                        span, cfs, V, Fo, out, arg);
     return RECON_OK;
@@ -217,7 +198,7 @@ int cc_launch_bwd(const void* chars, int64_t ld_chars, const float* g_out, const
                   int64_t words_per_wg, int32_t G, int32_t W, int32_t span, int32_t cfs, int32_t V, int32_t Fo, float* partial, hipStream_t st) {
     const size_t lds = LDS ? static_cast<size_t>(cc_table_floats(cfs, V, Fo)) * 4 : 0;
     auto kern = &k_char_table_bwd<LDS, IdT>;
-    if (!cc_allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
+    if (!allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
     const int waves = cfs < 4 ? cfs : 4;
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(G)), dim3(64 * waves), lds, st, static_cast<const IdT*>(chars), ld_chars, g_out, out, arg,
                        n_words, words_per_wg, W, span, cfs, V, Fo, partial);
@@ -253,23 +234,18 @@ extern "C" int recon_char_features_fwd(const void* chars, int32_t index_bytes, i
     if (S == 0) return RECON_OK;
     if (!recon_char_features_supported(S, W, span, cfs, V, C, Fo)) return RECON_ERR_UNSUPPORTED;
     if (keep) return RECON_ERR_UNSUPPORTED;                             // the masked (direct) form is not built: the caller runs the op chain
-    if (!chars || !emb || !conv_w || !conv_b || !out || !workspace || ld_chars < cfs - 1 + static_cast<int64_t>(W) * span) return RECON_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(workspace) % 16) return RECON_ERR_INVALID;
-    if (workspace_bytes < recon_char_features_workspace_bytes(S, W, span, cfs, V, C, Fo, 0)) return RECON_ERR_WORKSPACE;
+    if (const int bad = recon::char_io_checks(chars && emb && conv_w && conv_b && out && workspace, ld_chars, W, span, cfs, workspace, workspace_bytes,
+                                              recon_char_features_workspace_bytes(S, W, span, cfs, V, C, Fo, 0))) return bad;
     hipStream_t st = as_stream(stream);
     const int64_t n = recon::cc_table_floats(cfs, V, Fo), n_words = S * W;
     float* T = static_cast<float*>(workspace);
     hipLaunchKernelGGL(recon::k_char_tables, dim3(static_cast<unsigned>(ceil_div64(n, 256))), dim3(256), 0, st, emb, conv_w, cfs, V, C, Fo, T);
     RECON_CHECK_LAUNCH();
     const bool lds = n * 4 <= recon::kCcLdsBytes;
-    int rc;
-    if (index_bytes == 8) {
-        rc = lds ? recon::cc_launch_fwd<true, int64_t>(chars, ld_chars, T, conv_b, n_words, W, span, cfs, V, Fo, out, arg_pos, st)
-                 : recon::cc_launch_fwd<false, int64_t>(chars, ld_chars, T, conv_b, n_words, W, span, cfs, V, Fo, out, arg_pos, st);
-    } else {
-        rc = lds ? recon::cc_launch_fwd<true, int32_t>(chars, ld_chars, T, conv_b, n_words, W, span, cfs, V, Fo, out, arg_pos, st)
-                 : recon::cc_launch_fwd<false, int32_t>(chars, ld_chars, T, conv_b, n_words, W, span, cfs, V, Fo, out, arg_pos, st);
-    }
+    const int rc = recon::dispatch_lds_ids(index_bytes, lds, [&](auto in_lds, auto id) {
+        return recon::cc_launch_fwd<decltype(in_lds)::value, typename decltype(id)::type>(chars, ld_chars, T, conv_b, n_words, W, span, cfs, V, Fo, out,
+                                                                                          arg_pos, st);
+    });
     if (rc != RECON_OK) return rc;
     RECON_CHECK_LAUNCH();
     return RECON_OK;
@@ -284,15 +260,10 @@ extern "C" int recon_char_features_bwd(const void* chars, int32_t index_bytes, i
     if (keep) return RECON_ERR_UNSUPPORTED;
     if (!g_emb || !g_conv_w || !g_conv_b) return RECON_ERR_INVALID;
     hipStream_t st = as_stream(stream);
-    if (S == 0) {
-        if (hipMemsetAsync(g_emb, 0, static_cast<size_t>(V) * C * 4, st) != hipSuccess ||
-            hipMemsetAsync(g_conv_w, 0, static_cast<size_t>(Fo) * C * cfs * 4, st) != hipSuccess ||
-            hipMemsetAsync(g_conv_b, 0, static_cast<size_t>(Fo) * 4, st) != hipSuccess) return RECON_ERR_LAUNCH;
-        return RECON_OK;
-    }
-    if (!chars || !emb || !conv_w || !g_out || !out || !arg_pos || !workspace || ld_chars < cfs - 1 + static_cast<int64_t>(W) * span) return RECON_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(workspace) % 16) return RECON_ERR_INVALID;
-    if (workspace_bytes < recon_char_features_workspace_bytes(S, W, span, cfs, V, C, Fo, 1)) return RECON_ERR_WORKSPACE;
+    if (S == 0)
+        return recon::zero_fill({{g_emb, static_cast<size_t>(V) * C}, {g_conv_w, static_cast<size_t>(Fo) * C * cfs}, {g_conv_b, static_cast<size_t>(Fo)}}, st);
+    if (const int bad = recon::char_io_checks(chars && emb && conv_w && g_out && out && arg_pos && workspace, ld_chars, W, span, cfs, workspace,
+                                              workspace_bytes, recon_char_features_workspace_bytes(S, W, span, cfs, V, C, Fo, 1))) return bad;
     const int64_t n = recon::cc_table_floats(cfs, V, Fo), n_words = S * W;
     int64_t per;
     int32_t G;
@@ -301,14 +272,10 @@ extern "C" int recon_char_features_bwd(const void* chars, int32_t index_bytes, i
     float* dT = partial + static_cast<int64_t>(G) * (n + Fo);
     const bool lds = n * 4 <= recon::kCcLdsBytes;
     if (!lds && hipMemsetAsync(partial, 0, static_cast<size_t>(G) * (n + Fo) * 4, st) != hipSuccess) return RECON_ERR_LAUNCH;
-    int rc;
-    if (index_bytes == 8) {
-        rc = lds ? recon::cc_launch_bwd<true, int64_t>(chars, ld_chars, g_out, out, arg_pos, n_words, per, G, W, span, cfs, V, Fo, partial, st)
-                 : recon::cc_launch_bwd<false, int64_t>(chars, ld_chars, g_out, out, arg_pos, n_words, per, G, W, span, cfs, V, Fo, partial, st);
-    } else {
-        rc = lds ? recon::cc_launch_bwd<true, int32_t>(chars, ld_chars, g_out, out, arg_pos, n_words, per, G, W, span, cfs, V, Fo, partial, st)
-                 : recon::cc_launch_bwd<false, int32_t>(chars, ld_chars, g_out, out, arg_pos, n_words, per, G, W, span, cfs, V, Fo, partial, st);
-    }
+    const int rc = recon::dispatch_lds_ids(index_bytes, lds, [&](auto in_lds, auto id) {
+        return recon::cc_launch_bwd<decltype(in_lds)::value, typename decltype(id)::type>(chars, ld_chars, g_out, out, arg_pos, n_words, per, G, W, span, cfs,
+                                                                                          V, Fo, partial, st);
+    });
     if (rc != RECON_OK) return rc;
     RECON_CHECK_LAUNCH();
     hipLaunchKernelGGL(recon::k_char_reduce, dim3(static_cast<unsigned>(ceil_div64(n + Fo, 256))), dim3(256), 0, st, partial, G, static_cast<int32_t>(n), Fo,

@@ -21,7 +21,7 @@
 //   rows of a word can hold the same id).  The next word's ids, bits, g_out, out and positions are loaded before the current word's
 //   arithmetic.  k_char_masked_reduce adds the slabs in workgroup order and writes g_conv_w in its [Fo][C][cfs] layout.
 #include <math.h>
-#include "recon_common.h"
+#include "ctx_enc_common.h"
 
 namespace recon {
 namespace {
@@ -33,10 +33,6 @@ constexpr int kCmLdsBytes = 144 * 1024;
 constexpr int64_t kCmMaxSlab = 1 << 22;        // floats of one private accumulator set
 constexpr int kCmBwdMinWords = 16;
 constexpr int kCmBwdMaxWg = 256;
-
-typedef float cm_f32x4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ inline int64_t cm_min64(int64_t a, int64_t b) { return a < b ? a : b; }
 
 struct CmFwdGeo { int32_t Kp, FoP, pitch, n_pt, xs_floats; };
 inline CmFwdGeo cm_fwd_geo(int32_t span, int32_t cfs, int32_t C, int32_t Fo) {
@@ -50,12 +46,6 @@ inline CmFwdGeo cm_fwd_geo(int32_t span, int32_t cfs, int32_t C, int32_t Fo) {
 }
 inline int64_t cm_slab_floats(int32_t cfs, int32_t V, int32_t C, int32_t Fo) {
     return static_cast<int64_t>(V) * C + static_cast<int64_t>(Fo) * cfs * C + Fo;
-}
-inline void cm_bwd_split(int64_t n_words, int64_t* words_per_wg, int32_t* G) {
-    int64_t per = ceil_div64(n_words, kCmBwdMaxWg);
-    if (per < kCmBwdMinWords) per = kCmBwdMinWords;
-    *words_per_wg = per;
-    *G = static_cast<int32_t>(ceil_div64(n_words, per));
 }
 // floats of LDS the backward needs beside the accumulators: Xs, the summed dX, four partial dX tiles, d_pre and positions of a word
 inline int64_t cm_bwd_small_floats(int32_t span, int32_t cfs, int32_t C, int32_t Fo) {
@@ -92,14 +82,6 @@ __global__ void __launch_bounds__(256) k_keep_bits_draw(uint32_t* __restrict__ b
         }
         bits[q * KW + kw] = word;
     }
-}
-
-// id j of the word at `cp` in lane j (j < n), clamped into the table
-template <typename IdT>
-__device__ __forceinline__ int cm_word_ids(const IdT* cp, int lane, int n, int V) {
-    int64_t v = 0;
-    if (lane < n) v = static_cast<int64_t>(cp[lane]);
-    return static_cast<int>(v < 0 ? 0 : (v >= V ? V - 1 : v));
 }
 
 __global__ void __launch_bounds__(256) k_char_masked_prep(const float* __restrict__ Wc, int32_t cfs, int32_t C, int32_t Fo, int32_t Kp,
@@ -146,7 +128,7 @@ __global__ void __launch_bounds__(512) k_char_masked_fwd(const IdT* __restrict__
     auto fetch = [&](int64_t word) {                                            // ids and bit words of a word: row j in lane j
         const int64_t s = word / W;
         const int w = static_cast<int>(word - s * W);
-        idv_n = cm_word_ids(chars + s * ld_chars + static_cast<int64_t>(w) * span, lane, n_ids, V);
+        idv_n = word_ids(chars + s * ld_chars + static_cast<int64_t>(w) * span, lane, n_ids, V);
         const int64_t pos = s * Lc + static_cast<int64_t>(w) * span + (lane < n_ids ? lane : 0);
         bw0_n = bits[pos * KW];
         bw1_n = bits[pos * KW + KW - 1];
@@ -186,9 +168,9 @@ __global__ void __launch_bounds__(512) k_char_masked_fwd(const IdT* __restrict__
                 bsv[q] = bias[min(co[q] + col, Fo - 1)];
             }
             for (int pt = 0; pt < n_pt; ++pt) {
-                cm_f32x4 acc[4];
+                enc_f32x4 acc[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = cm_f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int q = 0; q < 4; ++q) acc[q] = enc_f32x4{0.f, 0.f, 0.f, 0.f};
                 const float* ap = xs + (pt * 16 + col) * C + grp;
                 const float* bq = wr + grp * pitch + col;
                 int kk = 0;
@@ -276,7 +258,7 @@ __global__ void __launch_bounds__(256) k_char_masked_bwd(const IdT* __restrict__
         emb = e_;
     }
     __syncthreads();
-    const int64_t w0 = static_cast<int64_t>(blockIdx.x) * words_per_wg, w1 = cm_min64(w0 + words_per_wg, n_words);
+    const int64_t w0 = static_cast<int64_t>(blockIdx.x) * words_per_wg, w1 = min64(w0 + words_per_wg, n_words);
     float db = 0.f;
     int idv_n = 0;
     uint32_t bw0_n = 0, bw1_n = 0;
@@ -285,7 +267,7 @@ __global__ void __launch_bounds__(256) k_char_masked_bwd(const IdT* __restrict__
     auto fetch = [&](int64_t word) {
         const int64_t s = word / W;
         const int w = static_cast<int>(word - s * W);
-        idv_n = cm_word_ids(chars + s * ld_chars + static_cast<int64_t>(w) * span, lane, n_ids, V);
+        idv_n = word_ids(chars + s * ld_chars + static_cast<int64_t>(w) * span, lane, n_ids, V);
         const int64_t pos = s * Lc + static_cast<int64_t>(w) * span + (lane < n_ids ? lane : 0);
         bw0_n = bits[pos * KW];
         bw1_n = bits[pos * KW + KW - 1];
@@ -368,20 +350,14 @@ __global__ void __launch_bounds__(256) k_char_masked_reduce(const float* __restr
     }
 }
 
-template <typename K>
-bool cm_allow_lds(K kern, size_t lds) {
-    return lds <= 48 * 1024 ||
-           hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) == hipSuccess;
-}
-
 template <bool LDS, typename IdT>
 int cm_launch_fwd(const void* chars, int64_t ld_chars, const float* E, const float* Wr, const float* bias, const uint32_t* bits, float scale,
                   int64_t n_words, int32_t W, int32_t span, int32_t cfs, int32_t V, int32_t C, int32_t Fo, const CmFwdGeo& g, int nw,
                   float* out, uint8_t* arg, hipStream_t st) {
     const size_t lds = (static_cast<size_t>(nw) * g.xs_floats + (LDS ? static_cast<size_t>(g.Kp) * g.pitch + static_cast<size_t>(V) * C : 0)) * 4;
     auto kern = &k_char_masked_fwd<LDS, IdT>;
-    if (!cm_allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
-    const int64_t blocks = LDS ? cm_min64(ceil_div64(n_words, 4 * nw), 256) : cm_min64(ceil_div64(n_words, nw), 2048);
+    if (!allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
+    const int64_t blocks = LDS ? min64(ceil_div64(n_words, 4 * nw), 256) : min64(ceil_div64(n_words, nw), 2048);
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * nw), lds, st, static_cast<const IdT*>(chars), ld_chars, E, Wr, bias, bits,
                        scale, n_words, W, span, cfs, V, C, Fo, g.Kp, g.pitch, g.xs_floats, out, arg);
     return RECON_OK;
@@ -394,7 +370,7 @@ int cm_launch_bwd(const void* chars, int64_t ld_chars, const float* E, const flo
     const int64_t nE = static_cast<int64_t>(V) * C, nW = static_cast<int64_t>(Fo) * cfs * C;
     const size_t lds = static_cast<size_t>(cm_bwd_small_floats(span, cfs, C, Fo) + (LDS ? 2 * (nE + nW) : 0)) * 4;
     auto kern = &k_char_masked_bwd<LDS, IdT>;
-    if (!cm_allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
+    if (!allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(G)), dim3(256), lds, st, static_cast<const IdT*>(chars), ld_chars, E, Wc, bits, scale, g_out,
                        out, arg, n_words, per, W, span, cfs, V, C, Fo, padding_idx, partial);
     return RECON_OK;
@@ -420,7 +396,7 @@ extern "C" size_t recon_char_masked_workspace_bytes(int64_t S, int32_t W, int32_
     }
     int64_t per;
     int32_t G;
-    recon::cm_bwd_split(S * W, &per, &G);
+    recon::split_rows(S * W, recon::kCmBwdMaxWg, recon::kCmBwdMinWords, &per, &G);
     return align_up(static_cast<size_t>(G) * recon::cm_slab_floats(cfs, V, C, Fo) * 4, 256);
 }
 
@@ -442,9 +418,8 @@ extern "C" int recon_char_masked_fwd(const void* chars, int32_t index_bytes, int
     if (S < 0 || (index_bytes != 4 && index_bytes != 8)) return RECON_ERR_INVALID;
     if (S == 0) return RECON_OK;
     if (!recon_char_masked_supported(S, W, span, cfs, V, C, Fo)) return RECON_ERR_UNSUPPORTED;
-    if (!chars || !emb || !conv_w || !conv_b || !bits || !out || !workspace || ld_chars < cfs - 1 + static_cast<int64_t>(W) * span) return RECON_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(workspace) % 16) return RECON_ERR_INVALID;
-    if (workspace_bytes < recon_char_masked_workspace_bytes(S, W, span, cfs, V, C, Fo, 0)) return RECON_ERR_WORKSPACE;
+    if (const int bad = recon::char_io_checks(chars && emb && conv_w && conv_b && bits && out && workspace, ld_chars, W, span, cfs, workspace,
+                                              workspace_bytes, recon_char_masked_workspace_bytes(S, W, span, cfs, V, C, Fo, 0))) return bad;
     hipStream_t st = as_stream(stream);
     const recon::CmFwdGeo g = recon::cm_fwd_geo(span, cfs, C, Fo);
     float* Wr = static_cast<float*>(workspace);
@@ -456,14 +431,10 @@ extern "C" int recon_char_masked_fwd(const void* chars, int32_t index_bytes, int
     const int nw = ((lds ? tables : 0) + 8 * g.xs_floats) * 4 <= recon::kCmLdsBytes ? 8 : 4;
     const uint32_t* b = reinterpret_cast<const uint32_t*>(bits);
     const int64_t n_words = S * W;
-    int rc;
-    if (index_bytes == 8) {
-        rc = lds ? recon::cm_launch_fwd<true, int64_t>(chars, ld_chars, emb, Wr, conv_b, b, scale, n_words, W, span, cfs, V, C, Fo, g, nw, out, arg_pos, st)
-                 : recon::cm_launch_fwd<false, int64_t>(chars, ld_chars, emb, Wr, conv_b, b, scale, n_words, W, span, cfs, V, C, Fo, g, nw, out, arg_pos, st);
-    } else {
-        rc = lds ? recon::cm_launch_fwd<true, int32_t>(chars, ld_chars, emb, Wr, conv_b, b, scale, n_words, W, span, cfs, V, C, Fo, g, nw, out, arg_pos, st)
-                 : recon::cm_launch_fwd<false, int32_t>(chars, ld_chars, emb, Wr, conv_b, b, scale, n_words, W, span, cfs, V, C, Fo, g, nw, out, arg_pos, st);
-    }
+    const int rc = recon::dispatch_lds_ids(index_bytes, lds, [&](auto in_lds, auto id) {
+        return recon::cm_launch_fwd<decltype(in_lds)::value, typename decltype(id)::type>(chars, ld_chars, emb, Wr, conv_b, b, scale, n_words, W, span, cfs, V,
+                                                                                          C, Fo, g, nw, out, arg_pos, st);
+    });
     if (rc != RECON_OK) return rc;
     RECON_CHECK_LAUNCH();
     return RECON_OK;
@@ -477,31 +448,22 @@ extern "C" int recon_char_masked_bwd(const void* chars, int32_t index_bytes, int
     if (!recon_char_masked_supported(S > 0 ? S : 1, W, span, cfs, V, C, Fo)) return RECON_ERR_UNSUPPORTED;
     if (!g_emb || !g_conv_w || !g_conv_b) return RECON_ERR_INVALID;
     hipStream_t st = as_stream(stream);
-    if (S == 0) {
-        if (hipMemsetAsync(g_emb, 0, static_cast<size_t>(V) * C * 4, st) != hipSuccess ||
-            hipMemsetAsync(g_conv_w, 0, static_cast<size_t>(Fo) * C * cfs * 4, st) != hipSuccess ||
-            hipMemsetAsync(g_conv_b, 0, static_cast<size_t>(Fo) * 4, st) != hipSuccess) return RECON_ERR_LAUNCH;
-        return RECON_OK;
-    }
-    if (!chars || !emb || !conv_w || !bits || !g_out || !out || !arg_pos || !workspace || ld_chars < cfs - 1 + static_cast<int64_t>(W) * span) return RECON_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(workspace) % 16) return RECON_ERR_INVALID;
-    if (workspace_bytes < recon_char_masked_workspace_bytes(S, W, span, cfs, V, C, Fo, 1)) return RECON_ERR_WORKSPACE;
+    if (S == 0)
+        return recon::zero_fill({{g_emb, static_cast<size_t>(V) * C}, {g_conv_w, static_cast<size_t>(Fo) * C * cfs}, {g_conv_b, static_cast<size_t>(Fo)}}, st);
+    if (const int bad = recon::char_io_checks(chars && emb && conv_w && bits && g_out && out && arg_pos && workspace, ld_chars, W, span, cfs, workspace,
+                                              workspace_bytes, recon_char_masked_workspace_bytes(S, W, span, cfs, V, C, Fo, 1))) return bad;
     const int64_t n_words = S * W, slab = recon::cm_slab_floats(cfs, V, C, Fo);
     int64_t per;
     int32_t G;
-    recon::cm_bwd_split(n_words, &per, &G);
+    recon::split_rows(n_words, recon::kCmBwdMaxWg, recon::kCmBwdMinWords, &per, &G);
     float* partial = static_cast<float*>(workspace);
     const bool lds = (recon::cm_bwd_small_floats(span, cfs, C, Fo) + 2 * (slab - Fo)) * 4 <= recon::kCmLdsBytes;
     if (!lds && hipMemsetAsync(partial, 0, static_cast<size_t>(G) * slab * 4, st) != hipSuccess) return RECON_ERR_LAUNCH;
     const uint32_t* b = reinterpret_cast<const uint32_t*>(bits);
-    int rc;
-    if (index_bytes == 8) {
-        rc = lds ? recon::cm_launch_bwd<true, int64_t>(chars, ld_chars, emb, conv_w, b, scale, g_out, out, arg_pos, n_words, per, G, W, span, cfs, V, C, Fo, padding_idx, partial, st)
-                 : recon::cm_launch_bwd<false, int64_t>(chars, ld_chars, emb, conv_w, b, scale, g_out, out, arg_pos, n_words, per, G, W, span, cfs, V, C, Fo, padding_idx, partial, st);
-    } else {
-        rc = lds ? recon::cm_launch_bwd<true, int32_t>(chars, ld_chars, emb, conv_w, b, scale, g_out, out, arg_pos, n_words, per, G, W, span, cfs, V, C, Fo, padding_idx, partial, st)
-                 : recon::cm_launch_bwd<false, int32_t>(chars, ld_chars, emb, conv_w, b, scale, g_out, out, arg_pos, n_words, per, G, W, span, cfs, V, C, Fo, padding_idx, partial, st);
-    }
+    const int rc = recon::dispatch_lds_ids(index_bytes, lds, [&](auto in_lds, auto id) {
+        return recon::cm_launch_bwd<decltype(in_lds)::value, typename decltype(id)::type>(chars, ld_chars, emb, conv_w, b, scale, g_out, out, arg_pos, n_words, per,
+                                                                                          G, W, span, cfs, V, C, Fo, padding_idx, partial, st);
+    });
     if (rc != RECON_OK) return rc;
     RECON_CHECK_LAUNCH();
     hipLaunchKernelGGL(recon::k_char_masked_reduce, dim3(static_cast<unsigned>(ceil_div64(slab, 256))), dim3(256), 0, st, partial, G, cfs, V, C, Fo, g_emb,

@@ -21,7 +21,7 @@
 //   through LDS, every output tile in the registers of one wave; the column of ones gives the bias gradient.  k_ctx_lstm_reduce adds the
 //   slabs in workgroup order and scatters into the eight gradients.
 #include <math.h>
-#include "recon_common.h"
+#include "ctx_enc_common.h"
 
 namespace recon {
 namespace {
@@ -32,9 +32,6 @@ constexpr int kClMaxI = 256;                   // 16 staged floats per thread an
 constexpr int kClMaxWg = 128;                  // workgroups per direction (the BPTT pass, one direction per launch: twice as many)
 constexpr int kClSlots = 48;                   // dW tiles one wave of the weight-gradient pass holds
 
-typedef float cl_f32x4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ inline int64_t cl_min64(int64_t a, int64_t b) { return a < b ? a : b; }
 inline int cl_pitch(int n, int mod32) { int p = n; while (p % 32 != mod32) ++p; return p; }
 
 struct ClGeo {
@@ -65,15 +62,11 @@ inline ClGeo cl_geo(int32_t Dw, int32_t Fc, int32_t H) {
     g.wg_floats = 2 * 16 * static_cast<int64_t>(g.pGs + g.pXs);
     return g;
 }
-inline void cl_split(int64_t S, int64_t* per, int32_t* G) {
-    *per = ceil_div64(S, kClMaxWg);
-    *G = static_cast<int32_t>(ceil_div64(S, *per));
-}
 
 __device__ __forceinline__ float cl_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // acc[q] += A[16 x K] . B[K x 16 at column cq[q]], K a multiple of 4; two k steps' operands are read before the first product
-__device__ __forceinline__ void cl_gate_products(const float* ap, const float* bq, int pitch, const int (&cq)[4], int K, cl_f32x4 (&acc)[4]) {
+__device__ __forceinline__ void cl_gate_products(const float* ap, const float* bq, int pitch, const int (&cq)[4], int K, enc_f32x4 (&acc)[4]) {
     int kk = 0;
     for (; kk + 8 <= K; kk += 8) {
         const float a0 = ap[kk], a1 = ap[kk + 4];
@@ -186,9 +179,9 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_fwd(const IdT* __restrict__ wo
             const float* hc = hs + (k & 1) * 16 * pH;
             float* hn = hs + ((k & 1) ^ 1) * 16 * pH;
             if (active) {
-                cl_f32x4 acc[4];
+                enc_f32x4 acc[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = cl_f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int q = 0; q < 4; ++q) acc[q] = enc_f32x4{0.f, 0.f, 0.f, 0.f};
                 const float* ap = xs + col * pX + grp;
                 const float* bq = wl + grp * pB;
                 cl_gate_products(ap, bq, pB, cq, Kx, acc);
@@ -313,9 +306,9 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_bptt(const float* __restrict__
                 }
             }
             __syncthreads();
-            cl_f32x4 acc[5];
+            enc_f32x4 acc[5];
 #pragma unroll
-            for (int e = 0; e < 5; ++e) acc[e] = cl_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int e = 0; e < 5; ++e) acc[e] = enc_f32x4{0.f, 0.f, 0.f, 0.f};
             const float* ap = dgs + col * pG + grp;
             const float* bq = wl + grp * pW;
             int kk = 0;
@@ -374,7 +367,7 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_wgrad(const IdT* __restrict__ 
     const int dir = blockIdx.y, I = Dw + Fc, N = I + H + 1, K4 = 4 * H, H5 = 5 * H, n_out = MT * NT;
     float* gs = cl_lds;                                                         // [2][16][pGs]
     float* xs = gs + 2 * 16 * pGs;                                              // [2][16][pXs]
-    const int64_t sa = blockIdx.x * per, sb = cl_min64(sa + per, S), n_rows = (sb - sa) * T, n_chunks = (n_rows + 15) / 16;
+    const int64_t sa = blockIdx.x * per, sb = min64(sa + per, S), n_rows = (sb - sa) * T, n_chunks = (n_rows + 15) / 16;
     const int lr = t >> 4, lc = t & 15;
     float gv[16], xv[21];
     auto load = [&](int64_t chunk) {                                            // row lr of the chunk: d_a and (x | h in front | 1)
@@ -417,9 +410,9 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_wgrad(const IdT* __restrict__ 
         for (int j = 0; j < 21; ++j)
             if (j < NT) xp[lc + 16 * j] = xv[j];
     };
-    cl_f32x4 acc[kClSlots];
+    enc_f32x4 acc[kClSlots];
 #pragma unroll
-    for (int e = 0; e < kClSlots; ++e) acc[e] = cl_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int e = 0; e < kClSlots; ++e) acc[e] = enc_f32x4{0.f, 0.f, 0.f, 0.f};
     const int mt0 = wid / NT, nt0 = wid - mt0 * NT, dq = 4 / NT, dr = 4 - dq * NT;       // tile e of this wave: index wid + 4 e = mt NT + nt
     if (n_chunks > 0) {
         load(0);
@@ -486,19 +479,13 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_reduce(const float* __restrict
     }
 }
 
-template <typename K>
-bool cl_allow_lds(K kern, size_t lds) {
-    return lds <= 48 * 1024 ||
-           hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) == hipSuccess;
-}
-
 template <typename IdT>
 int cl_launch_fwd(const void* words, int64_t ld_words, const float* table, int32_t Vw, const float* feat, int64_t ld_feat, const float* Wr,
                   int64_t S, int32_t T, int32_t Dw, int32_t Fc, int32_t H, const ClGeo& g, float* out, float* saved, hipStream_t st) {
     const size_t lds = static_cast<size_t>(g.fwd_floats) * 4;
     auto kern = &k_ctx_lstm_fwd<IdT>;
-    if (!cl_allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
-    const unsigned blocks = static_cast<unsigned>(cl_min64(ceil_div64(S, 16), kClMaxWg));
+    if (!allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
+    const unsigned blocks = static_cast<unsigned>(min64(ceil_div64(S, 16), kClMaxWg));
     hipLaunchKernelGGL(kern, dim3(blocks, 2), dim3(256), lds, st, static_cast<const IdT*>(words), ld_words, table, Vw, feat, ld_feat, Wr, S, T, Dw,
                        Fc, H, g.Kx, g.Kh, g.pB, g.pX, g.pH, out, saved);
     return RECON_OK;
@@ -510,7 +497,7 @@ int cl_launch_wgrad(const void* words, int64_t ld_words, const float* table, int
                     hipStream_t st) {
     const size_t lds = static_cast<size_t>(g.wg_floats) * 4;
     auto kern = &k_ctx_lstm_wgrad<IdT>;
-    if (!cl_allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
+    if (!allow_lds(kern, lds)) return RECON_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(G), 2), dim3(256), lds, st, static_cast<const IdT*>(words), ld_words, table, Vw, feat,
                        ld_feat, saved, S, T, Dw, Fc, H, per, g.MT, g.NT, g.pGs, g.pXs, partial);
     return RECON_OK;
@@ -535,7 +522,7 @@ extern "C" size_t recon_ctx_lstm_workspace_bytes(int64_t S, int32_t T, int32_t D
     if (!backward) return align_up(2 * (static_cast<size_t>(g.Kx + g.Kh) * g.pB + 4 * H) * 4, 256);
     int64_t per;
     int32_t G;
-    recon::cl_split(S, &per, &G);
+    recon::split_rows(S, recon::kClMaxWg, 1, &per, &G);
     return align_up(static_cast<size_t>(G) * 2 * 4 * H * g.N * 4, 256);
 }
 
@@ -564,9 +551,10 @@ extern "C" int recon_ctx_lstm_fwd(const void* words, int32_t index_bytes, int64_
     hipLaunchKernelGGL(recon::k_ctx_lstm_prep, dim3(static_cast<unsigned>(ceil_div64(n_prep, 256))), dim3(256), 0, st, w_ih, w_hh, b_ih, b_hh, w_ih_rev,
                        w_hh_rev, b_ih_rev, b_hh_rev, g.I, H, g.Kx, g.Kh, g.pB, Wr);
     RECON_CHECK_LAUNCH();
-    const int rc = index_bytes == 8
-        ? recon::cl_launch_fwd<int64_t>(words, ld_words, word_table, Vw, feat, ld_feat, Wr, S, T, Dw, Fc, H, g, out, static_cast<float*>(saved), st)
-        : recon::cl_launch_fwd<int32_t>(words, ld_words, word_table, Vw, feat, ld_feat, Wr, S, T, Dw, Fc, H, g, out, static_cast<float*>(saved), st);
+    const int rc = recon::dispatch_ids(index_bytes, [&](auto id) {
+        return recon::cl_launch_fwd<typename decltype(id)::type>(words, ld_words, word_table, Vw, feat, ld_feat, Wr, S, T, Dw, Fc, H, g, out,
+                                                                 static_cast<float*>(saved), st);
+    });
     if (rc != RECON_OK) return rc;
     RECON_CHECK_LAUNCH();
     return RECON_OK;
@@ -584,11 +572,9 @@ extern "C" int recon_ctx_lstm_bwd(const void* words, int32_t index_bytes, int64_
     hipStream_t st = as_stream(stream);
     const int32_t I = Dw + Fc;
     if (S == 0) {
-        float* w[] = {g_w_ih, g_w_ih_rev, g_w_hh, g_w_hh_rev, g_b_ih, g_b_ih_rev, g_b_hh, g_b_hh_rev};
-        const size_t n[] = {static_cast<size_t>(4) * H * I, static_cast<size_t>(4) * H * H, static_cast<size_t>(4) * H};
-        for (int i = 0; i < 8; ++i)
-            if (hipMemsetAsync(w[i], 0, n[i < 2 ? 0 : (i < 4 ? 1 : 2)] * 4, st) != hipSuccess) return RECON_ERR_LAUNCH;
-        return RECON_OK;
+        const size_t n_ih = static_cast<size_t>(4) * H * I, n_hh = static_cast<size_t>(4) * H * H, n_b = static_cast<size_t>(4) * H;
+        return recon::zero_fill({{g_w_ih, n_ih}, {g_w_ih_rev, n_ih}, {g_w_hh, n_hh}, {g_w_hh_rev, n_hh}, {g_b_ih, n_b}, {g_b_ih_rev, n_b}, {g_b_hh, n_b},
+                                 {g_b_hh_rev, n_b}}, st);
     }
     if (!feat || !w_ih || !w_hh || !w_ih_rev || !w_hh_rev || !g_out || !saved || !workspace || ld_feat < Fc) return RECON_ERR_INVALID;
     if (Dw > 0 && (!words || !word_table || Vw < 1 || ld_words < T)) return RECON_ERR_INVALID;
@@ -597,8 +583,8 @@ extern "C" int recon_ctx_lstm_bwd(const void* words, int32_t index_bytes, int64_
     const recon::ClGeo g = recon::cl_geo(Dw, Fc, H);
     {
         const size_t lds = static_cast<size_t>(g.bptt_floats) * 4;
-        if (!recon::cl_allow_lds(&recon::k_ctx_lstm_bptt, lds)) return RECON_ERR_LAUNCH;
-        const unsigned blocks = static_cast<unsigned>(recon::cl_min64(ceil_div64(S, 16), 2 * recon::kClMaxWg));
+        if (!recon::allow_lds(&recon::k_ctx_lstm_bptt, lds)) return RECON_ERR_LAUNCH;
+        const unsigned blocks = static_cast<unsigned>(recon::min64(ceil_div64(S, 16), 2 * recon::kClMaxWg));
         for (int dir = 0; dir < 2; ++dir) {                                     // one launch per direction: the second adds its d_x to the first's
             hipLaunchKernelGGL(recon::k_ctx_lstm_bptt, dim3(blocks), dim3(256), lds, st, w_ih, w_hh, w_ih_rev, w_hh_rev, g_out,
                                static_cast<float*>(saved), S, T, Dw, Fc, H, g.pW, g.pG, dir, d_feat, Dw > 0 ? d_word_vec : nullptr);
@@ -607,11 +593,12 @@ extern "C" int recon_ctx_lstm_bwd(const void* words, int32_t index_bytes, int64_
     }
     int64_t per;
     int32_t G;
-    recon::cl_split(S, &per, &G);
+    recon::split_rows(S, recon::kClMaxWg, 1, &per, &G);
     float* partial = static_cast<float*>(workspace);
-    const int rc = index_bytes == 8
-        ? recon::cl_launch_wgrad<int64_t>(words, ld_words, word_table, Vw, feat, ld_feat, static_cast<const float*>(saved), S, T, Dw, Fc, H, per, G, g, partial, st)
-        : recon::cl_launch_wgrad<int32_t>(words, ld_words, word_table, Vw, feat, ld_feat, static_cast<const float*>(saved), S, T, Dw, Fc, H, per, G, g, partial, st);
+    const int rc = recon::dispatch_ids(index_bytes, [&](auto id) {
+        return recon::cl_launch_wgrad<typename decltype(id)::type>(words, ld_words, word_table, Vw, feat, ld_feat, static_cast<const float*>(saved), S, T, Dw, Fc,
+                                                                   H, per, G, g, partial, st);
+    });
     if (rc != RECON_OK) return rc;
     RECON_CHECK_LAUNCH();
     hipLaunchKernelGGL(recon::k_ctx_lstm_reduce, dim3(static_cast<unsigned>(ceil_div64(static_cast<int64_t>(2) * 4 * H * g.N, 256))), dim3(256), 0, st,

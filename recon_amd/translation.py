@@ -28,25 +28,18 @@ def _chain(head, tail, W, rel):
     return (h + rel.unsqueeze(0) - t).abs().sum(-1)
 
 
-def _rows(x):
-    """x as the kernel reads it: unit column stride, row stride within reach; a copy only when it has to be."""
-    if x.stride(1) != 1 or (x.shape[0] > 1 and not x.shape[1] <= x.stride(0) <= _MAX_LD):
-        x = x.contiguous()
-    return x
-
-
 class _TranslationResiduals(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, tail, W, rel):
-        h, t, Wc, g = _rows(head.detach()), _rows(tail.detach()), W.detach().contiguous(), rel.detach().contiguous()
-        M, (n_rel, ent_dim, rel_dim) = h.shape[0], Wc.shape
+        Wc, g = W.detach().contiguous(), rel.detach().contiguous()
+        M, (n_rel, ent_dim, rel_dim) = head.shape[0], Wc.shape
+        (h, ld_h), (t, ld_t) = _lib.rows_in_place(head.detach(), ent_dim, _MAX_LD), _lib.rows_in_place(tail.detach(), ent_dim, _MAX_LD)
         L = _lib.lib()
         out = torch.empty(M, n_rel, dtype=torch.float32, device=h.device)
         saved = None
         if ctx.needs_input_grad[3]:
             saved = torch.empty(L.recon_rel_translation_saved_bytes(M, n_rel, rel_dim) // 4, dtype=torch.int32, device=h.device)
         with _lib.on_device(h.device):
-            ld_h, ld_t = (h.stride(0), t.stride(0)) if M > 1 else (ent_dim, ent_dim)      # (a single row's stride is arbitrary)
             _lib.check(L.recon_rel_translation_fwd(h.data_ptr(), ld_h, t.data_ptr(), ld_t, Wc.data_ptr(), g.data_ptr(), M, n_rel, ent_dim,
                                                    rel_dim, out.data_ptr(), _lib.ptr(saved), _lib.current_stream()), "recon_rel_translation_fwd")
         if saved is not None:
