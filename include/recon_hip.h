@@ -1080,6 +1080,54 @@ int recon_ctx_lstm_bwd(const void* words, int32_t index_bytes, int64_t ld_words,
                        void* workspace, size_t workspace_bytes, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * E9  The sentence encoder's pair LSTM (csrc/sent_lstm.hip): models/models.py:160-184, one layer, two directions, batch_first, over
+ *     S = B C independent sequences of exactly T steps (sequence s = b C + c is sentence b seen from entity pair c; no length masking),
+ *     h0 = c0 = 0, nn.LSTM's definition as in E8.  Only the final states are kept:
+ *         out[s] = (h_fwd after t = T - 1 | h_rev after t = 0),   out [B C][2 H].
+ *     The input row of step t is never written: word_table[sentence[b][t]] (Dw floats; sentence [B][T], row stride ld_sentence in
+ *     elements) times the dropout factors of (s, t), followed by pos_table[markers[s][t]] (P floats; markers [B C][T], row stride
+ *     ld_markers).  Both id arrays are int32 or int64 (index_bytes = 4 or 8, the same for both); ids outside their table are clamped into
+ *     it.  keep_bits: NULL (no dropout) or int32 [B C][T][ceil(Dw / 32)], contiguous: factor (s, t, c) = keep_scale if bit c % 32 of word
+ *     c / 32 is set, else 0.  I = Dw + P.  w_ih [4H][I], w_hh [4H][H], b_ih, b_hh [4H] per direction, fp32 and contiguous.  word_table is
+ *     a constant: no gradient of it is formed.  Everything is fp32 on v_mfma_f32_16x16x4_f32.  Status codes and the 16-byte alignment of
+ *     workspace and saved are those of the E7 entries.
+ * ------------------------------------------------------------------------------------------*/
+/* Shapes the kernels take (models/models.py:160-184): B, C, T, Dw, P >= 1, 1 <= H <= 256 (eight waves of up to two 16-unit blocks),
+ * Dw + P <= 128, T <= 2^20, B C T 5 H <= 2^40.  pos_table may have up to 16 rows (the fwd / bwd entries return RECON_ERR_UNSUPPORTED above,
+ * workspace_bytes 0).  The caller runs the stock ops for anything else. */
+int recon_sent_lstm_supported(int64_t B, int32_t C, int32_t T, int32_t Dw, int32_t P, int32_t H);
+/* Bytes of the workspace (models/models.py:160-184) of the forward (backward = 0: both directions' (W_ih | W_hh)^T in the order the
+ * recurrence reads its B fragments, k padded to a multiple of 16, and the bias sums) or of the backward (backward = 1: W_hh in fragment
+ * order; one private (d_w_ih | d_w_hh | d_b | class sums) of 4 H (I + H + 1 + Vp) floats per direction and row group, the groups being
+ * G = ceil(S / per) runs of per = ceil(S / 32) sequences; the reduced class sums).  16-byte aligned, any contents; 0 for a shape
+ * recon_sent_lstm_supported refuses. */
+size_t recon_sent_lstm_workspace_bytes(int64_t B, int32_t C, int32_t T, int32_t Dw, int32_t P, int32_t H, int32_t Vp, int32_t backward);
+/* Bytes of the opaque buffer the forward leaves for the backward (models/models.py:160-184): the post-activation gates and the cell
+ * state, 5 H floats per direction, sequence and step.  0 for a shape recon_sent_lstm_supported refuses. */
+size_t recon_sent_lstm_saved_bytes(int64_t B, int32_t C, int32_t T, int32_t Dw, int32_t P, int32_t H);
+/* Forward (models/models.py:160-184).  A workgroup owns one direction and one tile of sequences (16; 32 when S > 2048) for all T steps;
+ * the weights come from global memory / L2 straight into registers, h goes through LDS, the cell state never leaves registers.  No
+ * workgroup waits for another.  saved = NULL (no backward follows): out is the only thing written.  B C == 0: nothing is launched.
+ * Two launches (operand layout, sequences). */
+int recon_sent_lstm_fwd(const void* sentence, const void* markers, int32_t index_bytes, int64_t ld_sentence, int64_t ld_markers,
+                        const float* word_table, int32_t Vw, const float* pos_table, int32_t Vp, const int32_t* keep_bits, float keep_scale,
+                        const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* w_ih_rev, const float* w_hh_rev,
+                        const float* b_ih_rev, const float* b_hh_rev, int64_t B, int32_t C, int32_t T, int32_t Dw, int32_t P, int32_t H,
+                        float* out, void* saved, void* workspace, size_t workspace_bytes, recon_stream_t stream);
+/* Backward (models/models.py:160-184) from the forward's saved buffer, which it CONSUMES (the gate gradients and h replace the gates and
+ * c: one backward per forward).  g_out [B C][2 H] contiguous.  g_pos_table [Vp][P] receives the gradient of pos_table, row
+ * pos_padding_idx zero (< 0: none), formed as (sum of d_a over the rows of each marker value) . W_ih[:, Dw:]; no d_x is written.  g_b_ih
+ * and g_b_hh receive the same sums.  No floating-point atomics: a pass walks the steps backwards tile by tile; then workgroup
+ * (g, block of 128 gate rows, direction) adds d_a^T (x | h | 1 | onehot(marker)) over row group g and the groups are added in index
+ * order: bitwise identical from run to run.  B C == 0 writes zeros to the nine gradients and launches no kernel.  Five launches. */
+int recon_sent_lstm_bwd(const void* sentence, const void* markers, int32_t index_bytes, int64_t ld_sentence, int64_t ld_markers,
+                        const float* word_table, int32_t Vw, const float* pos_table, int32_t Vp, const int32_t* keep_bits, float keep_scale,
+                        const float* w_ih, const float* w_hh, const float* w_ih_rev, const float* w_hh_rev, const float* g_out, void* saved,
+                        int64_t B, int32_t C, int32_t T, int32_t Dw, int32_t P, int32_t H, int32_t pos_padding_idx, float* g_pos_table,
+                        float* g_w_ih, float* g_w_hh, float* g_b_ih, float* g_b_hh, float* g_w_ih_rev, float* g_w_hh_rev, float* g_b_ih_rev,
+                        float* g_b_hh_rev, void* workspace, size_t workspace_bytes, recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
  *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
  * ------------------------------------------------------------------------------------------*/

@@ -1,9 +1,10 @@
 """Stage-B caller of the propagation path, shaped like the reference's `GPGNN` (models/models.py:85-277):
 same constructor, forward signature and state_dict keys (word_embedding.weight, pos_embedding.weight, rnn1.*,
 representation_to_adj[.i].weight/bias, identity_transformation, start_embedding, head_indices, tail_indices,
-linear3.*), so a checkpoint written by the reference's train.py:415-416 loads unchanged.  The sentence encoder
-(embeddings, LSTM, Linear) stays stock PyTorch-ROCm (MIOpen / rocBLAS); the block-adjacency construction and the
-L-hop propagation with its fused head*tail gather run on the HIP kernels of csrc/prop.hip.  SURVEY.md 8f row N3."""
+linear3.*), so a checkpoint written by the reference's train.py:415-416 loads unchanged.  The sentence encoder's
+embeddings and LSTM run as `pair_sentence_states` (csrc/sent_lstm.hip; the stock PyTorch-ROCm ops where it does not apply), its
+Linear stays stock (rocBLAS); the block-adjacency construction and the L-hop propagation with its fused head*tail gather run on
+the HIP kernels of csrc/prop.hip.  SURVEY.md 8f row N3."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -12,6 +13,7 @@ from .propagation import (build_block_adjacency, propagate, propagate_blocks, ma
                           get_tail_indices)
 from .char_features import char_word_features, draw_packed_keep
 from .context_lstm import context_line_states
+from .sentence_lstm import pair_sentence_states
 
 
 class GPGNN(nn.Module):
@@ -49,9 +51,29 @@ class GPGNN(nn.Module):
         self.linear3 = nn.Linear(d * 2 * L, n_out)                                                    # :143-146
         nn.init.xavier_uniform_(self.linear3.weight)
 
+    # fused_sentence_encoder: run `encode` as `pair_sentence_states` (csrc/sent_lstm.hip) whenever the embeddings are plain, the word table
+    # is frozen and dropout1 is inactive or drawn as packed bits; DESIGN.md section 21 says why this is the default it is.
+    # packed_word_dropout (default False): draw dropout1 as packed bits (`draw_packed_keep`), so that training batches run the kernels too.
+    # Same distribution, another random stream than the reference's nn.Dropout call: an opt-in, like EntityEmbedding.packed_char_dropout.
+    fused_sentence_encoder = True
+    packed_word_dropout = False
+
+    def _fused_encode_applies(self, sentence_input, entity_markers, active):
+        we, pe = self.word_embedding, self.pos_embedding
+        plain = all(type(e) is nn.Embedding and e.max_norm is None and not e.sparse and not e.scale_grad_by_freq for e in (we, pe))
+        return (self.fused_sentence_encoder and plain and not we.weight.requires_grad and (not active or (self.packed_word_dropout and self.dropout1.p < 1))
+                and sentence_input.dim() == 2 and entity_markers.dim() == 3 and sentence_input.size(1) == self.max_sent_len
+                and tuple(entity_markers.shape) == (sentence_input.size(0), self.MAX_EDGES_PER_GRAPH, self.max_sent_len))
+
     def encode(self, sentence_input, entity_markers):
         """models/models.py:160-184: one LSTM pass per (sentence, ordered entity pair); returns [B, C, 2*units1]."""
         B, C = sentence_input.size(0), self.MAX_EDGES_PER_GRAPH
+        active = self.training and self.dropout1.p > 0
+        if self._fused_encode_applies(sentence_input, entity_markers, active):
+            we = self.word_embedding
+            keep = draw_packed_keep(B * C, self.max_sent_len, we.embedding_dim, self.dropout1.p, sentence_input.device) if active else None
+            return self.dropout2(pair_sentence_states(self.rnn1, sentence_input, entity_markers, we.weight, self.pos_embedding.weight, keep,
+                                                      pos_padding_idx=self.pos_embedding.padding_idx))
         expanded = torch.transpose(sentence_input.expand(C, B, self.max_sent_len), 0, 1)
         word = self.word_embedding(expanded.contiguous().view(-1, self.max_sent_len)).view(B, C, self.max_sent_len, -1)
         word = self.dropout1(word)
