@@ -341,6 +341,15 @@ size_t recon_gat_atp_bwd_split_bytes(int32_t N, int32_t D, int32_t H);
 
 size_t recon_gat_atp_bwd_partial_floats(int32_t N, int32_t E, int32_t F, int32_t R, int32_t D, int32_t H);
 size_t recon_gat_atp_bwd_partial2_floats(int32_t N, int32_t E, int32_t F, int32_t R, int32_t D, int32_t H);
+/* Host only: the launch plan of the backward's last three kernels for a shape (NR: destination rows, N unless the graph is
+ * row-compacted).  plan[0..2]: row slices of the three skinny products (destination sums over NR rows, source sums over N rows, the
+ * edge-side product over E rows; 0 for a product without rows), plan[3..5]: blocks of their fixed-order reduce (16 elements each),
+ * plan[6]: splits of the weight gradient V^T g_h, plan[7]: its tile workgroups, plan[8]: the z extent of its grid with the reduce's
+ * plan[9] blocks riding in further layers behind the tiles.
+ * Returns 1 where the reduce rides in the weight gradient's launch — the F16X2 mode with per-row scales (D <= 256), at most 8 heads,
+ * in a recon_gat_atp_bwd call (or a phase call with INPUTS and WEIGHTS and without EARLY_SUM) on a graph without source-side hub
+ * pieces —, 0 where it keeps a launch of its own. */
+int recon_gat_atp_bwd_ride_plan(int32_t NR, int32_t N, int32_t E, int32_t F, int32_t R, int32_t D, int32_t H, int32_t* plan /*[10]*/);
 int recon_gat_atp_bwd(const recon_graph* g, const recon_gat_atp_bwd_args* args, recon_stream_t stream);
 /* the same backward as independently launchable phases (bit mask): PREPARE -> { INPUTS, WEIGHTS } -> FINISH.
  * INPUTS (g_V GEMM, edge pass, source pass, score-vector gradient: HBM bound) and WEIGHTS (g_a = g_h^T V:

@@ -178,6 +178,7 @@ SYMBOLS = [
     ("recon_gat_atp_project", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatAtpArgs), C.c_void_p]),
     ("recon_gat_atp_bwd_partial_floats", C.c_size_t, [C.c_int32] * 6),
     ("recon_gat_atp_bwd_partial2_floats", C.c_size_t, [C.c_int32] * 6),
+    ("recon_gat_atp_bwd_ride_plan", C.c_int, [C.c_int32] * 7 + [C.POINTER(C.c_int32)]),
     ("recon_gat_atp_bwd", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatAtpBwdArgs), C.c_void_p]),
     ("recon_gat_atp_bwd_phase", C.c_int, [C.POINTER(ReconGraph), C.POINTER(GatAtpBwdArgs), C.c_int32, C.c_void_p]),
     ("recon_block_adjacency_fwd", C.c_int, [c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_void_p]),

@@ -148,6 +148,10 @@ __global__ void __launch_bounds__(256) k_score_vec_bwd(const float* __restrict__
 // (partial[h][z][w][d] -> g_a[h][d][w], transposed through LDS) with the score path's a_2[h][d] * g_u[h][w] added on the way, and —
 // in the blocks behind the tiles — g_a_2[h][d] = a[h][d][:] . g_u[h][:], 8 rows per block.  As k_splitk_reduce_t + k_score_vec_bwd
 // this was two launches and a second read-modify-write pass over g_a.  W % 4 == 0.
+// Tile order: the rows of a [w][d] image are D floats (800 bytes at cfg 2), no multiple of a 128-byte line, so the 128-byte row segments of
+// a tile share their first and last lines with the tiles beside it in d.  Workgroups go round-robin over the 8 XCDs, each with an L2 of
+// its own: in plain order the td neighbours of a row band sit on different XCDs and every shared line is fetched twice.  XCD c takes the
+// c-th CONTIGUOUS chunk of the tile order instead (as xcd_tile does for the GEMMs): 17.2 -> 13.2 us at cfg 2.
 __global__ void __launch_bounds__(256) k_atp_weights_finish(const float* __restrict__ partial, int32_t splits, int32_t W, int32_t D, int32_t H,
                                                             const float* __restrict__ a, const float* __restrict__ a2,
                                                             const float* __restrict__ gu, float* __restrict__ ga, float* __restrict__ ga2,
@@ -157,7 +161,8 @@ __global__ void __launch_bounds__(256) k_atp_weights_finish(const float* __restr
         for (int i = threadIdx.x; i < rezero_words; i += 256) rezero[i] = 0u;
     const int tw = (W + 31) / 32, td = (D + 31) / 32, ntile = tw * td * H;
     if (static_cast<int>(blockIdx.x) < ntile) {
-        const int b = blockIdx.x, h = b / (td * tw), m0 = ((b / td) % tw) * 32, n0 = (b % td) * 32;      // m = w, n = d
+        const int c8 = blockIdx.x & 7, b = c8 * (ntile >> 3) + min(c8, ntile & 7) + (blockIdx.x >> 3);     // a bijection of [0, ntile)
+        const int h = b / (td * tw), m0 = ((b / td) % tw) * 32, n0 = (b % td) * 32;      // m = w, n = d
         const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
         const int64_t MN = static_cast<int64_t>(W) * D;
         const float* pz = partial + static_cast<int64_t>(h) * splits * MN;
@@ -1928,41 +1933,11 @@ __global__ void __launch_bounds__(kBlock) k_gat_atp_src_skinny(const AtpSrcK p, 
 }
 
 // out[(j % P)*S1 + (j / P)*S2 + c] = sum_b partial[b][j][c]   (16 elements x 64 slice groups per block, fixed order)
-struct SkinnyRedJob { const float* partial; float* out; int64_t S1, S2; int32_t nb, nj, K, P, nblocks; };
+// (skinny_reduce_block, recon_common.h: the same blocks ride behind the weight-gradient tiles where that launch follows, see
+// recon_gat_atp_bwd_phase.)  The launch of its own: 1024 threads, one slice group each.
 __global__ void __launch_bounds__(1024) k_skinny_reduce(const SkinnyRedJob j0, const SkinnyRedJob j1, const SkinnyRedJob j2) {
     __shared__ float red[64][17];
-    const int which = static_cast<int>(blockIdx.x) < j0.nblocks ? 0 : (static_cast<int>(blockIdx.x) < j0.nblocks + j1.nblocks ? 1 : 2);
-    const SkinnyRedJob& jb = which == 0 ? j0 : (which == 1 ? j1 : j2);
-    const float* __restrict__ partial = jb.partial;
-    float* __restrict__ out = jb.out;
-    const int nb = jb.nb, nj = jb.nj, K = jb.K, P = jb.P;
-    const int64_t S1 = jb.S1, S2 = jb.S2;
-    const int bid = blockIdx.x - (which == 0 ? 0 : (which == 1 ? j0.nblocks : j0.nblocks + j1.nblocks));
-    const int e = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    const int idx = bid * 16 + e;
-    const int tot = nj * K;
-    const int per = (nb + 63) / 64;
-    const int b0 = grp * per, b1 = min(nb, (grp + 1) * per);
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (idx < tot) {
-        int b = b0;
-        for (; b + 4 <= b1; b += 4) {
-            s0 += partial[static_cast<int64_t>(b) * tot + idx];
-            s1 += partial[static_cast<int64_t>(b + 1) * tot + idx];
-            s2 += partial[static_cast<int64_t>(b + 2) * tot + idx];
-            s3 += partial[static_cast<int64_t>(b + 3) * tot + idx];
-        }
-        for (; b < b1; ++b) s0 += partial[static_cast<int64_t>(b) * tot + idx];
-    }
-    red[grp][e] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (grp == 0 && idx < tot) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 64; ++g) t += red[g][e];
-        const int j = idx / K, c = idx % K;
-        out[(j % P) * S1 + (j / P) * S2 + c] = t;
-    }
+    skinny_reduce_block<1024>(j0, j1, j2, blockIdx.x, threadIdx.x, red);
 }
 
 struct AtpShape { int vec, kr, ht; };
@@ -2354,6 +2329,32 @@ extern "C" size_t recon_gat_atp_bwd_partial2_floats(int32_t N, int32_t E, int32_
     const size_t mx = static_cast<size_t>(F > R ? F : R);
     return static_cast<size_t>(3) * kSkinnySlices * 16 * mx;       // three products in flight
 }
+// blocks of the fixed-order reduce of one skinny product: 16 of its nj * K elements each (skinny_reduce_block)
+static int32_t skinny_red_blocks(int nj, int K) { return static_cast<int32_t>(ceil_div64(1LL * nj * K, 16)); }
+
+// The launch plan of the backward's tail for a shape whose reduce rides behind the weight-gradient tiles (see `ride` in
+// recon_gat_atp_bwd_phase; NR: destination rows, N unless the graph is row-compacted).  The three products are the destination sums'
+// (NR rows), the source sums' (N rows) and the edge-side one (E rows); a product without rows has neither slices nor blocks.
+extern "C" int recon_gat_atp_bwd_ride_plan(int32_t NR, int32_t N, int32_t E, int32_t F, int32_t R, int32_t D, int32_t H, int32_t* plan) {
+    if (!plan || NR < 0 || N < 1 || E < 0 || F < 1 || R < 1 || D < 1 || H < 1) return 0;
+    const int64_t rows[3] = {NR, N, E};
+    const int K[3] = {F, F, R};
+    int32_t nr_total = 0;
+    for (int i = 0; i < 3; ++i) {
+        plan[i] = rows[i] > 0 ? static_cast<int32_t>(ceil_div64(rows[i], skinny_rpb(rows[i]))) : 0;
+        plan[3 + i] = rows[i] > 0 ? skinny_red_blocks(H, K[i]) : 0;
+        nr_total += plan[3 + i];
+    }
+    const int32_t W = 2 * F + R;
+    const int sk = bx3_kmajor_splits(NR, bx3_kmajor_split_k(W, D, NR, H));
+    const int64_t tiles_xy = hx2_kmajor_tiles_xy(W, D);
+    plan[6] = sk;
+    plan[7] = static_cast<int32_t>(tiles_xy * H * sk);
+    plan[8] = static_cast<int32_t>(1LL * H * sk + hx2_kmajor_rider_layers(tiles_xy, nr_total));
+    plan[9] = nr_total;
+    const bool lds_ok = static_cast<size_t>(skinny_rpb(N)) * H * sizeof(float) <= kSkinnySrcLdsMax;
+    return (H <= 8 && D <= 256 && lds_ok && recon_gat_atp_f16x2_supported(F, R, D, H) && nr_total > 0) ? 1 : 0;
+}
 
 extern "C" int recon_gat_atp_bwd(const recon_graph* g, const recon_gat_atp_bwd_args* b, recon_stream_t stream) {
     return recon_gat_atp_bwd_phase(g, b, RECON_ATP_BWD_ALL, stream);
@@ -2419,6 +2420,8 @@ extern "C" int recon_gat_atp_bwd_phase(const recon_graph* g, const recon_gat_atp
     if (a->concat || rw.row_node) { gh = b->g_h; ld_gh = static_cast<int32_t>(HD); }
     GemmBatch bt;
     bt.batch = H; bt.epilogue = 0;
+    SkinnyRedRider rider;                                              // filled by INPUTS for WEIGHTS, see `ride`
+    rider.nblocks = 0;
     if (phases & RECON_ATP_BWD_INPUTS) {
     // (1) g_V[:, h, :] = g_h[:, h, :] . a[h]
     {
@@ -2498,6 +2501,12 @@ extern "C" int recon_gat_atp_bwd_phase(const recon_graph* g, const recon_gat_atp
         const size_t lds_src = static_cast<size_t>(skinny_rpb(N)) * H * sizeof(float);
         const bool share = want_u && H <= 8 && !hubs && lds_src <= kSkinnySrcLdsMax && (!a->io_bf16 || s.vec == 4);
         const int nsrc = static_cast<int>(ceil_div64(N, kBlock / 64) + ceil_div64(p.n_piece, kBlock / 64));
+        // The fixed-order reduce rides behind the tiles of the weight-gradient product (rider) where that launch follows in THIS call: the
+        // f16 x 2 family with the shared launch above (so one run_jobs call: up to 8 heads, no source-side hub pieces), INPUTS and WEIGHTS
+        // both asked for, no early sum.  The multi-GPU overlapped schedule issues WEIGHTS before INPUTS on a stream of its own — the
+        // product is under way before these partial sums exist — and keeps k_skinny_reduce; so do all other callers (the product's form
+        // without per-row scales, heads wider than 256 columns, among them: one instance carries the rider).
+        const bool ride = share && hx2 && row_inv && (phases & RECON_ATP_BWD_WEIGHTS) && !(phases & RECON_ATP_BWD_EARLY_SUM);
         SkinnyJob sj[3];
         int nb_total = 0;                                                // of the jobs in sj
         // the launch: the walk alone, or (share) the walk in front of the blocks of sj[0..2]
@@ -2541,7 +2550,7 @@ extern "C" int recon_gat_atp_bwd_phase(const recon_graph* g, const recon_gat_atp
                     const int nb = static_cast<int>(ceil_div64(q.rows, rpb));
                     float* part = b->partial2 + i * third;
                     sj[i] = SkinnyJob{q.G, q.X, q.gather, part, q.ldg, q.nj, q.rows, q.K, rpb, nb};
-                    rj[i] = SkinnyRedJob{part, q.out, q.S1, q.S2, nb, q.nj, q.K, q.P, static_cast<int32_t>(ceil_div64(1LL * q.nj * q.K, 16))};
+                    rj[i] = SkinnyRedJob{part, q.out, q.S1, q.S2, nb, q.nj, q.K, q.P, skinny_red_blocks(q.nj, q.K)};
                     if (q.nj > nj_max) nj_max = q.nj;
                     nb_total += nb; nr_total += rj[i].nblocks;
                 }
@@ -2555,7 +2564,8 @@ extern "C" int recon_gat_atp_bwd_phase(const recon_graph* g, const recon_gat_atp
                     } else if (nj_max <= 8) hipLaunchKernelGGL((k_skinny_tn_partial<8>), gp, dim3(256), 0, st, sj[0], sj[1], sj[2]);
                     else hipLaunchKernelGGL((k_skinny_tn_partial<16>), gp, dim3(256), 0, st, sj[0], sj[1], sj[2]);
                 }
-                hipLaunchKernelGGL(k_skinny_reduce, dim3(static_cast<unsigned>(nr_total)), dim3(1024), 0, st, rj[0], rj[1], rj[2]);
+                if (ride) { rider.j[0] = rj[0]; rider.j[1] = rj[1]; rider.j[2] = rj[2]; rider.nblocks = nr_total; }
+                else hipLaunchKernelGGL(k_skinny_reduce, dim3(static_cast<unsigned>(nr_total)), dim3(1024), 0, st, rj[0], rj[1], rj[2]);
             };
             if (H <= 8) {
                 // the common case, all three in one <8> launch: node-side products (Gs is [N][2H], dst sums | src sums: column
@@ -2595,7 +2605,7 @@ extern "C" int recon_gat_atp_bwd_phase(const recon_graph* g, const recon_gat_atp
                 const int sk = bx3_kmajor_splits(NR, bx3_kmajor_split_k(W, D, NR, H));
                 rc = gemm_hx2_kmajor_batched(W, D, NR, a->V, 2LL * W, W, 2LL * NR * W, b->gh_split, 2LL * D, D, 2LL * NR * D,
                                              H, sk, b->partial, static_cast<const char*>(a->aux) + kHx2ZeroPageOffset, atp_scale_v(a), atp_scale_g(a), st,
-                                             atp_dst_shared(a), row_inv, ldi);
+                                             atp_dst_shared(a), row_inv, ldi, rider.nblocks > 0 ? &rider : nullptr);
                 // its second pass runs in FINISH, fused with the score path's terms (k_atp_weights_finish) — unless the caller wants G now
                 if (rc == RECON_OK && (phases & RECON_ATP_BWD_EARLY_SUM)) rc = splitk_reduce(b->partial, sk, W, D, C, bw.c_bs, H, 0, true, st);
             } else if (gh_planes && bx3_kmajor_supported(a->V, ldv, W, ld_ghp, D, W, D)) {    // split-precision MFMA, both operands k-major

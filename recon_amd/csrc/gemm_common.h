@@ -58,9 +58,10 @@ __device__ __forceinline__ int64_t out_row_off(const OutputDesc& C, int32_t row)
 // different L2s and each re-fetches the operand from HBM (PMC: 349 MB for the g_V GEMM whose operands are 56 MB).
 // Give XCD c the c-th CONTIGUOUS chunk of the (n fastest, m, batch*split) tile order instead.
 struct TileId { int x, y, z; };
-__device__ __forceinline__ TileId xcd_tile(int remap) {
+// gz: the z extent that holds tiles (a launch may carry other blocks in further z layers behind them, k_gemm_hx2_kmajor's rider)
+__device__ __forceinline__ TileId xcd_tile(int remap, unsigned gz) {
     if (!remap) return {static_cast<int>(blockIdx.x), static_cast<int>(blockIdx.y), static_cast<int>(blockIdx.z)};
-    const unsigned gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
+    const unsigned gx = gridDim.x, gy = gridDim.y, total = gx * gy * gz;
     const unsigned L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
     const unsigned c = L & 7u, pos = L >> 3, q = total >> 3, r = total & 7u;
     const unsigned logical = c * q + min(c, r) + pos;
@@ -71,6 +72,7 @@ __device__ __forceinline__ TileId xcd_tile(int remap) {
     id.z = static_cast<int>(rest / gy);
     return id;
 }
+__device__ __forceinline__ TileId xcd_tile(int remap) { return xcd_tile(remap, gridDim.z); }
 
 
 

@@ -341,6 +341,7 @@ struct Hx2KmArgs {
     int64_t lda, ldb, a_plane, b_plane, a_bs, b_bs;
     float* partial;
     int32_t M, N, K, k_per_split, nsplit;
+    int32_t tiles_z;               // batch * nsplit: the grid's z layers that hold tiles (a rider's blocks sit in the layers behind them)
     int32_t m_ld, n_ld;            // columns present in the planes (multiples of 8, >= M / N; the excess is zero padding)
     int32_t a_shared_m;            // A's columns m < a_shared_m are the same for every batch entry and are read from entry 0 (0: none)
     Hx2Scale sa, sb;
@@ -350,14 +351,25 @@ struct Hx2KmArgs {
 constexpr int KA_PIECES = T * (KA_PLANE / 1024), KA_DMA = KA_PIECES / 4;               // 16, 4
 constexpr int KB_PIECES = T * (KB_PLANE / 1024), KB_DMA = (KB_PIECES + 3) / 4;         // 28, 7
 
-template <int OCC, bool KSC>
-__global__ void __launch_bounds__(NT, OCC) k_gemm_hx2_kmajor(const Hx2KmArgs p) {
+// RIDE: the workgroups behind the tiles_z tile layers run the blocks of a skinny reduce (SkinnyRedRider, recon_common.h) and return:
+// they are dispatched after every tile and fill the tail that the tiles leave on the chip.  The tile path does not know of them.
+template <int OCC, bool KSC, bool RIDE>
+__global__ void __launch_bounds__(NT, OCC) k_gemm_hx2_kmajor(const Hx2KmArgs p, const SkinnyRedRider rd) {
     __shared__ __attribute__((aligned(16))) unsigned char S[T * KA_PLANE + T * KB_PLANE];      // A image | B image: 45056 B
+    if constexpr (RIDE) {
+        static_assert(sizeof(S) >= 64 * 17 * sizeof(float), "the rider's group sums");
+        const unsigned L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), ntile = gridDim.x * gridDim.y * p.tiles_z;
+        if (L >= ntile) {                                             // block-uniform
+            if (L - ntile < static_cast<unsigned>(rd.nblocks))
+                skinny_reduce_block<NT>(rd.j[0], rd.j[1], rd.j[2], static_cast<int>(L - ntile), threadIdx.x, reinterpret_cast<float(*)[17]>(S));
+            return;
+        }
+    }
     unsigned char* const As = S;
     unsigned char* const Bs = S + T * KA_PLANE;
     const int t = threadIdx.x, lane = t & 63;
     const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
-    const TileId tile = xcd_tile(1);
+    const TileId tile = RIDE ? xcd_tile(1, p.tiles_z) : xcd_tile(1);
     const int m0 = tile.y * BM, n0 = tile.x * BN;
     const int bz = tile.z / p.nsplit, zs = tile.z % p.nsplit;
     const int k_begin = zs * p.k_per_split, k_end = min(p.K, k_begin + p.k_per_split);
@@ -667,12 +679,20 @@ bool hx2_kmajor_supported(const void* Ap, int64_t lda, int64_t a_plane, int64_t 
     return !((reinterpret_cast<uintptr_t>(Ap) | reinterpret_cast<uintptr_t>(Bp)) & 15);
 }
 
+int64_t hx2_kmajor_tiles_xy(int32_t M, int32_t N) { return ceil_div64(N, BN) * ceil_div64(M, BM); }
+int64_t hx2_kmajor_rider_layers(int64_t tiles_xy, int32_t rider_blocks) {
+    return rider_blocks > 0 && tiles_xy > 0 ? ceil_div64(rider_blocks, tiles_xy) : 0;
+}
+
 // partial[batch][split][M][N] = A_slice^T . B_slice / (s_a s_b);  a_bs / b_bs = per-batch column offsets;
 // split_k must be bx3_kmajor_splits(K, requested) (same K-tile rounding as the bf16 x 3 kernel)
 int gemm_hx2_kmajor_batched(int32_t M, int32_t N, int32_t K, const void* Ap, int64_t lda, int64_t a_plane, int64_t a_bs, const void* Bp,
                             int64_t ldb, int64_t b_plane, int64_t b_bs, int32_t batch, int32_t split_k, float* partial, const void* zeros,
-                            const Hx2Scale& sa, const Hx2Scale& sb, hipStream_t st, int32_t a_shared_m, const float* k_inv, int64_t k_inv_bs) {
+                            const Hx2Scale& sa, const Hx2Scale& sb, hipStream_t st, int32_t a_shared_m, const float* k_inv, int64_t k_inv_bs,
+                            const SkinnyRedRider* rider) {
     if (M < 0 || N < 0 || K < 0 || batch < 0 || split_k < 1) return RECON_ERR_INVALID;
+    const bool ride = rider && rider->nblocks > 0;
+    if (ride && (M == 0 || N == 0 || batch == 0 || !k_inv)) return RECON_ERR_INVALID;       // no launch to ride in / no instance that carries one
     if (M == 0 || N == 0 || batch == 0) return RECON_OK;
     if (!Ap || !Bp || !partial || !zeros || (reinterpret_cast<uintptr_t>(zeros) & 15)) return RECON_ERR_INVALID;
     if (!hx2_kmajor_supported(Ap, lda, a_plane, a_bs, Bp, ldb, b_plane, b_bs, M, N)) return RECON_ERR_UNSUPPORTED;
@@ -685,16 +705,22 @@ int gemm_hx2_kmajor_batched(int32_t M, int32_t N, int32_t K, const void* Ap, int
     a.k_per_split = sp.k_per_split;
     a.nsplit = sp.nsplit;
     if (a.nsplit != split_k) return RECON_ERR_INVALID;
-    if (static_cast<int64_t>(batch) * split_k > 65535) return RECON_ERR_UNSUPPORTED;
+    a.tiles_z = batch * split_k;
+    const int64_t gz = static_cast<int64_t>(a.tiles_z) + (ride ? hx2_kmajor_rider_layers(hx2_kmajor_tiles_xy(M, N), rider->nblocks) : 0);
+    if (gz > 65535 || hx2_kmajor_tiles_xy(M, N) * gz >= (1LL << 31)) return RECON_ERR_UNSUPPORTED;
     a.sa = sa; a.sb = sb;
     if (a_shared_m < 0 || (a_shared_m & 7)) return RECON_ERR_UNSUPPORTED;
     a.a_shared_m = a_shared_m;
-    const dim3 grid(static_cast<unsigned>(ceil_div64(N, BN)), static_cast<unsigned>(ceil_div64(M, BM)), static_cast<unsigned>(batch * split_k));
+    const dim3 grid(static_cast<unsigned>(ceil_div64(N, BN)), static_cast<unsigned>(ceil_div64(M, BM)), static_cast<unsigned>(gz));
     a.k_inv = k_inv; a.k_inv_bs = k_inv_bs;
     if (k_inv && ((k_inv_bs & 3) || k_inv_bs < ((K + 7) & ~7) || (reinterpret_cast<uintptr_t>(k_inv) & 15))) return RECON_ERR_UNSUPPORTED;
     // three workgroups per CU (<= 168 registers) spill: 241 us against 70
-    if (k_inv) hipLaunchKernelGGL((k_gemm_hx2_kmajor<2, true>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((k_gemm_hx2_kmajor<2, false>), grid, dim3(NT), 0, st, a);
+    SkinnyRedRider none;
+    none.nblocks = 0;
+    for (SkinnyRedJob& j : none.j) j = SkinnyRedJob{nullptr, nullptr, 0, 0, 0, 0, 0, 1, 0};
+    if (ride) hipLaunchKernelGGL((k_gemm_hx2_kmajor<2, true, true>), grid, dim3(NT), 0, st, a, *rider);
+    else if (k_inv) hipLaunchKernelGGL((k_gemm_hx2_kmajor<2, true, false>), grid, dim3(NT), 0, st, a, none);
+    else hipLaunchKernelGGL((k_gemm_hx2_kmajor<2, false, false>), grid, dim3(NT), 0, st, a, none);
     if (hipGetLastError() != hipSuccess) return RECON_ERR_LAUNCH;
     return RECON_OK;
 }

@@ -392,10 +392,76 @@ int gemm_hx2_batched(int32_t M, int32_t N, int32_t K, const void* Ap, int64_t a_
                      const float* row_inv = nullptr, int64_t row_inv_bs = 0);
 bool hx2_kmajor_supported(const void* Ap, int64_t lda, int64_t a_plane, int64_t a_bs, const void* Bp, int64_t ldb, int64_t b_plane,
                           int64_t b_bs, int32_t M, int32_t N);
+
+// The fixed-order second pass of up to three skinny products (gat_atp.hip):
+//   out[(j % P)*S1 + (j / P)*S2 + c] = sum_b partial[b][j][c],   b < nb slices of nj*K floats.
+// A block owns 16 consecutive elements idx = j*K + c of ONE job (nblocks = ceil(nj*K / 16) blocks per job, the jobs' blocks one job
+// behind the other); the slices go to 64 groups of per = ceil(nb / 64) consecutive slices.  A group's sum is four interleaved chains
+// over whole quads of slices, the rest of the group added to chain 0 in order, then (s0 + s1) + (s2 + s3); the 64 group sums are added
+// in group order.  That order is the contract: g_u is the same bits from any block size.
+// A device function so that the pass can ride in another kernel's launch (k_gemm_hx2_kmajor, like hx2_split_both_block above).
+// NT threads (1024 or 256) hold 1024 / NT groups each, and all of a thread's loads of one quad step go out before the first add —
+// branch free: slices past a group's end re-read the last slice and are masked out of the sums.  red: 64 x 17 floats of LDS.
+struct SkinnyRedJob { const float* partial; float* out; int64_t S1, S2; int32_t nb, nj, K, P, nblocks; };
+struct SkinnyRedRider { SkinnyRedJob j[3]; int32_t nblocks; };        // nblocks: of the three jobs together; 0: nothing rides
+template <int NT>
+__device__ __forceinline__ void skinny_reduce_block(const SkinnyRedJob& j0, const SkinnyRedJob& j1, const SkinnyRedJob& j2, int blk, int tid,
+                                                    float (*red)[17]) {
+    static_assert(NT == 1024 || NT == 256, "64 slice groups x 16 elements over the block");
+    constexpr int GPT = 1024 / NT, GSTEP = NT / 16;                   // groups per thread: g0, g0 + GSTEP, ...
+    const int which = blk < j0.nblocks ? 0 : (blk < j0.nblocks + j1.nblocks ? 1 : 2);
+    const SkinnyRedJob& jb = which == 0 ? j0 : (which == 1 ? j1 : j2);
+    const float* __restrict__ partial = jb.partial;
+    const int nb = jb.nb, tot = jb.nj * jb.K;
+    const int bid = blk - (which == 0 ? 0 : (which == 1 ? j0.nblocks : j0.nblocks + j1.nblocks));
+    const int e = tid & 15, g0 = tid >> 4;
+    const int idx = bid * 16 + e;
+    const int idc = min(idx, tot - 1);
+    const int per = (nb + 63) / 64;
+    float s[GPT][4];
+    int b0[GPT], len[GPT];
+#pragma unroll
+    for (int i = 0; i < GPT; ++i) {
+        b0[i] = (g0 + i * GSTEP) * per;
+        len[i] = max(0, min(nb, b0[i] + per) - b0[i]);
+        s[i][0] = s[i][1] = s[i][2] = s[i][3] = 0.f;
+    }
+    for (int k = 0; k < per; k += 4) {
+        float v[GPT][4];
+#pragma unroll
+        for (int i = 0; i < GPT; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[i][q] = partial[static_cast<int64_t>(min(b0[i] + k + q, nb - 1)) * tot + idc];
+#pragma unroll
+        for (int i = 0; i < GPT; ++i) {
+            const bool quad = k + 4 <= len[i];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) s[i][q] = quad ? s[i][q] + v[i][q] : s[i][q];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) s[i][0] = (!quad && k + q < len[i]) ? s[i][0] + v[i][q] : s[i][0];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < GPT; ++i) red[g0 + i * GSTEP][e] = (s[i][0] + s[i][1]) + (s[i][2] + s[i][3]);
+    __syncthreads();
+    if (g0 == 0 && idx < tot) {
+        float t = 0.f;
+#pragma unroll
+        for (int g = 0; g < 64; ++g) t += red[g][e];
+        const int j = idx / jb.K, c = idx % jb.K;
+        jb.out[(j % jb.P) * jb.S1 + (j / jb.P) * jb.S2 + c] = t;
+    }
+}
+// rider (optional): the blocks of a skinny reduce, run by extra workgroups BEHIND the tiles of this launch (the reduce neither reads nor
+// writes anything the product touches; as a launch of its own it is a kernel turn-around for a few MB).  The grid is gx x gy tiles
+// (hx2_kmajor_tiles_xy) by batch * split_k in z; with a rider its z extent grows by hx2_kmajor_rider_layers layers of gx * gy
+// workgroups, whose first rider_blocks (in launch order) are the rider's and the rest return at once.
+int64_t hx2_kmajor_tiles_xy(int32_t M, int32_t N);
+int64_t hx2_kmajor_rider_layers(int64_t tiles_xy, int32_t rider_blocks);
 int gemm_hx2_kmajor_batched(int32_t M, int32_t N, int32_t K, const void* Ap, int64_t lda, int64_t a_plane, int64_t a_bs, const void* Bp,
                             int64_t ldb, int64_t b_plane, int64_t b_bs, int32_t batch, int32_t split_k, float* partial, const void* zeros,
                             const Hx2Scale& sa, const Hx2Scale& sb, hipStream_t st, int32_t a_shared_m = 0, const float* k_inv = nullptr,
-                            int64_t k_inv_bs = 0);
+                            int64_t k_inv_bs = 0, const SkinnyRedRider* rider = nullptr);
 // k_inv (optional): B's rows (the contraction index k) carry per-row power-of-two scales s_k = 1 / k_inv[z * k_inv_bs + k] while `sb`
 // names the tensor's global maximum (scale s_g <= every s_k).  The kernel brings the rows to the common scale on the OTHER operand: A's
 // fragments are multiplied by s_g / s_k (a power of two <= 1, exact in half precision down to its subnormals) as they leave LDS.
