@@ -18,12 +18,10 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
+from . import _lib, _lstm
+from ._lstm import _PARAMS, _kernel_lstm           # (importable from here under these names)
 
 BWD_MAX_WORKGROUPS = 128          # kClMaxWg of csrc/ctx_lstm.hip: the weight-gradient pass gives each of them ceil(S / 128) sequences
-
-_PARAMS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
-           "weight_ih_l0_reverse", "weight_hh_l0_reverse", "bias_ih_l0_reverse", "bias_hh_l0_reverse")
 
 
 def _chain(lstm, feat, words=None, word_table=None, padding_idx=None):
@@ -69,15 +67,12 @@ class _ContextLineStates(torch.autograd.Function):
         feat, ids, word_table, out, saved, *params = ctx.saved_tensors
         need = ctx.needs_input_grad
         S, T, Dw, Fc, H = ctx.geo
-        if torch.is_grad_enabled() or ctx.consumed:
-            # create_graph (the gradient itself must be differentiable; MIOpen's RNN backward is not) or a second backward over a retained
-            # graph (the first consumed the saved state): recompute through the stock ops, the native ones, which differentiate twice and
-            # run a backward in eval mode too
+        def stock():
             safe = None if ids is None else ids.clamp(0, word_table.shape[0] - 1)               # as the kernels clamp them
-            with torch.backends.cudnn.flags(enabled=False):
-                return (None, None, None) + _lib.recompute_grads(lambda: _chain(ctx.lstm, feat, safe, word_table, ctx.padding_idx),
-                                                                 (feat, None, word_table) + tuple(params), need[3:], g_out, torch.is_grad_enabled())
-        ctx.consumed = True
+            return _chain(ctx.lstm, feat, safe, word_table, ctx.padding_idx)
+        grads = _lstm._recompute(ctx, stock, (feat, None, word_table) + tuple(params), need[3:], g_out)
+        if grads is not None:
+            return (None, None, None) + grads
         L = _lib.lib()
         x, ld_feat = _lib.rows_in_place(feat.detach(), Fc)
         ld_words = 0
@@ -104,11 +99,6 @@ class _ContextLineStates(torch.autograd.Function):
             pad = -1 if ctx.padding_idx is None else int(ctx.padding_idx)
             g_table = torch.ops.aten.embedding_dense_backward(d_wv, ids.long().clamp(0, Vw - 1), Vw, pad, False)
         return (None, None, None, d_feat, None, g_table) + tuple(q if n else None for q, n in zip(gp, need[6:]))
-
-
-def _kernel_lstm(lstm):
-    return (isinstance(lstm, nn.LSTM) and lstm.num_layers == 1 and lstm.bidirectional and lstm.batch_first and lstm.bias
-            and lstm.proj_size == 0 and lstm.dropout == 0)
 
 
 def _fused(lstm, feat, words, word_table):
@@ -145,8 +135,7 @@ def context_line_states(lstm, feat, words=None, word_table=None, padding_idx=Non
         raise ValueError("context_line_states: the LSTM takes %d inputs, got Dw + Fc = %d + %d over T = %d steps"
                          % (lstm.input_size, Dw, feat.shape[2], feat.shape[1]))
     if feat.shape[0] == 0:
-        dirs = 2 if lstm.bidirectional else 1
-        return torch.empty(0, dirs * (lstm.proj_size or lstm.hidden_size), dtype=feat.dtype, device=feat.device)
+        return _lstm._empty_states(lstm, (0,), feat)
     if _fused(lstm, feat, words, word_table):
         params = [getattr(lstm, n) for n in _PARAMS]
         # (inside the function grad mode is off and needs_input_grad ignores no_grad: whether a backward can follow is decided here)

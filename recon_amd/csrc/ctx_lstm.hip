@@ -18,10 +18,9 @@
 //   d_h of its own units, the others are columns of d_x, written to d_word_vec / d_feat.  It leaves d_a where the gates were and h[t]
 //   where c[t] was.
 // k_ctx_lstm_wgrad: workgroup g owns a fixed run of sequences and accumulates d_a^T . (x | h[t'] | 1) over its (s, t) rows, 16 at a time
-//   through LDS, every output tile in the registers of one wave; the column of ones gives the bias gradient.  k_ctx_lstm_reduce adds the
-//   slabs in workgroup order and scatters into the eight gradients.
-#include <math.h>
-#include "ctx_enc_common.h"
+//   through LDS, every output tile in the registers of one wave; the column of ones gives the bias gradient.  k_lstm_reduce (lstm_common.h,
+//   with Vp = 0 and no class sums) adds the slabs in workgroup order and scatters into the eight gradients.
+#include "lstm_common.h"
 
 namespace recon {
 namespace {
@@ -31,8 +30,6 @@ constexpr int kClMaxH = 64;                    // four waves, one 16-unit block 
 constexpr int kClMaxI = 256;                   // 16 staged floats per thread and row
 constexpr int kClMaxWg = 128;                  // workgroups per direction (the BPTT pass, one direction per launch: twice as many)
 constexpr int kClSlots = 48;                   // dW tiles one wave of the weight-gradient pass holds
-
-inline int cl_pitch(int n, int mod32) { int p = n; while (p % 32 != mod32) ++p; return p; }
 
 struct ClGeo {
     int32_t I, Kx, Kh, pB, pX, pH;             // forward
@@ -45,25 +42,23 @@ inline ClGeo cl_geo(int32_t Dw, int32_t Fc, int32_t H) {
     g.I = Dw + Fc;
     g.Kx = (g.I + 3) / 4 * 4;
     g.Kh = (H + 3) / 4 * 4;
-    g.pB = cl_pitch(4 * H, 16);
-    g.pX = cl_pitch(g.Kx, 2);                   // A rows: 16 sequences x 2 k of a half-wave in 32 different banks
-    g.pH = cl_pitch(g.Kh, 2);
+    g.pB = lstm_pitch(4 * H, 16);
+    g.pX = lstm_pitch(g.Kx, 2);                   // A rows: 16 sequences x 2 k of a half-wave in 32 different banks
+    g.pH = lstm_pitch(g.Kh, 2);
     g.fwd_floats = static_cast<int64_t>(g.Kx + g.Kh) * g.pB + 16 * g.pX + 32 * g.pH;
     g.K4 = 4 * H;                               // (a multiple of 4 already)
-    g.pG = cl_pitch(g.K4, 2);
-    g.pW = cl_pitch(g.I + H, 16);
+    g.pG = lstm_pitch(g.K4, 2);
+    g.pW = lstm_pitch(g.I + H, 16);
     if (static_cast<int64_t>(g.K4) * g.pW + 16 * g.pG > kClLdsFloats) g.pW = (g.I + H) % 32 ? g.I + H : g.I + H + 1;      // compact: some 2-way conflicts
     g.bptt_floats = static_cast<int64_t>(g.K4) * g.pW + 16 * g.pG;
     g.N = g.I + H + 1;
     g.MT = (4 * H + 15) / 16;
     g.NT = (g.N + 15) / 16;
-    g.pGs = cl_pitch(16 * g.MT, 16);
-    g.pXs = cl_pitch(16 * g.NT, 16);
+    g.pGs = lstm_pitch(16 * g.MT, 16);
+    g.pXs = lstm_pitch(16 * g.NT, 16);
     g.wg_floats = 2 * 16 * static_cast<int64_t>(g.pGs + g.pXs);
     return g;
 }
-
-__device__ __forceinline__ float cl_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // acc[q] += A[16 x K] . B[K x 16 at column cq[q]], K a multiple of 4; two k steps' operands are read before the first product
 __device__ __forceinline__ void cl_gate_products(const float* ap, const float* bq, int pitch, const int (&cq)[4], int K, enc_f32x4 (&acc)[4]) {
@@ -85,12 +80,6 @@ __device__ __forceinline__ void cl_gate_products(const float* ap, const float* b
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, br[cq[q]], acc[q], 0, 0, 0);
     }
-}
-
-template <typename IdT>
-__device__ __forceinline__ int cl_id(const IdT* p, int Vw) {
-    const int64_t v = static_cast<int64_t>(*p);
-    return static_cast<int>(v < 0 ? 0 : (v >= Vw ? Vw - 1 : v));
 }
 
 __global__ void __launch_bounds__(256) k_ctx_lstm_prep(const float* __restrict__ w_ih_f, const float* __restrict__ w_hh_f,
@@ -150,7 +139,7 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_fwd(const IdT* __restrict__ wo
         float xv[16];
         auto load_x = [&](int tt) {                                             // row lr of step tt: columns lc, lc + 16, ...
             int id = 0;
-            if (Dw > 0 && sv) id = cl_id(words + srow * ld_words + tt, Vw);
+            if (Dw > 0 && sv) id = lstm_id(words + srow * ld_words + tt, Vw);
             const float* trow = table + static_cast<int64_t>(id) * Dw;
             const float* frow = feat + (srow * T + tt) * ld_feat - Dw;
 #pragma unroll
@@ -191,16 +180,14 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_fwd(const IdT* __restrict__ wo
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int m = 4 * grp + i;
-                    const float ig = cl_sigmoid(acc[0][i] + bias[0]), fg = cl_sigmoid(acc[1][i] + bias[1]);
-                    const float gg = tanhf(acc[2][i] + bias[2]), og = cl_sigmoid(acc[3][i] + bias[3]);
-                    c[i] = fmaf(fg, c[i], ig * gg);
-                    const float h = og * tanhf(c[i]);
+                    float ig, fg, gg, og;
+                    const float h = lstm_cell_fwd(acc[0][i], acc[1][i], acc[2][i], acc[3][i], bias, c[i], ig, fg, gg, og);
                     if (u < H) {
                         hn[m * pH + u] = h;
                         if (s0 + m < S) {
                             if (saved) {
-                                float* sp = saved + ((static_cast<int64_t>(dir) * S + s0 + m) * T + tt) * (5 * H) + u;
-                                sp[0] = ig; sp[H] = fg; sp[2 * H] = gg; sp[3 * H] = og; sp[4 * H] = c[i];
+                                float* sp = lstm_saved_row(saved, static_cast<int64_t>(dir) * S + s0 + m, T, tt, lstm_row_floats(H)) + u;
+                                lstm_cell_store(sp, H, ig, fg, gg, og, c[i]);
                             }
                             if (k == T - 1) out[(s0 + m) * (2 * H) + dir * H + u] = h;
                         }
@@ -251,14 +238,14 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_bptt(const float* __restrict__
     }
     __syncthreads();
     const int64_t n_tiles = (S + 15) / 16;
-    const int H5 = 5 * H;
+    const int H5 = lstm_row_floats(H);
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t s0 = tile * 16;
         float dh[4] = {0.f, 0.f, 0.f, 0.f}, dc[4] = {0.f, 0.f, 0.f, 0.f};
         float cur[4][5], nxt[4][5];
         auto slot = [&](int i, int k) {                                         // the cell of (sequence 4 grp + i, step k of the walk, unit u)
             const int tt = dir ? T - 1 - k : k;
-            return saved + ((static_cast<int64_t>(dir) * S + s0 + 4 * grp + i) * T + tt) * H5 + u;
+            return lstm_saved_row(saved, static_cast<int64_t>(dir) * S + s0 + 4 * grp + i, T, tt, H5) + u;
         };
         auto fetch = [&](int k) {
 #pragma unroll
@@ -295,14 +282,8 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_bptt(const float* __restrict__
                     dc[i] = dct * fg;
                     const float dai = dct * gg * ig * (1.f - ig), daf = dct * cp * fg * (1.f - fg);
                     const float dag = dct * ig * (1.f - gg * gg), dao = dht * th * og * (1.f - og);
-                    if (u < H) {
-                        float* dp = dgs + m * pG + u;
-                        dp[0] = dai; dp[H] = daf; dp[2 * H] = dag; dp[3 * H] = dao;
-                    }
-                    if (ok) {
-                        float* sp = slot(i, k);
-                        sp[0] = dai; sp[H] = daf; sp[2 * H] = dag; sp[3 * H] = dao; sp[4 * H] = og * th;
-                    }
+                    if (u < H) lstm_da_store(dgs + m * pG + u, H, dai, daf, dag, dao);
+                    if (ok) { float* sp = slot(i, k); lstm_da_store(sp, H, dai, daf, dag, dao); sp[4 * H] = og * th; }      // h[t] where c[t] was
                 }
             }
             __syncthreads();
@@ -364,37 +345,31 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_wgrad(const IdT* __restrict__ 
                                                         float* __restrict__ partial) {
     extern __shared__ float cl_lds[];
     const int t = threadIdx.x, lane = t & 63, wid = __builtin_amdgcn_readfirstlane(t >> 6), grp = lane >> 4, col = lane & 15;
-    const int dir = blockIdx.y, I = Dw + Fc, N = I + H + 1, K4 = 4 * H, H5 = 5 * H, n_out = MT * NT;
+    const int dir = blockIdx.y, I = Dw + Fc, N = I + H + 1, K4 = 4 * H, H5 = lstm_row_floats(H), n_out = MT * NT;
     float* gs = cl_lds;                                                         // [2][16][pGs]
     float* xs = gs + 2 * 16 * pGs;                                              // [2][16][pXs]
     const int64_t sa = blockIdx.x * per, sb = min64(sa + per, S), n_rows = (sb - sa) * T, n_chunks = (n_rows + 15) / 16;
     const int lr = t >> 4, lc = t & 15;
     float gv[16], xv[21];
     auto load = [&](int64_t chunk) {                                            // row lr of the chunk: d_a and (x | h in front | 1)
-        const int64_t r = chunk * 16 + lr;
-        const bool rv = r < n_rows;
-        const int64_t s = rv ? sa + r / T : sa;
-        const int tt = rv ? static_cast<int>(r % T) : 0;
-        const float* sp = saved + ((static_cast<int64_t>(dir) * S + s) * T + tt) * H5;
-        const bool first = dir ? tt == T - 1 : tt == 0;
-        const float* hp = sp + (dir ? H5 : -H5) + 4 * H - I;                    // h of the step in front lies where its c was
+        const LstmWgradRow w = lstm_wgrad_row(saved, dir, S, T, H, H5, I, sa, n_rows, chunk * 16 + lr);
         int id = 0;
-        if (Dw > 0) id = cl_id(words + s * ld_words + tt, Vw);
+        if (Dw > 0) id = lstm_id(words + w.s * ld_words + w.tt, Vw);
         const float* trow = table + static_cast<int64_t>(id) * Dw;
-        const float* frow = feat + (s * T + tt) * ld_feat - Dw;
+        const float* frow = feat + (w.s * T + w.tt) * ld_feat - Dw;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int c = lc + 16 * j;
-            gv[j] = (rv && c < K4) ? sp[c] : 0.f;
+            gv[j] = (w.rv && c < K4) ? w.sp[c] : 0.f;
         }
 #pragma unroll
         for (int j = 0; j < 21; ++j) {
             const int c = lc + 16 * j;
             float v = 0.f;
-            if (rv && c < N) {
+            if (w.rv && c < N) {
                 if (c < Dw) v = trow[c];
                 else if (c < I) v = frow[c];
-                else if (c < I + H) v = first ? 0.f : hp[c];
+                else if (c < I + H) v = w.first ? 0.f : w.hp[c];
                 else v = 1.f;
             }
             xv[j] = v;
@@ -457,28 +432,6 @@ __global__ void __launch_bounds__(256) k_ctx_lstm_wgrad(const IdT* __restrict__ 
     }
 }
 
-// the G slabs added in slab order; cell (dir, j, n): n < I -> g_w_ih[j][n], n < I + H -> g_w_hh[j][n - I], n = I + H -> both bias gradients
-__global__ void __launch_bounds__(256) k_ctx_lstm_reduce(const float* __restrict__ partial, int32_t G, int32_t I, int32_t H,
-                                                         float* __restrict__ g_w_ih_f, float* __restrict__ g_w_hh_f, float* __restrict__ g_b_ih_f,
-                                                         float* __restrict__ g_b_hh_f, float* __restrict__ g_w_ih_r, float* __restrict__ g_w_hh_r,
-                                                         float* __restrict__ g_b_ih_r, float* __restrict__ g_b_hh_r) {
-    const int N = I + H + 1, per = 4 * H * N;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= 2 * per) return;
-    float sum = 0.f;
-#pragma unroll 8
-    for (int g = 0; g < G; ++g) sum += partial[static_cast<int64_t>(g) * 2 * per + i];
-    const int dir = i / per, r = i - dir * per, j = r / N, n = r - j * N;
-    if (n < I) {
-        (dir ? g_w_ih_r : g_w_ih_f)[static_cast<int64_t>(j) * I + n] = sum;
-    } else if (n < I + H) {
-        (dir ? g_w_hh_r : g_w_hh_f)[static_cast<int64_t>(j) * H + (n - I)] = sum;
-    } else {
-        (dir ? g_b_ih_r : g_b_ih_f)[j] = sum;
-        (dir ? g_b_hh_r : g_b_hh_f)[j] = sum;
-    }
-}
-
 template <typename IdT>
 int cl_launch_fwd(const void* words, int64_t ld_words, const float* table, int32_t Vw, const float* feat, int64_t ld_feat, const float* Wr,
                   int64_t S, int32_t T, int32_t Dw, int32_t Fc, int32_t H, const ClGeo& g, float* out, float* saved, hipStream_t st) {
@@ -528,7 +481,7 @@ extern "C" size_t recon_ctx_lstm_workspace_bytes(int64_t S, int32_t T, int32_t D
 
 extern "C" size_t recon_ctx_lstm_saved_bytes(int64_t S, int32_t T, int32_t Dw, int32_t Fc, int32_t H) {
     if (S <= 0 || !recon_ctx_lstm_supported(S, T, Dw, Fc, H)) return 0;
-    return static_cast<size_t>(2) * S * T * 5 * H * 4;
+    return recon::lstm_saved_bytes(S, T, H);
 }
 
 extern "C" int recon_ctx_lstm_fwd(const void* words, int32_t index_bytes, int64_t ld_words, const float* word_table, int32_t Vw, const float* feat,
@@ -542,8 +495,7 @@ extern "C" int recon_ctx_lstm_fwd(const void* words, int32_t index_bytes, int64_
     if (!feat || !w_ih || !w_hh || !b_ih || !b_hh || !w_ih_rev || !w_hh_rev || !b_ih_rev || !b_hh_rev || !out || !workspace || ld_feat < Fc)
         return RECON_ERR_INVALID;
     if (Dw > 0 && (!words || !word_table || Vw < 1 || ld_words < T)) return RECON_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 || reinterpret_cast<uintptr_t>(saved) % 16) return RECON_ERR_INVALID;
-    if (workspace_bytes < recon_ctx_lstm_workspace_bytes(S, T, Dw, Fc, H, 0)) return RECON_ERR_WORKSPACE;
+    if (const int rc = recon::lstm_buffer_checks(workspace, saved, workspace_bytes, recon_ctx_lstm_workspace_bytes(S, T, Dw, Fc, H, 0))) return rc;
     hipStream_t st = as_stream(stream);
     const recon::ClGeo g = recon::cl_geo(Dw, Fc, H);
     float* Wr = static_cast<float*>(workspace);
@@ -571,15 +523,10 @@ extern "C" int recon_ctx_lstm_bwd(const void* words, int32_t index_bytes, int64_
     if (!g_w_ih || !g_w_hh || !g_b_ih || !g_b_hh || !g_w_ih_rev || !g_w_hh_rev || !g_b_ih_rev || !g_b_hh_rev) return RECON_ERR_INVALID;
     hipStream_t st = as_stream(stream);
     const int32_t I = Dw + Fc;
-    if (S == 0) {
-        const size_t n_ih = static_cast<size_t>(4) * H * I, n_hh = static_cast<size_t>(4) * H * H, n_b = static_cast<size_t>(4) * H;
-        return recon::zero_fill({{g_w_ih, n_ih}, {g_w_ih_rev, n_ih}, {g_w_hh, n_hh}, {g_w_hh_rev, n_hh}, {g_b_ih, n_b}, {g_b_ih_rev, n_b}, {g_b_hh, n_b},
-                                 {g_b_hh_rev, n_b}}, st);
-    }
+    if (S == 0) return recon::lstm_zero_param_grads(g_w_ih, g_w_hh, g_b_ih, g_b_hh, g_w_ih_rev, g_w_hh_rev, g_b_ih_rev, g_b_hh_rev, I, H, st);
     if (!feat || !w_ih || !w_hh || !w_ih_rev || !w_hh_rev || !g_out || !saved || !workspace || ld_feat < Fc) return RECON_ERR_INVALID;
     if (Dw > 0 && (!words || !word_table || Vw < 1 || ld_words < T)) return RECON_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 || reinterpret_cast<uintptr_t>(saved) % 16) return RECON_ERR_INVALID;
-    if (workspace_bytes < recon_ctx_lstm_workspace_bytes(S, T, Dw, Fc, H, 1)) return RECON_ERR_WORKSPACE;
+    if (const int rc = recon::lstm_buffer_checks(workspace, saved, workspace_bytes, recon_ctx_lstm_workspace_bytes(S, T, Dw, Fc, H, 1))) return rc;
     const recon::ClGeo g = recon::cl_geo(Dw, Fc, H);
     {
         const size_t lds = static_cast<size_t>(g.bptt_floats) * 4;
@@ -601,8 +548,8 @@ extern "C" int recon_ctx_lstm_bwd(const void* words, int32_t index_bytes, int64_
     });
     if (rc != RECON_OK) return rc;
     RECON_CHECK_LAUNCH();
-    hipLaunchKernelGGL(recon::k_ctx_lstm_reduce, dim3(static_cast<unsigned>(ceil_div64(static_cast<int64_t>(2) * 4 * H * g.N, 256))), dim3(256), 0, st,
-                       partial, G, I, H, g_w_ih, g_w_hh, g_b_ih, g_b_hh, g_w_ih_rev, g_w_hh_rev, g_b_ih_rev, g_b_hh_rev);
+    hipLaunchKernelGGL(recon::k_lstm_reduce, dim3(static_cast<unsigned>(ceil_div64(static_cast<int64_t>(2) * 4 * H * g.N, 256))), dim3(256), 0, st,
+                       partial, G, I, H, 0, g_w_ih, g_w_hh, g_b_ih, g_b_hh, g_w_ih_rev, g_w_hh_rev, g_b_ih_rev, g_b_hh_rev, static_cast<float*>(nullptr));
     RECON_CHECK_LAUNCH();
     return RECON_OK;
 }

@@ -21,10 +21,9 @@
 //   through LDS as the A operand against W_hh (K = 4H, N = H).  It leaves d_a where the gates were and h[t] where c[t] was.  No d_x.
 // k_sent_lstm_wgrad: d_a^T (x | h[t'] | 1 | onehot(marker)) over the S T rows; grid (row groups) x (blocks of 128 gate rows) x direction,
 //   wave w owns gate rows [16 w, 16 w + 16) of the block and every column tile; 16 rows at a time through LDS.  Each workgroup writes its
-//   slab; k_sent_lstm_reduce adds the slabs in group order and scatters into the eight gradients and the class sums
+//   slab; k_lstm_reduce (lstm_common.h) adds the slabs in group order and scatters into the eight gradients and the class sums
 //   D[dir][j][v] = sum over the rows with marker v of d_a[j]; k_sent_lstm_dpos: d_pos[v] = sum_dir D[dir][:, v]^T W_ih[:, Dw:].
-#include <math.h>
-#include "ctx_enc_common.h"
+#include "lstm_common.h"
 
 namespace recon {
 namespace {
@@ -37,8 +36,6 @@ constexpr int kSlWideFrom = 2048;              // above this many sequences a ti
 constexpr int kSlMaxGroups = 32;               // row groups of the weight-gradient pass
 constexpr int kSlGateRows = 128;               // gate rows per workgroup of the weight-gradient pass
 constexpr int kSlSlots = 28;                   // column tiles of (x | h | 1 | onehot), in fours: ceil((128 + 256 + 1 + 16) / 16) = 26 -> 28
-
-inline int sl_pitch(int n, int mod32) { int p = n; while (p % 32 != mod32) ++p; return p; }
 
 struct SlGeo {
     int32_t I, Kx, K16, pA, NB, UB, NBp;       // forward
@@ -59,8 +56,8 @@ inline SlGeo sl_geo(int32_t Dw, int32_t P, int32_t H, int32_t Vp) {
     g.pG = 16 * g.K16b + 4;
     g.N = g.I + H + 1 + Vp;
     g.NT = (g.N + 15) / 16;
-    g.pGs = sl_pitch(kSlGateRows, 16);
-    g.pXs = sl_pitch(16 * ((g.NT + 3) / 4 * 4), 16);      // the products take the column tiles four at a time: zeros behind NT
+    g.pGs = lstm_pitch(kSlGateRows, 16);
+    g.pXs = lstm_pitch(16 * ((g.NT + 3) / 4 * 4), 16);      // the products take the column tiles four at a time: zeros behind NT
     g.JB = (4 * H + kSlGateRows - 1) / kSlGateRows;
     g.wr_dir = static_cast<int64_t>(g.NBp) * 4 * g.K16 * 256 + 4 * H;
     g.whr_dir = static_cast<int64_t>(g.NBp) * g.K16b * 256;
@@ -68,20 +65,12 @@ inline SlGeo sl_geo(int32_t Dw, int32_t P, int32_t H, int32_t Vp) {
 }
 inline int sl_row_tiles(int64_t S) { return S > kSlWideFrom ? 2 : 1; }
 
-__device__ __forceinline__ float sl_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
 // An address (or index) the compiler must form before the load that uses it: a load whose address is a select would otherwise be sunk into
 // per-column branches, and loads in branches wait for one another (one memory latency each instead of one for all of them).
 template <typename V>
 __device__ __forceinline__ void sl_opaque(V& v) { asm volatile("" : "+v"(v)); }
 // (behind the asm the compiler no longer knows the pointer is global and would issue a flat load, which every LDS wait waits for)
 __device__ __forceinline__ float sl_global(const float* p) { return *(const __attribute__((address_space(1))) float*)p; }
-
-template <typename IdT>
-__device__ __forceinline__ int sl_id(const IdT* p, int V) {
-    const int64_t v = static_cast<int64_t>(*p);
-    return static_cast<int>(v < 0 ? 0 : (v >= V ? V - 1 : v));
-}
 
 __global__ void __launch_bounds__(256) k_sent_lstm_prep_fwd(const float* __restrict__ w_ih_f, const float* __restrict__ w_hh_f,
                                                             const float* __restrict__ b_ih_f, const float* __restrict__ b_hh_f,
@@ -159,8 +148,8 @@ __global__ void __launch_bounds__(kSlThreads) k_sent_lstm_fwd(const IdT* __restr
     auto load_x = [&](int tt) {                                                 // row lr of step tt: columns lc, lc + TPR, ...
         int wi = 0, mk = 0;
         if (sv) {
-            wi = sl_id(sentence + b * ld_sent + tt, Vw);
-            mk = sl_id(markers + srow * ld_mark + tt, Vp);
+            wi = lstm_id(sentence + b * ld_sent + tt, Vw);
+            mk = lstm_id(markers + srow * ld_mark + tt, Vp);
         }
         const float* trow = table + static_cast<int64_t>(wi) * Dw;
         const float* prow = pos + static_cast<int64_t>(mk) * P - Dw;
@@ -253,16 +242,15 @@ __global__ void __launch_bounds__(kSlThreads) k_sent_lstm_fwd(const IdT* __restr
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int m = 16 * rt + 4 * grp + i;
-                        const float ig = sl_sigmoid(acc[rt][ub][0][i] + bias[ub][0]), fg = sl_sigmoid(acc[rt][ub][1][i] + bias[ub][1]);
-                        const float gg = tanhf(acc[rt][ub][2][i] + bias[ub][2]), og = sl_sigmoid(acc[rt][ub][3][i] + bias[ub][3]);
-                        c[rt][ub][i] = fmaf(fg, c[rt][ub][i], ig * gg);
-                        const float h = og * tanhf(c[rt][ub][i]);
+                        float ig, fg, gg, og;
+                        const float h = lstm_cell_fwd(acc[rt][ub][0][i], acc[rt][ub][1][i], acc[rt][ub][2][i], acc[rt][ub][3][i], bias[ub], c[rt][ub][i],
+                                                      ig, fg, gg, og);
                         if (u < H) {
                             nxt[m * pA + Kx + u] = h;
                             if (s0 + m < S) {
                                 if (saved) {
-                                    float* sp = saved + ((static_cast<int64_t>(dir) * S + s0 + m) * T + tt) * (5 * H) + u;
-                                    sp[0] = ig; sp[H] = fg; sp[2 * H] = gg; sp[3 * H] = og; sp[4 * H] = c[rt][ub][i];
+                                    float* sp = lstm_saved_row(saved, static_cast<int64_t>(dir) * S + s0 + m, T, tt, lstm_row_floats(H)) + u;
+                                    lstm_cell_store(sp, H, ig, fg, gg, og, c[rt][ub][i]);
                                 }
                                 if (k == T - 1) out[(s0 + m) * (2 * H) + dir * H + u] = h;
                             }
@@ -282,7 +270,7 @@ __global__ void __launch_bounds__(kSlThreads) k_sent_lstm_bptt(const float* __re
     extern __shared__ float sl_lds[];
     constexpr int M = 16 * RT;
     const int t = threadIdx.x, lane = t & 63, wid = __builtin_amdgcn_readfirstlane(t >> 6), grp = lane >> 4, col = lane & 15;
-    const int dir = blockIdx.y, H5 = 5 * H;
+    const int dir = blockIdx.y, H5 = lstm_row_floats(H);
     float* dgs = sl_lds;                                                        // [M][pG]: d_a of the step
     for (int i = t; i < M * pG; i += kSlThreads) dgs[i] = 0.f;                  // (the tail behind 4H stays zero)
     const int nb0 = wid * UB;
@@ -292,7 +280,7 @@ __global__ void __launch_bounds__(kSlThreads) k_sent_lstm_bptt(const float* __re
     float dh[RT][UB][4], dc[RT][UB][4], ct[RT][UB][4];
     auto slot = [&](int m, int k) {                                             // the cell row of (sequence s0 + m, step k of the walk)
         const int tt = dir ? T - 1 - k : k;
-        return saved + ((static_cast<int64_t>(dir) * S + s0 + m) * T + tt) * H5;
+        return lstm_saved_row(saved, static_cast<int64_t>(dir) * S + s0 + m, T, tt, H5);
     };
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
@@ -333,11 +321,8 @@ __global__ void __launch_bounds__(kSlThreads) k_sent_lstm_bptt(const float* __re
                         const float dai = dct * gg * ig * (1.f - ig), daf = dct * cp * fg * (1.f - fg);
                         const float dag = dct * ig * (1.f - gg * gg), dao = dht * th * og * (1.f - og);
                         ct[rt][ub][i] = cp;
-                        if (u < H) {
-                            float* dp = dgs + m * pG + u;
-                            dp[0] = dai; dp[H] = daf; dp[2 * H] = dag; dp[3 * H] = dao;
-                        }
-                        if (ok) { sp[0] = dai; sp[H] = daf; sp[2 * H] = dag; sp[3 * H] = dao; sp[4 * H] = og * th; }
+                        if (u < H) { float* dp = dgs + m * pG + u; lstm_da_store(dp, H, dai, daf, dag, dao); }
+                        if (ok) { lstm_da_store(sp, H, dai, daf, dag, dao); sp[4 * H] = og * th; }     // h[t] where c[t] was
                     }
                 }
         }
@@ -388,7 +373,7 @@ __global__ void __launch_bounds__(kSlThreads) k_sent_lstm_wgrad(const IdT* __res
                                                                 int32_t pXs, float* __restrict__ partial) {
     extern __shared__ float sl_lds[];
     const int t = threadIdx.x, lane = t & 63, wid = __builtin_amdgcn_readfirstlane(t >> 6), grp = lane >> 4, col = lane & 15;
-    const int dir = blockIdx.z, j0 = blockIdx.y * kSlGateRows, I = Dw + P, N = I + H + 1 + Vp, K4 = 4 * H, H5 = 5 * H, KW = (Dw + 31) >> 5;
+    const int dir = blockIdx.z, j0 = blockIdx.y * kSlGateRows, I = Dw + P, N = I + H + 1 + Vp, K4 = 4 * H, H5 = lstm_row_floats(H), KW = (Dw + 31) >> 5;
     float* gs = sl_lds;                                                         // [2][16][pGs]
     float* xs = gs + 2 * 16 * pGs;                                              // [2][16][pXs]
     const int NT4 = (NT + 3) / 4 * 4;
@@ -402,36 +387,30 @@ __global__ void __launch_bounds__(kSlThreads) k_sent_lstm_wgrad(const IdT* __res
     int row_mk = 0;
     bool row_rv = false, row_hv = false;
     auto load = [&](int64_t chunk) {                                            // row lr of the chunk: d_a and (x | h in front | 1 | onehot)
-        const int64_t r = chunk * 16 + lr;
-        const bool rv = r < n_rows;
-        const int64_t s = rv ? sa + r / T : sa;
-        const int tt = rv ? static_cast<int>(r % T) : 0;
-        const float* sp = saved + ((static_cast<int64_t>(dir) * S + s) * T + tt) * H5;
-        const bool first = dir ? tt == T - 1 : tt == 0;
-        const float* hp = sp + (dir ? H5 : -H5) + 4 * H - I;                    // h of the step in front lies where its c was
-        const int wi = sl_id(sentence + (s / C) * ld_sent + tt, Vw);
-        const int mk = sl_id(markers + s * ld_mark + tt, Vp);
+        const LstmWgradRow w = lstm_wgrad_row(saved, dir, S, T, H, H5, I, sa, n_rows, chunk * 16 + lr);
+        const int wi = lstm_id(sentence + (w.s / C) * ld_sent + w.tt, Vw);
+        const int mk = lstm_id(markers + w.s * ld_mark + w.tt, Vp);
         const float* trow = table + static_cast<int64_t>(wi) * Dw;
         const float* prow = pos + static_cast<int64_t>(mk) * P - Dw;
         row_mk = mk;
-        row_rv = rv;
-        row_hv = rv && !first;
+        row_rv = w.rv;
+        row_hv = w.rv && !w.first;
 #pragma unroll
         for (int j = 0; j < NG; ++j) {
             const int c = j0 + lc + 32 * j;
             int at = c < K4 ? c : 0;
             sl_opaque(at);
-            gv[j] = sp[at];
+            gv[j] = w.sp[at];
         }
 #pragma unroll
         for (int j = 0; j < NX; ++j) {
             const int c = lc + 32 * j;
-            const float* src = c < Dw ? trow + c : (c < I ? prow + c : ((c < I + H && row_hv) ? hp + c : trow));
+            const float* src = c < Dw ? trow + c : (c < I ? prow + c : ((c < I + H && row_hv) ? w.hp + c : trow));
             sl_opaque(src);
             xv[j] = sl_global(src);
         }
         if (bits) {
-            const int32_t* brow = bits + (s * T + tt) * KW;
+            const int32_t* brow = bits + (w.s * T + w.tt) * KW;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 int at = q < KW ? q : 0;
@@ -505,31 +484,6 @@ __global__ void __launch_bounds__(kSlThreads) k_sent_lstm_wgrad(const IdT* __res
                 if (j < K4 && n < N) slab[static_cast<int64_t>(j) * N + n] = acc[e][i];
             }
         }
-    }
-}
-
-// the G slabs added in slab order; cell (dir, j, n): n < I -> g_w_ih[j][n], n < I + H -> g_w_hh[j][n - I], n = I + H -> both bias
-// gradients, behind it the class sum D[dir][j][n - I - H - 1]
-__global__ void __launch_bounds__(256) k_sent_lstm_reduce(const float* __restrict__ partial, int32_t G, int32_t I, int32_t H, int32_t Vp,
-                                                          float* __restrict__ g_w_ih_f, float* __restrict__ g_w_hh_f, float* __restrict__ g_b_ih_f,
-                                                          float* __restrict__ g_b_hh_f, float* __restrict__ g_w_ih_r, float* __restrict__ g_w_hh_r,
-                                                          float* __restrict__ g_b_ih_r, float* __restrict__ g_b_hh_r, float* __restrict__ cls) {
-    const int N = I + H + 1 + Vp, per = 4 * H * N;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= 2 * per) return;
-    float sum = 0.f;
-#pragma unroll 8
-    for (int g = 0; g < G; ++g) sum += partial[static_cast<int64_t>(g) * 2 * per + i];
-    const int dir = i / per, r = i - dir * per, j = r / N, n = r - j * N;
-    if (n < I) {
-        (dir ? g_w_ih_r : g_w_ih_f)[static_cast<int64_t>(j) * I + n] = sum;
-    } else if (n < I + H) {
-        (dir ? g_w_hh_r : g_w_hh_f)[static_cast<int64_t>(j) * H + (n - I)] = sum;
-    } else if (n == I + H) {
-        (dir ? g_b_ih_r : g_b_ih_f)[j] = sum;
-        (dir ? g_b_hh_r : g_b_hh_f)[j] = sum;
-    } else {
-        cls[(static_cast<int64_t>(dir) * 4 * H + j) * Vp + (n - I - H - 1)] = sum;
     }
 }
 
@@ -623,7 +577,7 @@ extern "C" size_t recon_sent_lstm_workspace_bytes(int64_t B, int32_t C, int32_t 
 
 extern "C" size_t recon_sent_lstm_saved_bytes(int64_t B, int32_t C, int32_t T, int32_t Dw, int32_t P, int32_t H) {
     if (!recon_sent_lstm_supported(B, C, T, Dw, P, H)) return 0;
-    return static_cast<size_t>(2) * B * C * T * 5 * H * 4;
+    return recon::lstm_saved_bytes(B * C, T, H);
 }
 
 extern "C" int recon_sent_lstm_fwd(const void* sentence, const void* markers, int32_t index_bytes, int64_t ld_sentence, int64_t ld_markers,
@@ -638,8 +592,7 @@ extern "C" int recon_sent_lstm_fwd(const void* sentence, const void* markers, in
     if (!sentence || !markers || !word_table || !pos_table || !w_ih || !w_hh || !b_ih || !b_hh || !w_ih_rev || !w_hh_rev || !b_ih_rev || !b_hh_rev ||
         !out || !workspace || Vw < 1 || Vp < 1 || ld_sentence < T || ld_markers < T)
         return RECON_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 || reinterpret_cast<uintptr_t>(saved) % 16) return RECON_ERR_INVALID;
-    if (workspace_bytes < recon_sent_lstm_workspace_bytes(B, C, T, Dw, P, H, Vp, 0)) return RECON_ERR_WORKSPACE;
+    if (const int rc = recon::lstm_buffer_checks(workspace, saved, workspace_bytes, recon_sent_lstm_workspace_bytes(B, C, T, Dw, P, H, Vp, 0))) return rc;
     hipStream_t st = as_stream(stream);
     const recon::SlGeo g = recon::sl_geo(Dw, P, H, Vp);
     const int64_t S = B * C;
@@ -648,14 +601,11 @@ extern "C" int recon_sent_lstm_fwd(const void* sentence, const void* markers, in
                        w_ih_rev, w_hh_rev, b_ih_rev, b_hh_rev, g.I, H, g.Kx, g.K16, g.wr_dir, Wr);
     RECON_CHECK_LAUNCH();
     const recon::SlIds x{sentence, markers, ld_sentence, ld_markers, word_table, Vw, pos_table, Vp, keep_bits, keep_scale};
-    const bool wide = recon::sl_row_tiles(S) == 2, two = g.UB == 2;
     const int rc = recon::dispatch_ids(index_bytes, [&](auto id) {
-        using IdT = typename decltype(id)::type;
-        float* sv = static_cast<float*>(saved);
-        if (wide) return two ? recon::sl_launch_fwd<IdT, 2, 2>(x, Wr, S, C, T, Dw, P, H, g, out, sv, st)
-                             : recon::sl_launch_fwd<IdT, 2, 1>(x, Wr, S, C, T, Dw, P, H, g, out, sv, st);
-        return two ? recon::sl_launch_fwd<IdT, 1, 2>(x, Wr, S, C, T, Dw, P, H, g, out, sv, st)
-                   : recon::sl_launch_fwd<IdT, 1, 1>(x, Wr, S, C, T, Dw, P, H, g, out, sv, st);
+        return recon::dispatch_tile(recon::sl_row_tiles(S) == 2, g.UB == 2, [&](auto rt, auto ub) {
+            return recon::sl_launch_fwd<typename decltype(id)::type, decltype(rt)::value, decltype(ub)::value>(x, Wr, S, C, T, Dw, P, H, g, out,
+                                                                                                              static_cast<float*>(saved), st);
+        });
     });
     if (rc != RECON_OK) return rc;
     RECON_CHECK_LAUNCH();
@@ -676,15 +626,13 @@ extern "C" int recon_sent_lstm_bwd(const void* sentence, const void* markers, in
     hipStream_t st = as_stream(stream);
     const int32_t I = Dw + P;
     if (B == 0 || C == 0) {
-        const size_t n_ih = static_cast<size_t>(4) * H * I, n_hh = static_cast<size_t>(4) * H * H, n_b = static_cast<size_t>(4) * H;
-        return recon::zero_fill({{g_pos_table, static_cast<size_t>(Vp) * P}, {g_w_ih, n_ih}, {g_w_ih_rev, n_ih}, {g_w_hh, n_hh}, {g_w_hh_rev, n_hh},
-                                 {g_b_ih, n_b}, {g_b_ih_rev, n_b}, {g_b_hh, n_b}, {g_b_hh_rev, n_b}}, st);
+        if (const int rc = recon::zero_fill({{g_pos_table, static_cast<size_t>(Vp) * P}}, st)) return rc;
+        return recon::lstm_zero_param_grads(g_w_ih, g_w_hh, g_b_ih, g_b_hh, g_w_ih_rev, g_w_hh_rev, g_b_ih_rev, g_b_hh_rev, I, H, st);
     }
     if (!sentence || !markers || !word_table || !pos_table || !w_ih || !w_hh || !w_ih_rev || !w_hh_rev || !g_out || !saved || !workspace || Vw < 1 ||
         ld_sentence < T || ld_markers < T)
         return RECON_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 || reinterpret_cast<uintptr_t>(saved) % 16) return RECON_ERR_INVALID;
-    if (workspace_bytes < recon_sent_lstm_workspace_bytes(B, C, T, Dw, P, H, Vp, 1)) return RECON_ERR_WORKSPACE;
+    if (const int rc = recon::lstm_buffer_checks(workspace, saved, workspace_bytes, recon_sent_lstm_workspace_bytes(B, C, T, Dw, P, H, Vp, 1))) return rc;
     const recon::SlGeo g = recon::sl_geo(Dw, P, H, Vp);
     const int64_t S = B * C;
     const recon::SlBwdWs w = recon::sl_bwd_ws(S, H, g, Vp);
@@ -695,21 +643,18 @@ extern "C" int recon_sent_lstm_bwd(const void* sentence, const void* markers, in
     hipLaunchKernelGGL(recon::k_sent_lstm_prep_bwd, dim3(static_cast<unsigned>(ceil_div64(2 * g.whr_dir, 256))), dim3(256), 0, st, w_hh, w_hh_rev, H,
                        g.K16b, g.whr_dir, Whr);
     RECON_CHECK_LAUNCH();
-    {
-        const bool wide = recon::sl_row_tiles(S) == 2, two = g.UB == 2;
-        float* sv = static_cast<float*>(saved);
-        const int rc = wide ? (two ? recon::sl_launch_bptt<2, 2>(Whr, g_out, sv, S, T, H, g, st) : recon::sl_launch_bptt<2, 1>(Whr, g_out, sv, S, T, H, g, st))
-                            : (two ? recon::sl_launch_bptt<1, 2>(Whr, g_out, sv, S, T, H, g, st) : recon::sl_launch_bptt<1, 1>(Whr, g_out, sv, S, T, H, g, st));
-        if (rc != RECON_OK) return rc;
-        RECON_CHECK_LAUNCH();
-    }
+    const int rc_bptt = recon::dispatch_tile(recon::sl_row_tiles(S) == 2, g.UB == 2, [&](auto rt, auto ub) {
+        return recon::sl_launch_bptt<decltype(rt)::value, decltype(ub)::value>(Whr, g_out, static_cast<float*>(saved), S, T, H, g, st);
+    });
+    if (rc_bptt != RECON_OK) return rc_bptt;
+    RECON_CHECK_LAUNCH();
     const recon::SlIds x{sentence, markers, ld_sentence, ld_markers, word_table, Vw, pos_table, Vp, keep_bits, keep_scale};
     const int rc = recon::dispatch_ids(index_bytes, [&](auto id) {
         return recon::sl_launch_wgrad<typename decltype(id)::type>(x, static_cast<const float*>(saved), S, C, T, Dw, P, H, w.per, w.G, g, partial, st);
     });
     if (rc != RECON_OK) return rc;
     RECON_CHECK_LAUNCH();
-    hipLaunchKernelGGL(recon::k_sent_lstm_reduce, dim3(static_cast<unsigned>(ceil_div64(static_cast<int64_t>(2) * 4 * H * g.N, 256))), dim3(256), 0, st,
+    hipLaunchKernelGGL(recon::k_lstm_reduce, dim3(static_cast<unsigned>(ceil_div64(static_cast<int64_t>(2) * 4 * H * g.N, 256))), dim3(256), 0, st,
                        partial, w.G, I, H, Vp, g_w_ih, g_w_hh, g_b_ih, g_b_hh, g_w_ih_rev, g_w_hh_rev, g_b_ih_rev, g_b_hh_rev, cls);
     RECON_CHECK_LAUNCH();
     hipLaunchKernelGGL(recon::k_sent_lstm_dpos, dim3(static_cast<unsigned>(Vp * P)), dim3(64), 0, st, cls, w_ih,

@@ -21,9 +21,9 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
+from . import _lib, _lstm
+from ._lstm import _PARAMS, _kernel_lstm
 from .char_features import PackedKeep
-from .context_lstm import _PARAMS, _kernel_lstm
 
 MAX_POS_ROWS = 16                 # kSlMaxVp of csrc/sent_lstm.hip: one-hot columns of the weight-gradient pass
 BWD_MAX_ROW_GROUPS = 32           # kSlMaxGroups: the weight-gradient pass gives each row group ceil(B C / 32) sequences
@@ -87,16 +87,13 @@ class _PairSentenceStates(torch.autograd.Function):
         need = ctx.needs_input_grad
         B, C, T, Dw, P, H = ctx.geo
         Vw, Vp = word_table.shape[0], pos_table.shape[0]
-        if torch.is_grad_enabled() or ctx.consumed:
-            # create_graph (the gradient itself must be differentiable; MIOpen's RNN backward is not) or a second backward over a retained
-            # graph (the first consumed the saved state): recompute through the stock ops, the native ones, which differentiate twice and
-            # run a backward in eval mode too
+        def stock():
             keep = None if bits is None else PackedKeep(bits, ctx.scale, Dw).factors(word_table.dtype).view(B, C, T, Dw)
             ss, mm = s.clamp(0, Vw - 1), m.clamp(0, Vp - 1)                                      # as the kernels clamp them
-            with torch.backends.cudnn.flags(enabled=False):
-                return (None,) * 8 + _lib.recompute_grads(lambda: _chain(ctx.rnn, ss, mm, word_table, pos_table, keep, ctx.pos_padding_idx),
-                                                          (pos_table,) + tuple(params), need[8:], g_out, torch.is_grad_enabled())
-        ctx.consumed = True
+            return _chain(ctx.rnn, ss, mm, word_table, pos_table, keep, ctx.pos_padding_idx)
+        grads = _lstm._recompute(ctx, stock, (pos_table,) + tuple(params), need[8:], g_out)
+        if grads is not None:
+            return (None,) * 8 + grads
         L = _lib.lib()
         s, ld_s, m, ld_m = _ids(s, m)
         table, pos = word_table.detach().contiguous(), pos_table.detach().contiguous()
@@ -161,8 +158,7 @@ def pair_sentence_states(rnn, sentence, markers, word_table, pos_table, keep=Non
     if not (sentence.device == markers.device == word_table.device == pos_table.device and (keep is None or keep_device == sentence.device)):
         raise ValueError("pair_sentence_states: the tensors must be on one device")
     if B * C == 0:
-        dirs = 2 if rnn.bidirectional else 1
-        return torch.empty(B, C, dirs * (rnn.proj_size or rnn.hidden_size), dtype=word_table.dtype, device=word_table.device)
+        return _lstm._empty_states(rnn, (B, C), word_table)
     if _fused(rnn, sentence, markers, word_table, pos_table, keep):
         params = [getattr(rnn, n) for n in _PARAMS]
         # (inside the function grad mode is off and needs_input_grad ignores no_grad: whether a backward can follow is decided here)
