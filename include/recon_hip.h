@@ -1137,6 +1137,40 @@ int recon_sent_lstm_bwd(const void* sentence, const void* markers, int32_t index
                         float* g_b_hh_rev, void* workspace, size_t workspace_bytes, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * E10 The pair states' transition projections (csrc/pair_trans.hip): the L per-hop projections of the pair states in front of the
+ *     propagation, T_l = act(x W_l^T + b_l) for l < L  (GPGNN models/models.py:185-192 tied, :240-249 untied; RECON_EAC :395-402 and
+ *     :450-459; RECON_EAC_KGGAT :605-612 and :660-669; RECON :843-850 and :898-907).  x [M][K] with row stride ld_x (elements), W_l
+ *     [N1][K], b_l [N1], out[l] and g_out[l] [M][N1], all fp32; everything but x contiguous.  w, b, out, g_out, g_w, g_b are HOST arrays of L
+ *     device pointers (like recon_prop_args.adj).  act is RECON_ACT_*; act' is taken from the OUTPUT (relu T > 0, tanh 1 - T^2, linear 1)
+ *     and d_pre_l = g_out[l] act'(out[l]) is formed while an operand is staged, never written.  Everything is fp32 on
+ *     v_mfma_f32_16x16x4_f32, without atomics, every sum in an order the shape alone decides: bitwise identical from run to run.  Status
+ *     codes and the 16-byte alignment of workspace are those of the E8 / E9 entries.
+ * ------------------------------------------------------------------------------------------*/
+/* Shapes the kernels take (models/models.py:185-192, :240-249): 0 <= M <= 2^24, K a multiple of 4 in 4..1024, 1 <= N1 <= 1024,
+ * 1 <= L <= 8.  The fwd / bwd entries also need 16-byte aligned x and W_l and ld_x % 4 == 0.  Everything else answers
+ * RECON_ERR_UNSUPPORTED and writes nothing; the caller then runs the stock ops. */
+int recon_pair_transitions_supported(int64_t M, int32_t K, int32_t N1, int32_t L);
+/* Bytes of the workspace (models/models.py:185-192, :240-249).  Forward (backward = 0): none.  Backward (backward = 1): G slabs of
+ * L N1 (K + 1) floats, one per row group, where G = min(8, ceil(M / 32)) and a group is per = ceil(M / G) consecutive rows: a function of
+ * M alone.  16-byte aligned, any contents; 0 for a shape recon_pair_transitions_supported refuses and for M == 0. */
+size_t recon_pair_transitions_workspace_bytes(int64_t M, int32_t K, int32_t N1, int32_t L, int32_t backward);
+/* Forward (models/models.py:185-192, :240-249; the other models' lines above): [M][K] x [K][L N1] in 64 x 64 tiles, the bias (b NULL or
+ * b[l] NULL: none) and the activation in the epilogue, stored into out[l].  A column tile may straddle a layer boundary.  M == 0: nothing
+ * is launched.  One launch. */
+int recon_pair_transitions_fwd(const float* x, int64_t ld_x, const float* const* w, const float* const* b, int64_t M, int32_t K, int32_t N1,
+                               int32_t L, int32_t act, float* const* out, recon_stream_t stream);
+/* Backward (models/models.py:185-192, :240-249) from the forward's outputs, which it leaves as they are (any number of backwards per
+ * forward, the same bits each time).  g_out[l] NULL: that output received no gradient; the layer adds nothing to g_x and its wanted
+ * parameter gradients receive zeros.  g_x [M][K] contiguous or NULL (not wanted: its launch is skipped) = sum_l d_pre_l W_l, reduced in
+ * the order l ascending, n ascending.  g_w[l] [N1][K] and g_b[l] [N1] (g_w, g_b or single entries NULL: not wanted; no entry wanted: both
+ * launches are skipped) = d_pre_l^T (x | 1): workgroup (column tile, layer and row tile, g) writes its part of slab g of the workspace
+ * over row group g, then the slabs are added in group order.  M == 0 writes zeros to every wanted gradient and launches no kernel.
+ * Three launches: one for g_x, two for the parameters. */
+int recon_pair_transitions_bwd(const float* x, int64_t ld_x, const float* const* w, const float* const* out, const float* const* g_out,
+                               int64_t M, int32_t K, int32_t N1, int32_t L, int32_t act, float* g_x, float* const* g_w, float* const* g_b,
+                               void* workspace, size_t workspace_bytes, recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
  *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
  * ------------------------------------------------------------------------------------------*/

@@ -6,3 +6,4 @@ from .translation import translation_residuals  # noqa: E402,F401
 from .char_features import char_word_features  # noqa: E402,F401
 from .context_lstm import context_line_states  # noqa: E402,F401
 from .sentence_lstm import pair_sentence_states  # noqa: E402,F401
+from .transitions import pair_transitions  # noqa: E402,F401

@@ -3,8 +3,9 @@ same constructor, forward signature and state_dict keys (word_embedding.weight, 
 representation_to_adj[.i].weight/bias, identity_transformation, start_embedding, head_indices, tail_indices,
 linear3.*), so a checkpoint written by the reference's train.py:415-416 loads unchanged.  The sentence encoder's
 embeddings and LSTM run as `pair_sentence_states` (csrc/sent_lstm.hip; the stock PyTorch-ROCm ops where it does not apply), its
-Linear stays stock (rocBLAS); the block-adjacency construction and the L-hop propagation with its fused head*tail gather run on
-the HIP kernels of csrc/prop.hip.  SURVEY.md 8f row N3."""
+per-hop projections as `pair_transitions` (csrc/pair_trans.hip; `F.linear` and the activation where it does not apply); the
+block-adjacency construction and the L-hop propagation with its fused head*tail gather run on the HIP kernels of csrc/prop.hip.
+SURVEY.md 8f row N3."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -14,6 +15,7 @@ from .propagation import (build_block_adjacency, propagate, propagate_blocks, ma
 from .char_features import char_word_features, draw_packed_keep
 from .context_lstm import context_line_states
 from .sentence_lstm import pair_sentence_states
+from .transitions import pair_transitions
 
 
 class GPGNN(nn.Module):
@@ -85,6 +87,27 @@ class GPGNN(nn.Module):
         rnn_result = torch.cat([rnn_output[:, -1, :u], rnn_output[:, 0, u:]], dim=1).view(B, C, -1)
         return self.dropout2(rnn_result)
 
+    # fused_transitions: run the L per-hop projections of the pair states as `pair_transitions` (csrc/pair_trans.hip) whenever every
+    # projection is a plain nn.Linear; DESIGN.md section 22 says why this is the default it is.
+    fused_transitions = True
+
+    def transitions(self, rnn_result):
+        """[B, C, 2*units1] -> the list of L transition tensors [B, C, (2d)^2] `propagate_blocks` takes.  Tied (models/models.py:186-192): ONE
+        tensor under `non-linear`, repeated L times; untied (:240-249): one per hop under `non-linear1`."""
+        p, L = self.p, self.p['layer_number']
+        name = p['non-linear'] if self.tied else p['non-linear1']
+        lins = [self.representation_to_adj] if self.tied else [self.representation_to_adj[i] for i in range(L)]
+        if self.fused_transitions and all(type(lin) is nn.Linear for lin in lins):
+            Ts = list(pair_transitions(rnn_result, [lin.weight for lin in lins], [lin.bias for lin in lins], name))
+        else:
+            Ts = []
+            for lin in lins:
+                T = lin(rnn_result)
+                if name != "linear":
+                    T = getattr(F, name)(T)
+                Ts.append(T)
+        return Ts * L if self.tied else Ts
+
     def forward(self, sentence_input, entity_markers, num_entities=None):
         """(B, max_sent_len), (B, C, max_sent_len) -> (B*C, n_out).  Unlike the reference, any batch size works
         (its head/tail index tensors bake in 50, models/models.py:138-142; the kernels take the [C,2d] pattern)."""
@@ -92,18 +115,7 @@ class GPGNN(nn.Module):
         n, L = p['max_num_nodes'], p['layer_number']
         rnn_result = self.encode(sentence_input, entity_markers)
         B = rnn_result.size(0)
-        if self.tied:                                                    # :186-236: ONE transition tensor, `non-linear` on it
-            T = self.representation_to_adj(rnn_result)
-            if p['non-linear'] != "linear":
-                T = getattr(F, p['non-linear'])(T)
-            Ts = [T] * L
-        else:                                                            # :238-259: one per hop, `non-linear1` on it
-            Ts = []
-            for i in range(L):
-                T = self.representation_to_adj[i](rnn_result)
-                if p['non-linear1'] != "linear":
-                    T = getattr(F, p['non-linear1'])(T)
-                Ts.append(T)
+        Ts = self.transitions(rnn_result)
         # :240-274 — block adjacency + propagation; fused (A_l never materialised) where the kernels allow, else build_block_adjacency + propagate
         relation = propagate_blocks(Ts, self.identity_transformation, n, self.start_embedding, p['non-linear1'], self.head_indices[0], self.tail_indices[0])
         return self.linear3(relation).view(B * self.MAX_EDGES_PER_GRAPH, -1)
@@ -215,12 +227,7 @@ class RECON_EAC(GPGNN):
         h0 = make_start_entity_embeddings(entity_embeddings, entities_position, None, p['embedding_dim'],
                                           max_occurred_entity_in_batch_pos, self.start_embedding, max_num_nodes=n)     # :365
         rnn_result = self.encode(sentence_input, entity_markers)
-        Ts = []
-        for i in range(L):                                               # :447-466
-            T = self.representation_to_adj[i](rnn_result)
-            if p['non-linear1'] != "linear":
-                T = getattr(F, p['non-linear1'])(T)
-            Ts.append(T)
+        Ts = self.transitions(rnn_result)                                # :447-466
         return propagate_blocks(Ts, self.identity_transformation, n, h0, p['non-linear1'], self.head_indices[0], self.tail_indices[0])     # :447-484
 
     def forward(self, sentence_input, entity_markers, num_entities, unique_entites, entity_indices, context_words, context_chars,
