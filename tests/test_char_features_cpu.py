@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import ROOT, load_golden
+from op_checks import state_dict_of
 
 NAMES = ("recon_char_features_supported", "recon_char_features_workspace_bytes", "recon_char_features_fwd", "recon_char_features_bwd")
 #        S    W  max_char cfs C   Fo  V
@@ -59,7 +60,28 @@ def test_shapes_outside_the_kernels_are_refused():
     assert L.recon_char_features_fwd(fake, 8, 26, fake, fake, fake, None, 4, 2, 12, 3, 90, 50, 50, fake, None, fake, 16, None) == -4
 
 
-def _inputs(S, W, max_char, cfs, C, Fo, V, seed, dtype=torch.float32):
+def inputs(S, W, max_char, cfs, C, Fo, V, seed=0):
+    """Per sequence a random number of words (0..W), each 1..max_char random ids in [1, V), the rest padding; E ~ N(0, 1) with row 0 zero,
+    W xavier-scaled, bias ~ 0.1 N(0, 1).  CPU tensors.  The GPU files' cases: the seed is mixed with the shape, g_out is drawn too."""
+    g = torch.Generator().manual_seed(1000 * seed + S + W + max_char + cfs + C + Fo + V)
+    span = max_char + cfs - 1
+    chars = torch.zeros(S, cfs - 1 + W * span, dtype=torch.int64)
+    n_words = torch.randint(0, W + 1, (S,), generator=g)
+    lens = torch.randint(1, max_char + 1, (S, W), generator=g)
+    ids = torch.randint(1, V, (S, W, span), generator=g)
+    live = (torch.arange(span)[None, None, :] < lens[:, :, None]) & (torch.arange(W)[None, :, None] < n_words[:, None, None])
+    chars[:, :W * span] = (ids * live).view(S, W * span)
+    E = torch.randn(V, C, generator=g)
+    E[0] = 0
+    Wc = torch.randn(Fo, C, cfs, generator=g) * (2.0 / (C * cfs + Fo * cfs)) ** 0.5
+    b = 0.1 * torch.randn(Fo, generator=g)
+    g_out = torch.randn(S, W, Fo, generator=g)
+    return chars, E, Wc, b, span, g_out
+
+
+def inputs_word_by_word(S, W, max_char, cfs, C, Fo, V, seed, dtype=torch.float32):
+    """The CPU tests' inputs: the seed as it is, the ids drawn word by word in a Python loop (another stream than `inputs`), a dtype,
+    no g_out."""
     g = torch.Generator().manual_seed(seed)
     span = max_char + cfs - 1
     chars = torch.zeros(S, cfs - 1 + W * span, dtype=torch.int64)
@@ -74,8 +96,8 @@ def _inputs(S, W, max_char, cfs, C, Fo, V, seed, dtype=torch.float32):
     return chars, E, Wc, b, span
 
 
-def _stock(chars, E, Wc, b, span, keep=None):
-    """The lines EntityEmbedding.forward had (models/models.py:57-61), written out here."""
+def stock(chars, E, Wc, b, span, keep=None):
+    """models/models.py:57-61 written out: embedding (* dropout factors), conv1d, max_pool1d, tanh."""
     x = F.embedding(chars, E, padding_idx=0)
     if keep is not None:
         x = x * keep
@@ -86,11 +108,11 @@ def _stock(chars, E, Wc, b, span, keep=None):
 @pytest.mark.parametrize("ids", [torch.int64, torch.int32])
 def test_cpu_tensors_run_the_stock_sequence_bit_for_bit(with_keep, ids):
     from recon_amd import char_word_features
-    chars, E, Wc, b, span = _inputs(7, 3, 4, 3, 5, 6, 9, seed=1)
+    chars, E, Wc, b, span = inputs_word_by_word(7, 3, 4, 3, 5, 6, 9, seed=1)
     keep = F.dropout(torch.ones(chars.shape[0], chars.shape[1], 5), 0.5, True) if with_keep else None
     G = torch.randn(7, 3, 6)
     grads = []
-    for fn in (lambda *a: char_word_features(a[0].to(ids), *a[1:], keep=keep), lambda *a: _stock(*a, keep=keep)):
+    for fn in (lambda *a: char_word_features(a[0].to(ids), *a[1:], keep=keep), lambda *a: stock(*a, keep=keep)):
         p = [t.clone().requires_grad_(True) for t in (E, Wc, b)]
         y = fn(chars, *p, span)
         (y * G).sum().backward()
@@ -103,7 +125,7 @@ def test_cpu_tensors_run_the_stock_sequence_bit_for_bit(with_keep, ids):
 
 def test_shape_and_dtype_checks_raise():
     from recon_amd import char_word_features
-    chars, E, Wc, b, span = _inputs(4, 3, 4, 3, 5, 6, 9, seed=2)
+    chars, E, Wc, b, span = inputs_word_by_word(4, 3, 4, 3, 5, 6, 9, seed=2)
     with pytest.raises(ValueError):
         char_word_features(chars[:, :-1], E, Wc, b, span)                           # Lc != cfs - 1 + W span
     with pytest.raises(ValueError):
@@ -161,7 +183,7 @@ def fixture_model(g):
     dropout factors replayed through draw_keep."""
     import torch.nn as nn
     from recon_amd.gpgnn import EntityEmbedding
-    sd = {k[3:]: torch.from_numpy(np.asarray(v)) for k, v in g.items() if k.startswith("sd.")}
+    sd = state_dict_of(g)
     (V, C), (Fo, _, cfs) = sd["char_embeddings.embeddings.weight"].shape, sd["conv1d.weight"].shape
     n_words, word_dim = sd["word_embeddings.weight"].shape
     hidden = sd["lstm.weight_hh_l0"].shape[1]

@@ -1,10 +1,8 @@
 """recon_amd.char_word_features (csrc/char_cnn.hip) against the stock sequence of models/models.py:57-61 in fp64 on the CPU, and against
 the fixtures written from the reference's EntityEmbedding.
 
-Tolerance of value and gradients (the scheme of test_translation_gpu.py): the stock chain's own error on the GPU against fp64 on the same
-inputs is measured in the test, relative to max |oracle|; the op has to stay within min(max(4 e_chain, 2^-20), 2e-5): 4x for another
-summation order, 2^-20 the bound of test_sgemm_hx2, 2e-5 the figure README.md gives.  The figures measured on an MI355X are in DESIGN.md
-section 18.
+Tolerance of value and gradients: `op_checks.bound` of the stock chain's own error on the GPU against fp64 on the same inputs, measured in
+the test.  The figures measured on an MI355X are in DESIGN.md section 18.
 
 Gradient cells near a tie: a window whose two best positions differ by less than fp32 rounding can pick another position than fp64 does,
 and the gradient then differs discretely, which is not an error.  g_out is zeroed at every (s, w, o) where, in fp64, the maximum and the
@@ -18,6 +16,8 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden
+from op_checks import band_failures, bound, calls_of, close, dev, peak_bytes, rel_err, rounded, same
+from test_char_features_cpu import fixture_model, inputs, stock
 
 pytestmark = pytest.mark.gpu
 
@@ -26,45 +26,6 @@ CASES = [(1, 1, 1, 1, 1, 1, 2), (3, 3, 4, 3, 5, 6, 9), (24, 5, 4, 2, 3, 3, 8), (
          (19, 3, 10, 3, 50, 50, 300), (130, 32, 10, 3, 50, 50, 90)]
 REF_GEOMETRY = (130, 32, 10, 3, 50, 50, 90)
 PARAMS = ("emb_weight", "conv_weight", "conv_bias")
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def bound(e_chain):
-    return min(max(4 * e_chain, 2.0 ** -20), 2e-5)
-
-
-def rel_err(got, ref):
-    return ((got.detach().double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
-
-
-def inputs(S, W, max_char, cfs, C, Fo, V, seed=0):
-    """Per sequence a random number of words (0..W), each 1..max_char random ids in [1, V), the rest padding; E ~ N(0, 1) with row 0 zero,
-    W xavier-scaled, bias ~ 0.1 N(0, 1).  CPU tensors."""
-    g = torch.Generator().manual_seed(1000 * seed + S + W + max_char + cfs + C + Fo + V)
-    span = max_char + cfs - 1
-    chars = torch.zeros(S, cfs - 1 + W * span, dtype=torch.int64)
-    n_words = torch.randint(0, W + 1, (S,), generator=g)
-    lens = torch.randint(1, max_char + 1, (S, W), generator=g)
-    ids = torch.randint(1, V, (S, W, span), generator=g)
-    live = (torch.arange(span)[None, None, :] < lens[:, :, None]) & (torch.arange(W)[None, :, None] < n_words[:, None, None])
-    chars[:, :W * span] = (ids * live).view(S, W * span)
-    E = torch.randn(V, C, generator=g)
-    E[0] = 0
-    Wc = torch.randn(Fo, C, cfs, generator=g) * (2.0 / (C * cfs + Fo * cfs)) ** 0.5
-    b = 0.1 * torch.randn(Fo, generator=g)
-    g_out = torch.randn(S, W, Fo, generator=g)
-    return chars, E, Wc, b, span, g_out
-
-
-def stock(chars, E, Wc, b, span, keep=None):
-    """models/models.py:57-61 written out: embedding (* dropout factors), conv1d, max_pool1d, tanh."""
-    x = F.embedding(chars, E, padding_idx=0)
-    if keep is not None:
-        x = x * keep
-    return torch.tanh(F.max_pool1d(F.conv1d(x.permute(0, 2, 1), Wc, b), span, span)).permute(0, 2, 1)
 
 
 def near_ties(chars, E, Wc, b, span, margin=1e-5):
@@ -106,12 +67,8 @@ def run(fn, chars, E, Wc, b, span, g_out, **kw):
 
 
 def fused_ran(monkeypatch):
-    """Counts the calls of the fused autograd function during a test."""
     from recon_amd import char_features
-    calls = []
-    real = char_features._CharWordFeatures.apply
-    monkeypatch.setattr(char_features._CharWordFeatures, "apply", staticmethod(lambda *a: (calls.append(1), real(*a))[1]))
-    return calls
+    return calls_of(monkeypatch, char_features._CharWordFeatures, "apply")
 
 
 @pytest.mark.parametrize("shape", CASES, ids=lambda s: "x".join(map(str, s)))
@@ -129,12 +86,7 @@ def test_value_and_gradients(shape, monkeypatch):
     chain = run(_chain, chars, E, Wc, b, span, g_out)
     assert fused[0].shape == (S, W, Fo) and fused[1].shape == E.shape and fused[2].shape == Wc.shape and fused[3].shape == b.shape
     print("char_features %s: %d of %d cells near a tie" % (shape, n_ties, S * W * Fo))
-    failures = []
-    for what, f, c, r in zip(("out",) + PARAMS, fused, chain, ref):
-        e_f, e_c = rel_err(f, r), rel_err(c, r)
-        print("char_features %s %s: fused %.3e chain %.3e (of max |ref|)" % (shape, what, e_f, e_c))
-        if not e_f <= bound(e_c):
-            failures.append((what, e_f, e_c))
+    failures = band_failures(("out",) + PARAMS, fused, chain, ref, "char_features %s" % (shape,))
     assert not failures, failures
     assert torch.count_nonzero(fused[1][0]) == 0                                    # the padding row's gradient
 
@@ -144,8 +96,7 @@ def test_int32_ids():
     chars, E, Wc, b, span, g_out, ref, _ = case((7, 2, 10, 3, 50, 50, 90))
     a = run(char_word_features, chars, E, Wc, b, span, g_out)
     c = run(char_word_features, chars.to(torch.int32), E, Wc, b, span, g_out)
-    for x, y in zip(a, c):
-        assert torch.equal(x, y)
+    same(a, c)
     assert rel_err(c[0], ref[0]) <= 2e-5
 
 
@@ -156,8 +107,7 @@ def test_strided_ids_are_read_in_place():
     wide[:, :chars.shape[1]] = chars
     a = run(char_word_features, chars, E, Wc, b, span, g_out)
     c = run(lambda ch, *r: char_word_features(ch[:, :chars.shape[1]], *r), wide, E, Wc, b, span, g_out)
-    for x, y in zip(a, c):
-        assert torch.equal(x, y)
+    same(a, c)
 
 
 def test_all_padding_gives_tanh_of_the_bias_exactly():
@@ -208,8 +158,7 @@ def test_dropout_factors_run_the_stock_chain(monkeypatch):
     a = run(char_word_features, chars, E, Wc, b, span, g_out, keep=keep)
     c = run(stock, chars, E, Wc, b, span, g_out, keep=keep)
     assert not calls
-    for x, y in zip(a, c):
-        assert torch.equal(x, y)
+    same(a, c)
 
 
 def test_create_graph_stays_differentiable():
@@ -252,8 +201,6 @@ def test_fixture_pool_output(name):
 def test_fixture_entity_embedding(name, monkeypatch):
     """EntityEmbedding with the fixture's parameters (strict load) against the reference module's output and the three gradients; the
     training fixture replays its recorded factors through draw_keep.  The bound is the whole-model LSTM fixtures' (test_prop_gpu.py)."""
-    from test_gat_gpu import close
-    from tests.test_char_features_cpu import fixture_model
     g = load_golden(name)
     m = fixture_model(g)
     calls = fused_ran(monkeypatch)
@@ -267,10 +214,6 @@ def test_fixture_entity_embedding(name, monkeypatch):
         close(dict(m.named_parameters())[k].grad, g["g." + k], atol=1e-4, rel_to_max=1e-4, what=name + " grad " + k)
 
 
-def _rounded(nbytes):
-    return (nbytes + 511) // 512 * 512       # torch.cuda.memory_allocated counts whole 512-byte blocks
-
-
 @pytest.mark.parametrize("wants_grad", [False, True])
 def test_forward_materialises_nothing_of_size_S_Lc(wants_grad):
     """A forward at the reference's word and width geometry raises the allocated bytes by the output, the workspace and (with a gradient
@@ -281,10 +224,10 @@ def test_forward_materialises_nothing_of_size_S_Lc(wants_grad):
     chars, E, Wc, b, span, _ = inputs(*REF_GEOMETRY)
     chars, E, Wc, b = (x.to(dev()) for x in (chars, E, Wc, b))
     ws = _lib.lib().recon_char_features_workspace_bytes(S, W, span, cfs, V, C, Fo, 0)
-    allowed = _rounded(S * W * Fo * 4) + _rounded(ws)
+    allowed = rounded(S * W * Fo * 4) + rounded(ws)
     assert 10 * allowed < S * chars.shape[1] * C * 4
     if wants_grad:
-        allowed += _rounded(S * W * Fo)
+        allowed += rounded(S * W * Fo)
     E.requires_grad_(wants_grad)
 
     def forward():
@@ -292,14 +235,7 @@ def test_forward_materialises_nothing_of_size_S_Lc(wants_grad):
             return char_word_features(chars, E, Wc, b, span)
         with torch.no_grad():
             return char_word_features(chars, E, Wc, b, span)
-    out = forward()                                                                 # warm-up: library load, allocator pools
-    del out
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = forward()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
+    peak, out = peak_bytes(forward)
     print("char_features memory (grad %s): peak %d bytes, allowed %d, gathered embedding %d" % (wants_grad, peak, allowed, S * chars.shape[1] * C * 4))
     assert peak <= allowed, (peak, allowed)
     assert out.shape == (S, W, Fo)

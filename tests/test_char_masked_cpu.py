@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from conftest import ROOT
-from test_char_features_cpu import _inputs, _stock
+from test_char_features_cpu import inputs_word_by_word, stock
 
 NAMES = ("recon_char_masked_supported", "recon_char_masked_workspace_bytes", "recon_char_keep_bits_draw", "recon_char_masked_fwd",
          "recon_char_masked_bwd")
@@ -130,12 +130,12 @@ def test_pack_keep_refuses_two_different_nonzero_values():
 def test_cpu_tensors_run_the_stock_sequence_bit_for_bit(ids):
     from recon_amd import char_word_features
     from recon_amd.char_features import pack_keep
-    chars, E, Wc, b, span = _inputs(7, 3, 4, 3, 5, 6, 9, seed=1)
+    chars, E, Wc, b, span = inputs_word_by_word(7, 3, 4, 3, 5, 6, 9, seed=1)
     keep = (torch.rand(7, chars.shape[1], 5, generator=torch.Generator().manual_seed(3)) >= 0.5).float() * 2.0
     pk = pack_keep(keep)
     G = torch.randn(7, 3, 6)
     grads = []
-    for fn in (lambda *a: char_word_features(a[0].to(ids), *a[1:], keep=pk), lambda *a: _stock(*a, keep=keep)):
+    for fn in (lambda *a: char_word_features(a[0].to(ids), *a[1:], keep=pk), lambda *a: stock(*a, keep=keep)):
         p = [t.clone().requires_grad_(True) for t in (E, Wc, b)]
         y = fn(chars, *p, span)
         (y * G).sum().backward()
@@ -148,7 +148,7 @@ def test_cpu_tensors_run_the_stock_sequence_bit_for_bit(ids):
 def test_packed_keep_checks_raise():
     from recon_amd import char_word_features
     from recon_amd.char_features import PackedKeep
-    chars, E, Wc, b, span = _inputs(4, 3, 4, 3, 5, 6, 9, seed=2)
+    chars, E, Wc, b, span = inputs_word_by_word(4, 3, 4, 3, 5, 6, 9, seed=2)
     Lc = chars.shape[1]
     good = torch.zeros(4, Lc, 1, dtype=torch.int32)
     assert char_word_features(chars, E, Wc, b, span, keep=PackedKeep(good, 2.0, 5)).shape == (4, 3, 6)

@@ -2,8 +2,7 @@
 sequence of models/models.py:57-61 with the same dropout factors in fp64 on the CPU, and against the training fixture written from the
 reference's EntityEmbedding.
 
-Tolerance: that of test_char_features_gpu.py.  The stock chain (fp32, same factors) is run in the same test and its error against fp64,
-relative to max |oracle|, measured; the op has to stay within min(max(4 e_chain, 2^-20), 2e-5).
+Tolerance: `op_checks.bound` of the error of the stock chain (fp32, same factors), run in the same test.
 
 Gradient cells near a tie: g_out is zeroed at every (s, w, o) where, in fp64, the window's maximum and a position whose MASKED ROWS
 X[t .. t + cfs) differ from the winner's are closer than 1e-5.  Rows are compared, not ids: all-masked and all-padding positions tie
@@ -16,7 +15,9 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden
-from test_char_features_gpu import REF_GEOMETRY, _rounded, bound, case, dev, inputs, rel_err, run
+from op_checks import band_failures, bound, calls_of, close, dev, peak_bytes, rel_err, rounded, same
+from test_char_features_cpu import fixture_model, inputs
+from test_char_features_gpu import REF_GEOMETRY, case, run
 
 pytestmark = pytest.mark.gpu
 
@@ -83,12 +84,8 @@ def masked_case(shape, p):
 
 
 def masked_ran(monkeypatch):
-    """Counts the calls of the masked autograd function during a test."""
     from recon_amd import char_features
-    calls = []
-    real = char_features._CharWordFeaturesMasked.apply
-    monkeypatch.setattr(char_features._CharWordFeaturesMasked, "apply", staticmethod(lambda *a: (calls.append(1), real(*a))[1]))
-    return calls
+    return calls_of(monkeypatch, char_features._CharWordFeaturesMasked, "apply")
 
 
 # ---- 1. value and three gradients ---------------------------------------------------------------------------------------------------
@@ -108,12 +105,7 @@ def test_value_and_gradients(shape, p, monkeypatch):
     chain = run(_chain, chars, E, Wc, b, span, g_out, keep=keep.to(dev()))
     assert op[0].shape == (S, W, Fo) and op[1].shape == E.shape and op[2].shape == Wc.shape and op[3].shape == b.shape
     print("char_masked %s p %.1f: %d of %d cells near a tie" % (shape, p, n_ties, S * W * Fo))
-    failures = []
-    for what, f, c, r in zip(("out",) + PARAMS, op, chain, ref):
-        e_f, e_c = rel_err(f, r), rel_err(c, r)
-        print("char_masked %s p %.1f %s: op %.3e chain %.3e (of max |ref|)" % (shape, p, what, e_f, e_c))
-        if not e_f <= bound(e_c):
-            failures.append((what, e_f, e_c))
+    failures = band_failures(("out",) + PARAMS, op, chain, ref, "char_masked %s p %.1f" % (shape, p))
     assert not failures, failures
     assert torch.count_nonzero(op[1][0]) == 0                                       # the padding row's gradient
 
@@ -125,8 +117,7 @@ def test_forward_and_backward_are_bitwise_reproducible(shape):
     chars, E, Wc, b, span, g_out, _, pk, _, _ = masked_case(shape, 0.5)
     a = run(char_word_features, chars, E, Wc, b, span, g_out, keep=on_dev(pk))
     c = run(char_word_features, chars, E, Wc, b, span, g_out, keep=on_dev(pk))
-    for x, y in zip(a, c):
-        assert torch.equal(x, y)
+    same(a, c)
 
 
 # ---- 3. edge cases ------------------------------------------------------------------------------------------------------------------
@@ -166,8 +157,7 @@ def test_bits_at_and_above_C_are_ignored(shape, garbage):
     assert not torch.equal(dirty, pk.bits)
     a = run(char_word_features, chars, E, Wc, b, span, g_out, keep=on_dev(pk))
     c = run(char_word_features, chars, E, Wc, b, span, g_out, keep=on_dev(PackedKeep(dirty, pk.scale, pk.C)))
-    for x, y in zip(a, c):
-        assert torch.equal(x, y)
+    same(a, c)
 
 
 def test_int32_ids():
@@ -175,8 +165,7 @@ def test_int32_ids():
     chars, E, Wc, b, span, g_out, _, pk, ref, _ = masked_case(REF_WIDTHS, 0.5)
     a = run(char_word_features, chars, E, Wc, b, span, g_out, keep=on_dev(pk))
     c = run(char_word_features, chars.to(torch.int32), E, Wc, b, span, g_out, keep=on_dev(pk))
-    for x, y in zip(a, c):
-        assert torch.equal(x, y)
+    same(a, c)
     assert rel_err(c[0], ref[0]) <= 2e-5
 
 
@@ -188,8 +177,7 @@ def test_strided_ids_are_read_in_place():
     wide[:, :chars.shape[1]] = chars
     a = run(char_word_features, chars, E, Wc, b, span, g_out, keep=on_dev(pk))
     c = run(lambda ch, *r, **kw: char_word_features(ch[:, :chars.shape[1]], *r, **kw), wide, E, Wc, b, span, g_out, keep=on_dev(pk))
-    for x, y in zip(a, c):
-        assert torch.equal(x, y)
+    same(a, c)
 
 
 def test_nonzero_padding_idx():
@@ -252,8 +240,6 @@ def test_fixture_pool_output():
 def test_fixture_entity_embedding_with_packed_dropout(monkeypatch):
     """EntityEmbedding with packed_char_dropout and the fixture's recorded factors replayed through draw_packed_keep: the output and the
     three gradients within test_fixture_entity_embedding's tolerances, through the masked function."""
-    from test_gat_gpu import close
-    from tests.test_char_features_cpu import fixture_model
     from recon_amd.char_features import pack_keep
     name = "char_features2_train"
     g = load_golden(name)
@@ -365,18 +351,11 @@ def test_forward_materialises_nothing_of_size_S_Lc_C():
     pk = on_dev(pk)
     assert pk.bits.numel() * 4 == S * chars.shape[1] * 8
     ws = _lib.lib().recon_char_masked_workspace_bytes(S, W, span, cfs, V, C, Fo, 0)
-    allowed = _rounded(S * W * Fo * 4) + _rounded(ws)
+    allowed = rounded(S * W * Fo * 4) + rounded(ws)
     assert 10 * allowed < S * chars.shape[1] * C * 4
-    allowed += _rounded(S * W * Fo)
+    allowed += rounded(S * W * Fo)
     E.requires_grad_(True)
-    out = char_word_features(chars, E, Wc, b, span, keep=pk)                         # warm-up: library load, allocator pools
-    del out
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = char_word_features(chars, E, Wc, b, span, keep=pk)
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
+    peak, out = peak_bytes(lambda: char_word_features(chars, E, Wc, b, span, keep=pk))
     print("char_masked memory: peak %d bytes, allowed %d, gathered embedding %d" % (peak, allowed, S * chars.shape[1] * C * 4))
     assert peak <= allowed, (peak, allowed)
     assert out.shape == (S, W, Fo) and out.grad_fn is not None

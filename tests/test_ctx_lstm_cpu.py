@@ -2,7 +2,6 @@
 argument errors, the empty batch, and the fixture tests/golden/ctx_lstm1.npz under the stock lines in fp64 (which pins the fixture to the
 reference before any kernel is involved)."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -10,7 +9,10 @@ import torch
 from torch import nn
 
 from conftest import ROOT, load_golden
+from op_checks import calls_of, entries_declared_and_bound
+from test_char_features_cpu import fixture_model
 
+VW = 11                                                                      # rows of the word table `inputs` draws
 ENTRIES = ("recon_ctx_lstm_supported", "recon_ctx_lstm_workspace_bytes", "recon_ctx_lstm_saved_bytes", "recon_ctx_lstm_fwd",
            "recon_ctx_lstm_bwd")
 
@@ -21,6 +23,18 @@ def stock(lstm, feat, words=None, table=None):
     _, (h_n, _) = lstm(x)
     h_n = h_n.view(lstm.num_layers, 2, x.shape[0], lstm.hidden_size)[-1]
     return h_n.permute(1, 0, 2).contiguous().view(x.shape[0], 2 * lstm.hidden_size)
+
+
+def inputs(S, T, Dw, Fc, H, seed=0):
+    """The GPU file's cases: the seeds are mixed with the shape, weights uniform in +-1 / sqrt(H) (nn.LSTM's own init), g_out is drawn too."""
+    g = torch.Generator().manual_seed(1000 * seed + S + T + Dw + Fc + H)
+    torch.manual_seed(1000 * seed + S + 7 * T + Dw + Fc + H)
+    lstm = nn.LSTM(Dw + Fc, H, 1, batch_first=True, bidirectional=True)       # uniform in +-1 / sqrt(H)
+    feat = torch.randn(S, T, Fc, generator=g)
+    words = torch.randint(0, VW, (S, T), generator=g) if Dw else None
+    table = torch.randn(VW, Dw, generator=g) if Dw else None
+    g_out = torch.randn(S, 2 * H, generator=g)
+    return lstm, feat, words, table, g_out
 
 
 def make(S=5, T=4, Dw=3, Fc=2, H=3, dtype=torch.float32, seed=0, **kw):
@@ -35,16 +49,7 @@ def make(S=5, T=4, Dw=3, Fc=2, H=3, dtype=torch.float32, seed=0, **kw):
 
 
 def test_header_declares_and_lib_binds_the_entries():
-    from recon_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "recon_hip.h")).read(), flags=re.S)
-    bound = {name for name, _, _ in _lib.SYMBOLS}
-    for name in ENTRIES:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in bound, name
-    raw = open(os.path.join(ROOT, "include", "recon_hip.h")).read()
-    for name in ENTRIES:                                                     # every entry cites its lines of the reference
-        comment = raw[:raw.index(name + "(")].rsplit("/*", 1)[1]
-        assert "models/models.py:56-70" in comment, name
+    entries_declared_and_bound(ENTRIES, "models/models.py:56-70")
 
 
 @pytest.mark.parametrize("gather", [True, False])
@@ -71,9 +76,7 @@ def test_fallback_conditions_reach_the_chain(how, monkeypatch):
     kw = {"fp64": dict(dtype=torch.float64), "two_layers": dict(num_layers=2), "unidirectional": dict(bidirectional=False),
           "proj_size": dict(proj_size=2), "cpu_fp32": {}}[how]
     lstm, feat, words, table = make(**kw)
-    calls = []
-    real = context_lstm._chain
-    monkeypatch.setattr(context_lstm, "_chain", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    calls = calls_of(monkeypatch, context_lstm, "_chain")
     monkeypatch.setattr(context_lstm._ContextLineStates, "apply", staticmethod(lambda *a: pytest.fail("the kernels' function was entered")))
     out = context_line_states(lstm, feat, words, table)
     assert calls == [1]
@@ -138,13 +141,10 @@ def test_fixture_reproduces_under_the_stock_lines_in_fp64(monkeypatch):
     """EntityEmbedding in fp64 on the CPU (its op runs `_chain` there) against the reference module's recorded output and the gradient of
     every parameter."""
     from recon_amd import context_lstm
-    from tests.test_char_features_cpu import fixture_model
     g = load_golden("ctx_lstm1")
     assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "ctx_lstm1.npz")) < 32 * 1024
     m = fixture_model(g).double()
-    calls = []
-    real = context_lstm._chain
-    monkeypatch.setattr(context_lstm, "_chain", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    calls = calls_of(monkeypatch, context_lstm, "_chain")
     out, grads = fixture_gradients(g, m)
     assert calls == [1]
     np.testing.assert_allclose(out.numpy(), g["out"], rtol=0, atol=1e-12)

@@ -1,20 +1,20 @@
 """recon_amd.context_line_states (csrc/ctx_lstm.hip) against the stock lines of models/models.py:56-70 in fp64 on the CPU, and against the
 fixture written from the reference's EntityEmbedding.
 
-Tolerance of value and gradients (the scheme of test_char_features_gpu.py): the stock fp32 chain's own error on the GPU against fp64 on the
-same inputs, e_chain, is measured in the test, relative to max |oracle|; the op has to stay within min(max(4 e_chain, 2^-20), 2e-5).
-Weights uniform in +-1 / sqrt(H) (nn.LSTM's own init), inputs N(0, 1).  No cell is excluded: the op makes no discrete choice.  The
+Tolerance of value and gradients: `op_checks.bound` of the stock fp32 chain's own error on the GPU against fp64 on the same inputs, measured
+in the test.  Weights uniform in +-1 / sqrt(H) (nn.LSTM's own init), inputs N(0, 1).  No cell is excluded: the op makes no discrete choice.  The
 figures measured on an MI355X are in DESIGN.md section 20."""
 import copy
 import ctypes
 
-import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 from torch import nn
 
 from conftest import load_golden
+from op_checks import band_failures, calls_of, close, dev, peak_bytes, rel_err, rounded, same
+from test_char_features_cpu import fixture_model
+from test_ctx_lstm_cpu import VW, inputs, stock
 
 pytestmark = pytest.mark.gpu
 
@@ -23,40 +23,8 @@ LONG_THIN = (2 * 16 * G_BWD + 5, 3, 3, 4, 5)
 #        S   T  Dw  Fc  H
 CASES = [(1, 1, 1, 1, 1), (3, 3, 4, 6, 3), (17, 5, 3, 4, 5), (33, 7, 0, 41, 64), (20, 2, 50, 50, 50), (130, 32, 50, 50, 50), LONG_THIN]
 REF_WIDTHS = (130, 32, 50, 50, 50)
-VW = 11
 NAMES = ("out", "feat", "word_table", "weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0", "weight_ih_l0_reverse",
          "weight_hh_l0_reverse", "bias_ih_l0_reverse", "bias_hh_l0_reverse")
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def bound(e_chain):
-    return min(max(4 * e_chain, 2.0 ** -20), 2e-5)
-
-
-def rel_err(got, ref):
-    return ((got.detach().double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
-
-
-def stock(lstm, feat, words=None, table=None):
-    """models/models.py:56-70 written out: embedding, cat, lstm, h_n of the last layer with the directions side by side."""
-    x = feat if words is None else torch.cat((F.embedding(words, table), feat), -1)
-    _, (h_n, _) = lstm(x)
-    h_n = h_n.view(1, 2, x.shape[0], lstm.hidden_size)[-1]
-    return h_n.permute(1, 0, 2).contiguous().view(x.shape[0], 2 * lstm.hidden_size)
-
-
-def inputs(S, T, Dw, Fc, H, seed=0):
-    g = torch.Generator().manual_seed(1000 * seed + S + T + Dw + Fc + H)
-    torch.manual_seed(1000 * seed + S + 7 * T + Dw + Fc + H)
-    lstm = nn.LSTM(Dw + Fc, H, 1, batch_first=True, bidirectional=True)       # uniform in +-1 / sqrt(H)
-    feat = torch.randn(S, T, Fc, generator=g)
-    words = torch.randint(0, VW, (S, T), generator=g) if Dw else None
-    table = torch.randn(VW, Dw, generator=g) if Dw else None
-    g_out = torch.randn(S, 2 * H, generator=g)
-    return lstm, feat, words, table, g_out
 
 
 _CASES = {}
@@ -88,28 +56,13 @@ def run(fn, lstm, feat, words, table, g_out, frozen_table=False, ids=None):
 
 
 def kernels_ran(monkeypatch):
-    """Counts the calls of the kernels' autograd function during a test."""
     from recon_amd import context_lstm
-    calls = []
-    real = context_lstm._ContextLineStates.apply
-    monkeypatch.setattr(context_lstm._ContextLineStates, "apply", staticmethod(lambda *a: (calls.append(1), real(*a))[1]))
-    return calls
+    return calls_of(monkeypatch, context_lstm._ContextLineStates, "apply")
 
 
 def chain_ran(monkeypatch):
     from recon_amd import context_lstm
-    calls = []
-    real = context_lstm._chain
-    monkeypatch.setattr(context_lstm, "_chain", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
-    return calls
-
-
-def same(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        assert (x is None) == (y is None)
-        if x is not None:
-            assert torch.equal(x, y)
+    return calls_of(monkeypatch, context_lstm, "_chain")
 
 
 def test_workgroup_cap_is_the_librarys():
@@ -135,16 +88,7 @@ def test_value_and_gradients(shape, monkeypatch):
     chain = run(_chain, lstm, feat, words, table, g_out)
     S, T, Dw, Fc, H = shape
     assert fused[0].shape == (S, 2 * H) and fused[1].shape == (S, T, Fc)
-    failures = []
-    for what, f, c, r in zip(NAMES, fused, chain, ref):
-        if r is None:
-            assert f is None
-            continue
-        assert f.shape == r.shape
-        e_f, e_c = rel_err(f, r), rel_err(c, r)
-        print("ctx_lstm %s %s: op %.3e chain %.3e (of max |ref|)" % (shape, what, e_f, e_c))
-        if not e_f <= bound(e_c):
-            failures.append((what, e_f, e_c))
+    failures = band_failures(NAMES, fused, chain, ref, "ctx_lstm %s" % (shape,))
     assert not failures, failures
 
 
@@ -155,21 +99,6 @@ def test_int32_ids():
     c = run(context_line_states, lstm, feat, words, table, g_out, ids=words.to(torch.int32))
     same(a, c)
     assert rel_err(c[0], ref[0]) <= 2e-5
-
-
-def _rounded(nbytes):
-    return (nbytes + 511) // 512 * 512       # torch.cuda.memory_allocated counts whole 512-byte blocks
-
-
-def _peak(fn):
-    out = fn()                                # warm-up: library load, allocator pools
-    del out
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = fn()
-    torch.cuda.synchronize()
-    return torch.cuda.max_memory_allocated() - base, out
 
 
 def test_strided_feat_is_read_in_place():
@@ -186,13 +115,13 @@ def test_strided_feat_is_read_in_place():
     assert torch.equal(a[1], c[1][:, :, 2:2 + Fc]) and torch.count_nonzero(c[1][:, :, :2]) == 0 and torch.count_nonzero(c[1][:, :, 2 + Fc:]) == 0
     m = copy.deepcopy(lstm).to(dev())
     view, w, tb = wide.to(dev())[:, :, 2:2 + Fc], words.to(dev()), table.to(dev())
-    allowed = _rounded(S * 2 * H * 4) + _rounded(_lib.lib().recon_ctx_lstm_workspace_bytes(S, T, Dw, Fc, H, 0))
+    allowed = rounded(S * 2 * H * 4) + rounded(_lib.lib().recon_ctx_lstm_workspace_bytes(S, T, Dw, Fc, H, 0))
     assert allowed < S * T * Fc * 4
 
     def forward():
         with torch.no_grad():
             return context_line_states(m, view, w, tb)
-    peak, out = _peak(forward)
+    peak, out = peak_bytes(forward)
     print("ctx_lstm memory (no_grad, strided feat): peak %d bytes, allowed %d, a copy of feat %d" % (peak, allowed, S * T * Fc * 4))
     assert peak <= allowed, (peak, allowed)
     assert torch.equal(out, a[0])
@@ -236,8 +165,8 @@ def test_saved_state_is_what_the_library_sizes_and_nothing_else():
     f, w, tb = feat.to(dev()).requires_grad_(True), words.to(dev()), table.to(dev())
     want = _lib.lib().recon_ctx_lstm_saved_bytes(S, T, Dw, Fc, H)
     assert want == 2 * S * T * 5 * H * 4
-    allowed = _rounded(S * 2 * H * 4) + _rounded(_lib.lib().recon_ctx_lstm_workspace_bytes(S, T, Dw, Fc, H, 0)) + _rounded(want)
-    peak, out = _peak(lambda: context_line_states(m, f, w, tb))
+    allowed = rounded(S * 2 * H * 4) + rounded(_lib.lib().recon_ctx_lstm_workspace_bytes(S, T, Dw, Fc, H, 0)) + rounded(want)
+    peak, out = peak_bytes(lambda: context_line_states(m, f, w, tb))
     print("ctx_lstm memory (grad): peak %d bytes, allowed %d" % (peak, allowed))
     assert peak <= allowed, (peak, allowed)
     saved = out.grad_fn.saved_tensors
@@ -339,8 +268,6 @@ def test_c_abi_agrees_with_the_op_and_launches_nothing_for_an_empty_batch():
 def test_fixture_entity_embedding(monkeypatch):
     """EntityEmbedding with the fixture's parameters (strict load) against the reference module's output and the gradient of every
     parameter at the whole-model bounds; the new kernels run and nn.LSTM.forward does not."""
-    from test_gat_gpu import close
-    from tests.test_char_features_cpu import fixture_model
     g = load_golden("ctx_lstm1")
     m = fixture_model(g)
     calls = kernels_ran(monkeypatch)

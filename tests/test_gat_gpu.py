@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from op_checks import close
 from oracle import recon_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -18,15 +19,6 @@ T = torch.from_numpy
 def dev():
     assert torch.cuda.is_available(), "these tests need an MI355X"
     return torch.device("cuda:0")
-
-
-def close(actual, desired, atol=1e-4, rel_to_max=1e-4, what=""):
-    actual = actual.detach().cpu().numpy() if torch.is_tensor(actual) else actual
-    desired = desired.detach().cpu().numpy() if torch.is_tensor(desired) else desired
-    tol = atol + rel_to_max * (np.abs(desired).max() if desired.size else 0.0)
-    err = np.abs(actual - desired).max() if desired.size else 0.0
-    assert np.isfinite(actual).all(), what + ": non-finite values"
-    assert err <= tol, "%s: max abs err %.3e > tol %.3e" % (what, err, tol)
 
 
 # ------------------------------------------------------------------------------- K3

@@ -1,14 +1,15 @@
 """recon_amd.pair_sentence_states without a GPU: the ABI entries, the stock lines of GPGNN.encode on CPU tensors (bit for bit, with every kind
 of keep), the conditions that reach `_chain`, argument errors, the empty batch, and GPGNN.encode with the op switched on."""
 import os
-import re
 
 import pytest
 import torch
 from torch import nn
 
 from conftest import ROOT
+from op_checks import calls_of, entries_declared_and_bound
 
+VW, VP = 11, 4                                                                  # rows of the tables `inputs` draws
 ENTRIES = ("recon_sent_lstm_supported", "recon_sent_lstm_workspace_bytes", "recon_sent_lstm_saved_bytes", "recon_sent_lstm_fwd",
            "recon_sent_lstm_bwd")
 
@@ -29,6 +30,22 @@ def stock(rnn, sentence, markers, word_table, pos_table, keep=None):
     return torch.cat([rnn_output[:, -1, :u], rnn_output[:, 0, u:]], dim=1).view(B, C, -1)
 
 
+def inputs(B, C, T, Dw, P, H, seed=0):
+    """The GPU file's cases: the seeds are mixed with the shape, weights uniform in +-1 / sqrt(H) (nn.LSTM's own init), tables N(0, 1) with
+    a non-zero padding row, markers over all VP values, g_out and packed dropout bits (p = 0.5) drawn too."""
+    from recon_amd.char_features import pack_keep
+    g = torch.Generator().manual_seed(1000 * seed + B + C + T + Dw + P + H)
+    torch.manual_seed(1000 * seed + B + 7 * T + C + Dw + P + H)
+    rnn = nn.LSTM(Dw + P, H, 1, batch_first=True, bidirectional=True)          # uniform in +-1 / sqrt(H)
+    sentence = torch.randint(0, VW, (B, T), generator=g)
+    markers = torch.randint(0, VP, (B, C, T), generator=g)
+    word_table = torch.randn(VW, Dw, generator=g)
+    pos_table = torch.randn(VP, P, generator=g)
+    g_out = torch.randn(B, C, 2 * H, generator=g)
+    keep = pack_keep((torch.rand(B * C, T, Dw, generator=g) >= 0.5).float() * 2.0, 2.0)        # p = 0.5
+    return rnn, sentence, markers, word_table, pos_table, g_out, keep
+
+
 def make(B=2, C=3, T=4, Dw=5, P=3, H=3, dtype=torch.float32, seed=0, **kw):
     g = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
@@ -42,15 +59,7 @@ def make(B=2, C=3, T=4, Dw=5, P=3, H=3, dtype=torch.float32, seed=0, **kw):
 
 
 def test_header_declares_and_lib_binds_the_entries():
-    from recon_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "recon_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    bound = {name for name, _, _ in _lib.SYMBOLS}
-    for name in ENTRIES:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in bound, name
-        comment = raw[:raw.index(name + "(")].rsplit("/*", 1)[1]                # every entry cites its lines of the reference
-        assert "models/models.py:160-184" in comment, name
+    entries_declared_and_bound(ENTRIES, "models/models.py:160-184")
     assert "sent_lstm.hip" in open(os.path.join(ROOT, "recon_amd", "csrc", "Makefile")).read()
 
 
@@ -89,9 +98,7 @@ def test_fallback_conditions_reach_the_chain(how, monkeypatch):
     keep = torch.full((2, 3, 4, 5), 2.0) if how == "fp32_keep" else None
     if how == "trainable_table":
         word_table.requires_grad_(True)
-    calls = []
-    real = sentence_lstm._chain
-    monkeypatch.setattr(sentence_lstm, "_chain", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    calls = calls_of(monkeypatch, sentence_lstm, "_chain")
     monkeypatch.setattr(sentence_lstm._PairSentenceStates, "apply", staticmethod(lambda *a: pytest.fail("the kernels' function was entered")))
     out = pair_sentence_states(rnn, sentence, markers, word_table, pos_table, keep)
     assert calls == [1]
@@ -174,9 +181,7 @@ def test_gpgnn_encode_with_the_op_switched_on_equals_todays_encode(mode, monkeyp
     g_out = torch.randn(2, 6, 8, generator=g)
     res = []
     for fused in (False, True):
-        calls = []
-        real = gpgnn.pair_sentence_states
-        monkeypatch.setattr(gpgnn, "pair_sentence_states", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+        calls = calls_of(monkeypatch, gpgnn, "pair_sentence_states")
         monkeypatch.setattr(m, "fused_sentence_encoder", fused, raising=False)
         monkeypatch.setattr(m, "packed_word_dropout", fused, raising=False)
         m.zero_grad()

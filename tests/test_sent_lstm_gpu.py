@@ -1,9 +1,8 @@
 """recon_amd.pair_sentence_states (csrc/sent_lstm.hip) against the stock lines of models/models.py:160-184 in fp64 on the CPU, and against
 the fixtures written from the reference's GPGNN and RECON_EAC.
 
-Tolerance of value and gradients (the scheme of test_ctx_lstm_gpu.py, unchanged): the stock fp32 chain's own error on the GPU against fp64
-on the same inputs, e_chain, is measured in the test, relative to max |oracle|; the op has to stay within min(max(4 e_chain, 2^-20), 2e-5)
-for out, pos_table's gradient and the eight parameter gradients.  Weights uniform in +-1 / sqrt(H) (nn.LSTM's own init), tables N(0, 1)
+Tolerance of value and gradients: `op_checks.bound` of the stock fp32 chain's own error on the GPU against fp64 on the same inputs, measured
+in the test, for out, pos_table's gradient and the eight parameter gradients.  Weights uniform in +-1 / sqrt(H) (nn.LSTM's own init), tables N(0, 1)
 with a non-zero padding row, markers over all Vp = 4 values.  No cell is excluded.  The figures measured on an MI355X are in DESIGN.md
 section 21."""
 import copy
@@ -11,9 +10,9 @@ import copy
 import numpy as np
 import pytest
 import torch
-from torch import nn
 
-from conftest import load_golden
+from op_checks import band_failures, calls_of, dev, eac_fixture, gpgnn_fixture, peak_bytes, pinned, rel_err, rounded, same
+from test_sent_lstm_cpu import VP, VW, inputs, stock
 
 pytestmark = pytest.mark.gpu
 
@@ -26,52 +25,8 @@ REF_ONE = (1, 72, 36, 50, 3, 256)
 #        B   C  T  Dw  P  H
 CASES = [(1, 1, 1, 1, 1, 1), (2, 3, 3, 4, 3, 3), (3, 2, 5, 5, 3, 17), (2, 6, 4, 50, 3, 64), (1, 20, 3, 7, 3, 256), (3, 72, 2, 50, 3, 100),
          REF_ONE, LONG_THIN, WIDE_FULL, WIDE_SMALL]
-VW, VP = 11, 4
 NAMES = ("out", "pos_table", "weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0", "weight_ih_l0_reverse", "weight_hh_l0_reverse",
          "bias_ih_l0_reverse", "bias_hh_l0_reverse")
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def bound(e_chain):
-    return min(max(4 * e_chain, 2.0 ** -20), 2e-5)
-
-
-def rel_err(got, ref):
-    return ((got.detach().double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
-
-
-def stock(rnn, sentence, markers, word_table, pos_table, keep=None):
-    """models/models.py:160-184 as GPGNN.encode writes it, with the dropout factors given."""
-    B, T = sentence.shape
-    C = markers.shape[1]
-    expanded = torch.transpose(sentence.expand(C, B, T), 0, 1)
-    word = nn.functional.embedding(expanded.contiguous().view(-1, T), word_table, padding_idx=0).view(B, C, T, -1)
-    if keep is not None:
-        word = word * keep
-    pos = nn.functional.embedding(markers.contiguous().view(-1, T), pos_table, padding_idx=0).view(B, C, T, -1)
-    merged = torch.cat([word, pos], dim=3)
-    merged = merged.view(-1, T, merged.size(-1))
-    rnn_output, _ = rnn(merged)
-    u = rnn.hidden_size
-    return torch.cat([rnn_output[:, -1, :u], rnn_output[:, 0, u:]], dim=1).view(B, C, -1)
-
-
-def inputs(B, C, T, Dw, P, H, seed=0):
-    from recon_amd.char_features import pack_keep
-    g = torch.Generator().manual_seed(1000 * seed + B + C + T + Dw + P + H)
-    torch.manual_seed(1000 * seed + B + 7 * T + C + Dw + P + H)
-    rnn = nn.LSTM(Dw + P, H, 1, batch_first=True, bidirectional=True)          # uniform in +-1 / sqrt(H)
-    sentence = torch.randint(0, VW, (B, T), generator=g)
-    markers = torch.randint(0, VP, (B, C, T), generator=g)
-    word_table = torch.randn(VW, Dw, generator=g)
-    pos_table = torch.randn(VP, P, generator=g)
-    g_out = torch.randn(B, C, 2 * H, generator=g)
-    keep = pack_keep((torch.rand(B * C, T, Dw, generator=g) >= 0.5).float() * 2.0, 2.0)        # p = 0.5
-    return rnn, sentence, markers, word_table, pos_table, g_out, keep
-
 
 _CASES = {}
 
@@ -113,26 +68,13 @@ def chain_fn(m, s, k, wt, pt, keep):
 
 
 def kernels_ran(monkeypatch):
-    """Counts the calls of the kernels' autograd function during a test."""
     from recon_amd import sentence_lstm
-    calls = []
-    real = sentence_lstm._PairSentenceStates.apply
-    monkeypatch.setattr(sentence_lstm._PairSentenceStates, "apply", staticmethod(lambda *a: (calls.append(1), real(*a))[1]))
-    return calls
+    return calls_of(monkeypatch, sentence_lstm._PairSentenceStates, "apply")
 
 
 def chain_ran(monkeypatch):
     from recon_amd import sentence_lstm
-    calls = []
-    real = sentence_lstm._chain
-    monkeypatch.setattr(sentence_lstm, "_chain", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
-    return calls
-
-
-def same(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        assert torch.equal(x, y)
+    return calls_of(monkeypatch, sentence_lstm, "_chain")
 
 
 def test_row_split_and_tile_rule_are_the_librarys():
@@ -166,14 +108,7 @@ def test_value_and_gradients(shape, packed, monkeypatch):
     B, C, T, Dw, P, H = shape
     assert fused[0].shape == (B, C, 2 * H) and fused[1].shape == (VP, P)
     assert torch.count_nonzero(fused[1][0]) == 0                                # the padding row's gradient
-    failures = []
-    for what, f, c, r in zip(NAMES, fused, chain, ref):
-        assert f.shape == r.shape
-        e_f, e_c = rel_err(f, r), rel_err(c, r)
-        print("sent_lstm %s %s %s: op %.3e chain %.3e bound %.3e ratio %.3f" % (shape, "packed" if packed else "nokeep", what, e_f, e_c,
-                                                                                 bound(e_c), e_f / bound(e_c)))
-        if not e_f <= bound(e_c):
-            failures.append((what, e_f, e_c))
+    failures = band_failures(NAMES, fused, chain, ref, "sent_lstm %s %s" % (shape, "packed" if packed else "nokeep"))
     assert not failures, failures
 
 
@@ -212,10 +147,6 @@ def test_forward_and_backward_are_bitwise_reproducible():
         same(run(pair_sentence_states, *args), run(pair_sentence_states, *args))
 
 
-def _rounded(nbytes):
-    return (nbytes + 511) // 512 * 512       # torch.cuda.memory_allocated counts whole 512-byte blocks
-
-
 def test_no_grad_allocates_no_saved_state_and_gives_the_training_forwards_bits():
     from recon_amd import _lib, pair_sentence_states
     shape = (3, 72, 2, 50, 3, 100)
@@ -231,15 +162,8 @@ def test_no_grad_allocates_no_saved_state_and_gives_the_training_forwards_bits()
     def forward():
         with torch.no_grad():
             return pair_sentence_states(m, s, k, wt, pt, kp)
-    out = forward()
-    del out
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = forward()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    allowed = _rounded(B * C * 2 * H * 4) + _rounded(L.recon_sent_lstm_workspace_bytes(*shape, VP, 0))
+    peak, out = peak_bytes(forward)
+    allowed = rounded(B * C * 2 * H * 4) + rounded(L.recon_sent_lstm_workspace_bytes(*shape, VP, 0))
     print("sent_lstm memory (no_grad): peak %d bytes, allowed %d, saved state would be %d" % (peak, allowed, L.recon_sent_lstm_saved_bytes(*shape)))
     assert peak <= allowed < L.recon_sent_lstm_saved_bytes(*shape)
     assert out.grad_fn is None and torch.equal(out, trained.detach())
@@ -314,43 +238,15 @@ def test_packed_word_dropout_is_governed_by_the_seed(monkeypatch):
     assert torch.equal(a, b) and not torch.equal(a, c)
 
 
-def _pinned(m, g, out_of, what, monkeypatch):
-    from test_gat_gpu import close
-    m.fused_sentence_encoder = True
-    calls = kernels_ran(monkeypatch)
-    m.train().to(dev())
-    monkeypatch.setattr(m.rnn1, "forward", lambda *a, **k: pytest.fail("nn.LSTM.forward of rnn1 ran"))
-    out = out_of(m)
-    assert len(calls) == 1
-    close(out, g["out"], atol=1e-4, what=what + " logits")
-    (out * torch.from_numpy(g["G"]).to(dev())).sum().backward()
-    seen = 0
-    for k, v in m.named_parameters():
-        if "g." + k in g:
-            close(v.grad, g["g." + k], atol=1e-4, rel_to_max=1e-4, what=what + " grad " + k)
-            seen += 1
-    assert seen == sum(k.startswith("g.") for k in g)
-    assert any(k.startswith("g.rnn1.") for k in g) and "g.pos_embedding.weight" in g
+def _through_the_op(fixture, monkeypatch):
+    pinned(*fixture, monkeypatch, "fused_sentence_encoder", kernels_ran(monkeypatch), lambda m: ([m.rnn1], "nn.LSTM.forward of rnn1 ran"),
+           ["g.rnn1.", "g.pos_embedding.weight"])
 
 
 @pytest.mark.parametrize("name", ["gpgnn1_untied", "gpgnn2_tied_n9"])
 def test_gpgnn_fixture_through_the_op(name, monkeypatch):
-    from recon_amd.gpgnn import GPGNN
-    g = load_golden(name)
-    p = {"max_num_nodes": int(g["n"]), "embedding_dim": int(g["d"]), "layer_number": int(g["L"]), "projection_style": str(g["style"]),
-         "non-linear1": "relu", "non-linear": "tanh", "dropout1": 0.0, "position_emb": 3, "units1": 4, "rnn1_layers": 1,
-         "bidirectional": 1, "batch_size": int(g["B"])}
-    m = GPGNN(p, g["emb"], max_sent_len=4, n_out=3)
-    m.load_state_dict({k[3:]: torch.from_numpy(np.asarray(v)) for k, v in g.items() if k.startswith("sd.")}, strict=False)
-    _pinned(m, g, lambda m: m(torch.from_numpy(g["sent"]).to(dev()), torch.from_numpy(g["mark"]).to(dev()), None), name, monkeypatch)
+    _through_the_op(gpgnn_fixture(name), monkeypatch)
 
 
 def test_recon_eac_fixture_through_the_op(monkeypatch):
-    from recon_amd.gpgnn import RECON_EAC
-    from tests.test_host_cpu import EAC_P
-    g = load_golden("eac1_untied")
-    m = RECON_EAC(dict(EAC_P), g["emb"], max_sent_len=4, n_out=3, char_vocab=list(range(int(g["n_chars"]))))
-    m.load_state_dict({k[3:]: torch.from_numpy(np.asarray(v)) for k, v in g.items() if k.startswith("sd.")}, strict=False)
-    t = lambda k: torch.from_numpy(g[k]).to(dev())
-    _pinned(m, g, lambda m: m(t("sent"), t("mark"), None, None, None, t("ctx_words"), t("ctx_chars"), t("ctx_mask"), t("pos"), int(g["max_occ"])),
-            "eac1_untied", monkeypatch)
+    _through_the_op(eac_fixture(), monkeypatch)

@@ -3,9 +3,8 @@ queries of the C ABI, `GPGNN.transitions` in both projection styles, and the gua
 kernels to.
 
 The input generator, the g_out construction, the fp64 reference and the comparison live here and are imported by the GPU file.  Inputs:
-x ~ N(0, 1), weights and biases uniform in +-1 / sqrt(K), from a seeded torch.Generator.  Band: errors relative to max |fp64|; with e_chain
-the stock fp32 chain's error on the same inputs, the candidate has to stay within min(max(4 e_chain, 2^-20), 2e-5) — the bound of
-tests/test_sent_lstm_gpu.py.  Relu's kink: a pre-activation within rounding of zero flips act' between fp32 and fp64 and moves a weight
+x ~ N(0, 1), weights and biases uniform in +-1 / sqrt(K), from a seeded torch.Generator.  Band: `op_checks.bound` of the stock fp32 chain's
+error on the same inputs, applied by `op_checks.band_failures`.  Relu's kink: a pre-activation within rounding of zero flips act' between fp32 and fp64 and moves a weight
 gradient by far more than the band (for the stock chain too), so g_out is zero wherever the fp64 pre-activation has magnitude below
 2^-12 max |pre| — a mask from fp64 alone (the fp32 pre-activation's error is about 6e-7 of the maximum: a margin of 400).
 
@@ -19,6 +18,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from op_checks import band_failures
+
 G_WGRAD = 8                                     # the weight-gradient pass's row groups (transitions.WGRAD_MAX_ROW_GROUPS, asserted below)
 GROUP_ROWS = 32                                 # a group holds at least this many rows: G = min(G_WGRAD, ceil(M / 32))
 LONG_THIN = (2 * 16 * G_WGRAD + 5, 8, 16, 2)    # 261 rows: every row group holds 33 rows, more than two tiles of 16 and a tail
@@ -29,14 +30,6 @@ SHAPES = [(1, 4, 1, 1), (17, 20, 24, 3), REF_ONE, (531, 36, 100, 2), LONG_THIN, 
 ACTS = ("relu", "tanh", "linear")
 SEEDS = {(1, 4, 1, 1): 2}                       # the one output of the smallest shape is positive: relu leaves something to check (asserted below)
 KINK = 2.0 ** -12
-
-
-def bound(e_chain):
-    return min(max(4 * e_chain, 2.0 ** -20), 2e-5)
-
-
-def rel_err(got, ref):
-    return ((got.detach().double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
 
 
 def names(L):
@@ -93,15 +86,7 @@ def run(fn, c, act, device="cpu", x_of=None):
 
 
 def failures(got, chain, ref, label=""):
-    """The outputs of `got` outside the band that `chain`'s own error sets; prints every figure."""
-    bad = []
-    for what, f, c, r in zip(names((len(ref) - 1) // 3), got, chain, ref):
-        assert f.shape == r.shape, (what, f.shape, r.shape)
-        e_f, e_c = rel_err(f, r), rel_err(c, r)
-        print("transitions %s %s: op %.3e chain %.3e bound %.3e ratio %.3f" % (label, what, e_f, e_c, bound(e_c), e_f / bound(e_c)))
-        if not e_f <= bound(e_c):
-            bad.append((what, e_f, e_c))
-    return bad
+    return band_failures(names((len(ref) - 1) // 3), got, chain, ref, "transitions " + label)
 
 
 def groups_of(M):

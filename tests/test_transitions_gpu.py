@@ -1,23 +1,18 @@
 """recon_amd.pair_transitions (csrc/pair_trans.hip) against the stock lines of models/models.py:185-192 / :240-249 in fp64 on the CPU, and
 against the fixtures written from the reference's GPGNN, RECON_EAC and RECON_EAC_KGGAT.
 
-Inputs, the g_out mask at relu's kink, the fp64 oracle and the band are those of tests/test_transitions_cpu.py, which also guards them:
-the stock fp32 chain's own error on the GPU against fp64 on the same inputs, e_chain, is measured in the test, relative to max |oracle|;
-the op has to stay within min(max(4 e_chain, 2^-20), 2e-5) for every T_l, d_x, every d_W_l and every d_b_l.  The figures measured on an
-MI355X are in DESIGN.md section 22."""
-import numpy as np
+Inputs, the g_out mask at relu's kink and the fp64 oracle are those of tests/test_transitions_cpu.py, which also guards them; the band is
+`op_checks.bound` of the stock fp32 chain's own error on the GPU, for every T_l, d_x, every d_W_l and every d_b_l.  The figures measured on
+an MI355X are in DESIGN.md section 22."""
 import pytest
 import torch
 import torch.nn.functional as F
+from torch import nn
 
-from conftest import load_golden
-from test_transitions_cpu import SHAPES, ACTS, LONG_THIN, REF_ONE, case, run, failures, rel_err, inputs
+from op_checks import calls_of, dev, eac_fixture, gpgnn_fixture, kggat_fixture, pinned, rel_err, same
+from test_transitions_cpu import SHAPES, ACTS, LONG_THIN, REF_ONE, case, run, failures, inputs
 
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device("cuda:0")
 
 
 def chain_fn(x, Ws, bs, act):
@@ -26,25 +21,8 @@ def chain_fn(x, Ws, bs, act):
 
 
 def kernels_ran(monkeypatch):
-    """Counts the calls of the kernels' autograd function during a test."""
     from recon_amd import transitions
-    calls = []
-    real = transitions._PairTransitions.apply
-    monkeypatch.setattr(transitions._PairTransitions, "apply", staticmethod(lambda *a: (calls.append(1), real(*a))[1]))
-    return calls
-
-
-def linear_calls(monkeypatch):
-    calls = []
-    real = F.linear
-    monkeypatch.setattr(F, "linear", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
-    return calls
-
-
-def same(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        assert torch.equal(x, y)
+    return calls_of(monkeypatch, transitions._PairTransitions, "apply")
 
 
 @pytest.mark.parametrize("act", ACTS)
@@ -117,7 +95,7 @@ def test_second_backward_over_a_retained_graph_gives_the_same_bits(monkeypatch):
     x = c["x"].to(dev()).requires_grad_(True)
     Ws = [W.to(dev()).requires_grad_(True) for W in c["Ws"]]
     bs = [b.to(dev()).requires_grad_(True) for b in c["bs"]]
-    lin = linear_calls(monkeypatch)
+    lin = calls_of(monkeypatch, F, "linear")
     Ts = pair_transitions(x, Ws, bs, act)
     kept = [t.clone() for t in Ts]
     gs = [g.to(dev()) for g in c["g_out"]]
@@ -145,7 +123,7 @@ def test_no_grad_gives_the_training_forwards_bits():
 
 def test_create_graph_unsupported_shape_and_bf16_run_the_chain(monkeypatch):
     from recon_amd import _lib, pair_transitions
-    kernel_calls, lin = kernels_ran(monkeypatch), linear_calls(monkeypatch)
+    kernel_calls, lin = kernels_ran(monkeypatch), calls_of(monkeypatch, F, "linear")
     c = case((17, 20, 24, 3), "tanh")
     x = c["x"].to(dev()).requires_grad_(True)
     Ws = [W.to(dev()).requires_grad_(True) for W in c["Ws"]]
@@ -201,58 +179,22 @@ def test_empty_batch():
 
 
 # ------------------------------------------------------------------------------------------------------------- the models
-def _pinned(m, g, out_of, what, monkeypatch):
-    from test_gat_gpu import close
-    from torch import nn
-    m.fused_transitions = True
-    calls = kernels_ran(monkeypatch)
-    m.train().to(dev())
-    lins = [m.representation_to_adj] if m.tied else list(m.representation_to_adj)
-    assert lins and all(type(lin) is nn.Linear for lin in lins)
-    for lin in lins:
-        monkeypatch.setattr(lin, "forward", lambda *a, **k: pytest.fail("a projection's nn.Linear.forward ran"))
-    out = out_of(m)
-    assert len(calls) == 1
-    close(out, g["out"], atol=1e-4, what=what + " logits")
-    (out * torch.from_numpy(g["G"]).to(dev())).sum().backward()
-    seen = 0
-    for k, v in m.named_parameters():
-        if "g." + k in g:
-            close(v.grad, g["g." + k], atol=1e-4, rel_to_max=1e-4, what=what + " grad " + k)
-            seen += 1
-    assert seen == sum(k.startswith("g.") for k in g)
-    assert any(k.startswith("g.representation_to_adj") for k in g)
+def _through_the_op(fixture, monkeypatch):
+    def projections(m):
+        lins = [m.representation_to_adj] if m.tied else list(m.representation_to_adj)
+        assert lins and all(type(lin) is nn.Linear for lin in lins)
+        return lins, "a projection's nn.Linear.forward ran"
+    pinned(*fixture, monkeypatch, "fused_transitions", kernels_ran(monkeypatch), projections, ["g.representation_to_adj."])
 
 
 @pytest.mark.parametrize("name", ["gpgnn1_untied", "gpgnn2_tied_n9"])
 def test_gpgnn_fixture_through_the_op(name, monkeypatch):
-    from recon_amd.gpgnn import GPGNN
-    g = load_golden(name)
-    p = {"max_num_nodes": int(g["n"]), "embedding_dim": int(g["d"]), "layer_number": int(g["L"]), "projection_style": str(g["style"]),
-         "non-linear1": "relu", "non-linear": "tanh", "dropout1": 0.0, "position_emb": 3, "units1": 4, "rnn1_layers": 1,
-         "bidirectional": 1, "batch_size": int(g["B"])}
-    m = GPGNN(p, g["emb"], max_sent_len=4, n_out=3)
-    m.load_state_dict({k[3:]: torch.from_numpy(np.asarray(v)) for k, v in g.items() if k.startswith("sd.")}, strict=False)
-    _pinned(m, g, lambda m: m(torch.from_numpy(g["sent"]).to(dev()), torch.from_numpy(g["mark"]).to(dev()), None), name, monkeypatch)
+    _through_the_op(gpgnn_fixture(name), monkeypatch)
 
 
 def test_recon_eac_fixture_through_the_op(monkeypatch):
-    from recon_amd.gpgnn import RECON_EAC
-    from tests.test_host_cpu import EAC_P
-    g = load_golden("eac1_untied")
-    m = RECON_EAC(dict(EAC_P), g["emb"], max_sent_len=4, n_out=3, char_vocab=list(range(int(g["n_chars"]))))
-    m.load_state_dict({k[3:]: torch.from_numpy(np.asarray(v)) for k, v in g.items() if k.startswith("sd.")}, strict=False)
-    t = lambda k: torch.from_numpy(g[k]).to(dev())
-    _pinned(m, g, lambda m: m(t("sent"), t("mark"), None, None, None, t("ctx_words"), t("ctx_chars"), t("ctx_mask"), t("pos"), int(g["max_occ"])),
-            "eac1_untied", monkeypatch)
+    _through_the_op(eac_fixture(), monkeypatch)
 
 
 def test_recon_eac_kggat_fixture_through_the_op(monkeypatch):
-    from recon_amd.gpgnn import RECON_EAC_KGGAT
-    from tests.test_host_cpu import KGGAT_P
-    g = load_golden("kggat1_untied")
-    m = RECON_EAC_KGGAT(dict(KGGAT_P), g["emb"], max_sent_len=4, n_out=3, char_vocab=list(range(int(g["n_chars"]))))
-    m.load_state_dict({k[3:]: torch.from_numpy(np.asarray(v)) for k, v in g.items() if k.startswith("sd.")}, strict=False)
-    t = lambda k: torch.from_numpy(g[k]).to(dev())
-    _pinned(m, g, lambda m: m(t("sent"), t("mark"), None, None, None, t("ctx_words"), t("ctx_chars"), t("ctx_mask"), t("pos"), int(g["max_occ"]),
-                              t("gat")), "kggat1_untied", monkeypatch)
+    _through_the_op(kggat_fixture(), monkeypatch)

@@ -9,14 +9,11 @@ import pytest
 import torch
 
 from conftest import load_golden
+from op_checks import dev, peak_bytes, rel_err
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 7, 5), (17, 3, 50, 200), (65, 5, 200, 50), (33, 353, 200, 200), (130, 9, 33, 47)]
-
-
-def dev():
-    return torch.device("cuda:0")
 
 
 def reference(head, tail, W, rel, g_out=None):
@@ -49,10 +46,6 @@ def case(shape):
         ent_dim = shape[2]
         _CASES[shape] = (emb, W, rel, g_out, reference(emb[:, :ent_dim], emb[:, ent_dim:], W, rel, g_out))
     return _CASES[shape]
-
-
-def rel_err(got, ref):
-    return ((got.detach().double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
 
 
 def run(fn, emb, W, rel, g_out, contiguous=False):
@@ -123,14 +116,11 @@ def test_translation_memory():
     emb, W, rel, g_out = inputs(M, n_rel, ent_dim, rel_dim)
     rel.requires_grad_(True)
     head, tail = emb[:, :ent_dim], emb[:, ent_dim:]
-    translation_residuals(head, tail, W, rel).backward(g_out)            # warm-up: library load, allocator pools
-    rel.grad = None
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    translation_residuals(head, tail, W, rel).backward(g_out)
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
+
+    def forward_backward():
+        translation_residuals(head, tail, W, rel).backward(g_out)
+        rel.grad = None                                                   # the gradient counts in the peak and not in the next call's base
+    peak, _ = peak_bytes(forward_backward)
     print("translation memory: peak above the inputs %d bytes, one intermediate %d" % (peak, M * n_rel * rel_dim * 4))
     assert peak < M * n_rel * rel_dim * 4 // 4, peak
 

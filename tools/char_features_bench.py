@@ -21,36 +21,10 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from op_bench import run_rounds, summarise, write_lines  # noqa: E402
+
 ENTITIES = [45, 450]
 LINES, WORDS, MAX_CHAR, CFS, C, FO, V, P = 32, 32, 10, 3, 50, 50, 90, 0.5
-
-
-def timed(fn, g_out):
-    """(forward ms, forward + backward ms, peak bytes above what was allocated before) of fn() and its backward."""
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    e[0].record()
-    out = fn()
-    e[1].record()
-    out.backward(g_out)
-    e[2].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[1]), e[0].elapsed_time(e[2]), torch.cuda.max_memory_allocated() - base
-
-
-def launches(fn, g_out):
-    """Device-side events (kernels, memsets, copies) of one forward + backward, or None where the profiler is not available."""
-    try:
-        from torch.autograd import DeviceType
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn().backward(g_out)
-            torch.cuda.synchronize()
-        return sum(1 for ev in prof.events() if ev.device_type == DeviceType.CUDA)
-    except Exception:                                                      # the count is a by-product: the timings do not depend on it
-        return None
 
 
 def main():
@@ -99,30 +73,20 @@ def main():
             torch.cuda.synchronize()
             return e[0].elapsed_time(e[1])
 
+        def clear_grads():
+            E.grad = Wc.grad = b.grad = None
+
         for mode in ("eval", "train"):
             paths = {"op": lambda: op(mode == "train"), "chain": lambda: stock(mode == "train")}
             if mode == "train":
                 paths["op_packed"] = op_packed
-            res = {k: [] for k in paths}
-            for rnd in range(a.rounds + 1):                               # round 0 warms up
-                for k, fn in paths.items():
-                    E.grad = Wc.grad = b.grad = None
-                    r = timed(fn, g_out)
-                    if rnd:
-                        res[k].append(r)
+            res, _ = run_rounds(paths, g_out, clear_grads, a.rounds)
             geo = (S, WORDS, span, CFS, V, C, FO)
             line = {"entities": U, "S": S, "words": WORDS, "mode": mode, "rounds": a.rounds,
                     "compulsory_bytes": chars.numel() * 8 + S * WORDS * FO * 4, "gathered_embedding_bytes": S * Lc * C * 4,
                     "workspace_bytes_fwd": _lib.lib().recon_char_features_workspace_bytes(*geo, 0),
                     "workspace_bytes_bwd": _lib.lib().recon_char_features_workspace_bytes(*geo, 1)}
-            for k, rs in res.items():
-                for i, name in enumerate(("fwd_ms", "fwd_bwd_ms")):
-                    line["%s_%s_median" % (k, name)] = round(statistics.median(r[i] for r in rs), 4)
-                    line["%s_%s_min" % (k, name)] = round(min(r[i] for r in rs), 4)
-                line["%s_peak_bytes" % k] = max(r[2] for r in rs)
-                E.grad = Wc.grad = b.grad = None
-                line["%s_launches_fwd_bwd" % k] = launches(paths[k], g_out)
-            line["speedup_fwd_bwd_median"] = round(line["chain_fwd_bwd_ms_median"] / line["op_fwd_bwd_ms_median"], 3)
+            summarise(line, res, paths, g_out, clear_grads)
             if mode == "train":
                 geo_m = _lib.lib().recon_char_masked_workspace_bytes
                 line.update({"packed_bits_bytes": S * Lc * ((C + 31) // 32) * 4, "packed_workspace_bytes_fwd": geo_m(*geo, 0),
@@ -131,9 +95,7 @@ def main():
                              "speedup_packed_fwd_bwd_median": round(line["chain_fwd_bwd_ms_median"] / line["op_packed_fwd_bwd_ms_median"], 3)})
             lines.append(json.dumps(line))
             print(lines[-1], flush=True)
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    write_lines(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,6 @@ workspaces, and the largest difference of the two paths' outputs.  Lines are app
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -20,36 +19,10 @@ from torch import nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from op_bench import run_rounds, summarise, wiring_rule, write_lines  # noqa: E402
+
 ENTITIES = [45, 450]
 LINES, T, DW, FC, H, VW = 32, 32, 50, 50, 50, 4000
-
-
-def timed(fn, g_out):
-    """(forward ms, forward + backward ms, peak bytes above what was allocated before) of fn() and its backward."""
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    e[0].record()
-    out = fn()
-    e[1].record()
-    out.backward(g_out)
-    e[2].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[1]), e[0].elapsed_time(e[2]), torch.cuda.max_memory_allocated() - base
-
-
-def launches(fn, g_out):
-    """Device-side events (kernels, memsets, copies) of one forward + backward, or None where the profiler is not available."""
-    try:
-        from torch.autograd import DeviceType
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn().backward(g_out)
-            torch.cuda.synchronize()
-        return sum(1 for ev in prof.events() if ev.device_type == DeviceType.CUDA)
-    except Exception:                                                      # the count is a by-product: the timings do not depend on it
-        return None
 
 
 def main():
@@ -77,15 +50,12 @@ def main():
         def op():
             return context_line_states(lstm, feat, words, table)
 
+        def clear_grads():
+            lstm.zero_grad(set_to_none=True)
+            feat.grad = None
+
         paths = {"op": op, "chain": chain}
-        res = {k: [] for k in paths}
-        for rnd in range(a.rounds + 1):                                   # round 0 warms up
-            for k, fn in paths.items():
-                lstm.zero_grad(set_to_none=True)
-                feat.grad = None
-                r = timed(fn, g_out)
-                if rnd:
-                    res[k].append(r)
+        res, _ = run_rounds(paths, g_out, clear_grads, a.rounds)
         geo = (S, T, DW, FC, H)
         L = _lib.lib()
         with torch.no_grad():
@@ -94,21 +64,11 @@ def main():
                 "concatenated_input_bytes": S * T * (DW + FC) * 4, "lstm_output_bytes": S * T * 2 * H * 4,
                 "saved_bytes": L.recon_ctx_lstm_saved_bytes(*geo), "workspace_bytes_fwd": L.recon_ctx_lstm_workspace_bytes(*geo, 0),
                 "workspace_bytes_bwd": L.recon_ctx_lstm_workspace_bytes(*geo, 1), "max_abs_diff_op_chain": diff}
-        for k, rs in res.items():
-            for i, name in enumerate(("fwd_ms", "fwd_bwd_ms")):
-                line["%s_%s_median" % (k, name)] = round(statistics.median(r[i] for r in rs), 4)
-                line["%s_%s_min" % (k, name)] = round(min(r[i] for r in rs), 4)
-            line["%s_peak_bytes" % k] = max(r[2] for r in rs)
-            lstm.zero_grad(set_to_none=True)
-            feat.grad = None
-            line["%s_launches_fwd_bwd" % k] = launches(paths[k], g_out)
-        line["speedup_fwd_bwd_median"] = round(line["chain_fwd_bwd_ms_median"] / line["op_fwd_bwd_ms_median"], 3)
-        line["op_median_below_chain_min"] = line["op_fwd_bwd_ms_median"] < line["chain_fwd_bwd_ms_min"]
+        summarise(line, res, paths, g_out, clear_grads)
+        wiring_rule(line)
         lines.append(json.dumps(line))
         print(lines[-1], flush=True)
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    write_lines(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,6 @@ operations, and without dropout the largest difference of the two paths' outputs
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -22,48 +21,11 @@ from torch import nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from op_bench import put_ms, run_rounds, summarise, wiring_rule, write_lines  # noqa: E402
+
 BATCHES = [5, 50]
 DROPOUT = [0.0, 0.5]
 C, T, DW, P, H, VW, VP = 72, 36, 50, 3, 256, 4000, 4
-
-
-def timed(fn, g_out):
-    """(forward ms, forward + backward ms, peak bytes above what was allocated before) of fn() and its backward."""
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    e[0].record()
-    out = fn()
-    e[1].record()
-    out.backward(g_out)
-    e[2].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[1]), e[0].elapsed_time(e[2]), torch.cuda.max_memory_allocated() - base
-
-
-def timed_forward(fn):
-    torch.cuda.synchronize()
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    e[0].record()
-    with torch.no_grad():
-        fn()
-    e[1].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[1])
-
-
-def launches(fn, g_out):
-    """Device-side events (kernels, memsets, copies) of one forward + backward, or None where the profiler is not available."""
-    try:
-        from torch.autograd import DeviceType
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn().backward(g_out)
-            torch.cuda.synchronize()
-        return sum(1 for ev in prof.events() if ev.device_type == DeviceType.CUDA)
-    except Exception:                                                      # the count is a by-product: the timings do not depend on it
-        return None
 
 
 def main():
@@ -99,19 +61,12 @@ def main():
                 keep = draw_packed_keep(B * C, T, DW, p, d) if p > 0 else None
                 return pair_sentence_states(rnn, sentence, markers, table, pos, keep)
 
+            def clear_grads():
+                rnn.zero_grad(set_to_none=True)
+                pos.grad = None
+
             paths = {"op": op, "chain": chain}
-            res = {k: [] for k in paths}
-            nograd = []
-            for rnd in range(a.rounds + 1):                               # round 0 warms up
-                for k, fn in paths.items():
-                    rnn.zero_grad(set_to_none=True)
-                    pos.grad = None
-                    r = timed(fn, g_out)
-                    if rnd:
-                        res[k].append(r)
-                t = timed_forward(op)
-                if rnd:
-                    nograd.append(t)
+            res, nograd = run_rounds(paths, g_out, clear_grads, a.rounds, nograd=op)
             geo = (B, C, T, DW, P, H)
             L = _lib.lib()
             flop = 2 * B * C * T * 2 * (DW + P + H) * 4 * H
@@ -119,26 +74,16 @@ def main():
                     "input_bytes": sentence.numel() * 8 + markers.numel() * 8, "concatenated_input_bytes": B * C * T * (DW + P) * 4,
                     "lstm_output_bytes": B * C * T * 2 * H * 4, "saved_bytes": L.recon_sent_lstm_saved_bytes(*geo),
                     "workspace_bytes_fwd": L.recon_sent_lstm_workspace_bytes(*geo, VP, 0),
-                    "workspace_bytes_bwd": L.recon_sent_lstm_workspace_bytes(*geo, VP, 1), "forward_flop": flop,
-                    "op_fwd_nograd_ms_median": round(statistics.median(nograd), 4), "op_fwd_nograd_ms_min": round(min(nograd), 4)}
+                    "workspace_bytes_bwd": L.recon_sent_lstm_workspace_bytes(*geo, VP, 1), "forward_flop": flop}
+            put_ms(line, "op_fwd_nograd_ms", nograd)
             if p == 0:
                 with torch.no_grad():
                     line["max_abs_diff_op_chain"] = (op() - chain()).abs().max().item()
-            for k, rs in res.items():
-                for i, name in enumerate(("fwd_ms", "fwd_bwd_ms")):
-                    line["%s_%s_median" % (k, name)] = round(statistics.median(r[i] for r in rs), 4)
-                    line["%s_%s_min" % (k, name)] = round(min(r[i] for r in rs), 4)
-                line["%s_peak_bytes" % k] = max(r[2] for r in rs)
-                rnn.zero_grad(set_to_none=True)
-                pos.grad = None
-                line["%s_launches_fwd_bwd" % k] = launches(paths[k], g_out)
-            line["speedup_fwd_bwd_median"] = round(line["chain_fwd_bwd_ms_median"] / line["op_fwd_bwd_ms_median"], 3)
-            line["op_median_below_chain_min"] = line["op_fwd_bwd_ms_median"] < line["chain_fwd_bwd_ms_min"]
+            summarise(line, res, paths, g_out, clear_grads)
+            wiring_rule(line)
             lines.append(json.dumps(line))
             print(lines[-1], flush=True)
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    write_lines(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,6 @@ import argparse
 import json
 import math
 import os
-import statistics
 import sys
 
 import torch
@@ -22,48 +21,11 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from op_bench import put_ms, run_rounds, summarise, wiring_rule, write_lines  # noqa: E402
+
 BATCHES = [5, 50]
 STYLES = [("untied", 3, "relu"), ("tied", 1, "tanh")]
 C, K, N1 = 72, 512, 256
-
-
-def timed(fn, g_outs):
-    """(forward ms, forward + backward ms, peak bytes above what was allocated before) of fn() and its backward."""
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    e[0].record()
-    outs = fn()
-    e[1].record()
-    torch.autograd.backward(list(outs), g_outs)
-    e[2].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[1]), e[0].elapsed_time(e[2]), torch.cuda.max_memory_allocated() - base
-
-
-def timed_forward(fn):
-    torch.cuda.synchronize()
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    e[0].record()
-    with torch.no_grad():
-        fn()
-    e[1].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[1])
-
-
-def launches(fn, g_outs):
-    """Device-side events (kernels, memsets, copies) of one forward + backward, or None where the profiler is not available."""
-    try:
-        from torch.autograd import DeviceType
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            torch.autograd.backward(list(fn()), g_outs)
-            torch.cuda.synchronize()
-        return sum(1 for ev in prof.events() if ev.device_type == DeviceType.CUDA)
-    except Exception:                                                      # the count is a by-product: the timings do not depend on it
-        return None
 
 
 def main():
@@ -96,42 +58,25 @@ def main():
             def op():
                 return pair_transitions(x, Ws, bs, act)
 
+            def clear_grads():
+                for t in leaves:
+                    t.grad = None
+
             paths = {"op": op, "chain": chain}
-            res = {k: [] for k in paths}
-            nograd = []
-            for rnd in range(a.rounds + 1):                               # round 0 warms up
-                for k, fn in paths.items():
-                    for t in leaves:
-                        t.grad = None
-                    r = timed(fn, g_outs)
-                    if rnd:
-                        res[k].append(r)
-                t = timed_forward(op)
-                if rnd:
-                    nograd.append(t)
+            res, nograd = run_rounds(paths, g_outs, clear_grads, a.rounds, nograd=op)
             M = B * C
             lib = _lib.lib()
             line = {"B": B, "C": C, "M": M, "K": K, "N1": N1, "L": L, "style": style, "act": act, "rounds": a.rounds,
                     "input_bytes": sum(t.numel() for t in leaves) * 4, "output_bytes": L * M * N1 * 4,
-                    "workspace_bytes_bwd": lib.recon_pair_transitions_workspace_bytes(M, K, N1, L, 1), "forward_flop": 2 * M * K * N1 * L,
-                    "op_fwd_nograd_ms_median": round(statistics.median(nograd), 4), "op_fwd_nograd_ms_min": round(min(nograd), 4)}
+                    "workspace_bytes_bwd": lib.recon_pair_transitions_workspace_bytes(M, K, N1, L, 1), "forward_flop": 2 * M * K * N1 * L}
+            put_ms(line, "op_fwd_nograd_ms", nograd)
             with torch.no_grad():
                 line["max_abs_diff_op_chain"] = max((u - v).abs().max().item() for u, v in zip(op(), chain()))
-            for k, rs in res.items():
-                for i, name in enumerate(("fwd_ms", "fwd_bwd_ms")):
-                    line["%s_%s_median" % (k, name)] = round(statistics.median(r[i] for r in rs), 4)
-                    line["%s_%s_min" % (k, name)] = round(min(r[i] for r in rs), 4)
-                line["%s_peak_bytes" % k] = max(r[2] for r in rs)
-                for t in leaves:
-                    t.grad = None
-                line["%s_launches_fwd_bwd" % k] = launches(paths[k], g_outs)
-            line["speedup_fwd_bwd_median"] = round(line["chain_fwd_bwd_ms_median"] / line["op_fwd_bwd_ms_median"], 3)
-            line["op_median_below_chain_min"] = line["op_fwd_bwd_ms_median"] < line["chain_fwd_bwd_ms_min"]
+            summarise(line, res, paths, g_outs, clear_grads)
+            wiring_rule(line)
             lines.append(json.dumps(line))
             print(lines[-1], flush=True)
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    write_lines(a.out, lines)
 
 
 if __name__ == "__main__":

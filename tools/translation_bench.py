@@ -8,29 +8,15 @@ The two paths alternate round by round on the same random data."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from op_bench import put_ms, run_rounds, write_lines  # noqa: E402
+
 SHAPES = [(3600, 353, 200, 200), (300, 353, 200, 200)]
-
-
-def timed(fn, parts=False):
-    """(ms of fn(), peak bytes above what was allocated before); fn returns (out, g_out)."""
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    e[0].record()
-    out, g_out = fn()
-    e[1].record()
-    out.backward(g_out)
-    e[2].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[2]), e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2]), torch.cuda.max_memory_allocated() - base
 
 
 def main():
@@ -49,26 +35,18 @@ def main():
         rel = (torch.randn(n_out, rel_dim, generator=g) * 0.5).to(d).requires_grad_(True)
         g_out = torch.randn(M, n_out, generator=g).to(d)
         head, tail = emb[:, :ent_dim], emb[:, ent_dim:]
-        paths = {"fused": lambda: (translation_residuals(head, tail, W, rel), g_out), "chain": lambda: (_chain(head, tail, W, rel), g_out)}
-        res = {k: [] for k in paths}
-        for rnd in range(a.rounds + 1):                                   # round 0 warms up
-            for k, fn in paths.items():
-                rel.grad = None
-                r = timed(fn)
-                if rnd:
-                    res[k].append(r)
+        paths = {"fused": lambda: translation_residuals(head, tail, W, rel), "chain": lambda: _chain(head, tail, W, rel)}
+        res, _ = run_rounds(paths, g_out, lambda: setattr(rel, "grad", None), a.rounds)
         line = {"shape": [M, n_out, ent_dim, rel_dim], "rounds": a.rounds}
         for k, rs in res.items():
-            for i, name in enumerate(("fwd_bwd_ms", "fwd_ms", "bwd_ms")):
-                line["%s_%s_median" % (k, name)] = round(statistics.median(r[i] for r in rs), 4)
-                line["%s_%s_min" % (k, name)] = round(min(r[i] for r in rs), 4)
-            line["%s_peak_bytes" % k] = max(r[3] for r in rs)
+            put_ms(line, k + "_fwd_bwd_ms", (r[1] for r in rs))
+            put_ms(line, k + "_fwd_ms", (r[0] for r in rs))
+            put_ms(line, k + "_bwd_ms", (r[1] - r[0] for r in rs))        # the same two events' difference
+            line["%s_peak_bytes" % k] = max(r[2] for r in rs)
         line["speedup_median"] = round(line["chain_fwd_bwd_ms_median"] / line["fused_fwd_bwd_ms_median"], 3)
         lines.append(json.dumps(line))
         print(lines[-1], flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    write_lines(a.out, lines, mode="w")
 
 
 if __name__ == "__main__":
