@@ -1171,6 +1171,50 @@ int recon_pair_transitions_bwd(const float* x, int64_t ld_x, const float* const*
                                void* workspace, size_t workspace_bytes, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * E11 The relation classifier over its feature blocks (csrc/rel_head.hip): the head between the propagation and the logits,
+ *     logits = cat(block_0 .. block_{n-1}, S) W^T + b  (GPGNN and RECON_EAC models/models.py:213, :234, :275: one block; RECON_EAC_KGGAT
+ *     :693-697: the propagation features and the KB-GAT columns; RECON :954-966: those two and the scattered translation scores), without
+ *     the concatenated operand.  blocks, ld and widths are HOST arrays of n_blocks entries: device pointer, row stride (elements) and
+ *     width K_i >= 1 of block i, [M][K_i]; they travel by value in the kernel arguments.  The scattered block S [M][K_s] is given by
+ *     scattered [Mnz][K_s] (row stride ld_s) and positions [Mnz] (int64, STRICTLY INCREASING, inside [0, M)): row positions[i] of S is
+ *     scattered[i], every other row is zero (the zeros + index_put of :954-958).  K_s == 0: no such block; Mnz == 0: an all-zero block,
+ *     scattered and positions are not read.  A position outside [0, M) is never used as an address: the kernels ignore such a row.  W
+ *     [N][Kt] with Kt = sum K_i + K_s, b [N] or NULL, out and g_out [M][N], all fp32; W, b, out, g_out and the gradients contiguous.  No
+ *     width, stride or base needs more than 4-byte alignment: a block (or a block's weight columns) whose base, stride and width are
+ *     4-aligned is read as float4, any other element by element (per block in the backward; in the forward one such block puts the
+ *     operand's loads of the whole call on the element form).  Everything is fp32 on v_mfma_f32_16x16x4_f32, without atomics, every
+ *     sum in an order the shapes and the positions decide: bitwise identical from run to run.  Status codes and the 16-byte alignment of
+ *     workspace are those of the E8 - E10 entries.
+ * ------------------------------------------------------------------------------------------*/
+/* Shapes the kernels take (models/models.py:213, :234, :275, :693-697, :954-966): 0 <= M <= 2^24, 1 <= n_blocks <= 4 dense blocks (plus
+ * the scattered one), 1 <= Kt <= 2048 for the weight's row length, 1 <= N <= 1024.  Everything else answers RECON_ERR_UNSUPPORTED and
+ * writes nothing; the caller then runs the stock ops. */
+int recon_relation_logits_supported(int64_t M, int32_t n_blocks, int32_t Kt, int32_t N);
+/* Bytes of the workspace (models/models.py:213, :234, :275, :693-697, :954-966).  Forward (backward = 0): none.  Backward
+ * (backward = 1): G slabs of N (Kt + 1) floats, one per row group, where G = min(8, ceil(M / 32)) and a group is per = ceil(M / G)
+ * consecutive rows: a function of M alone.  16-byte aligned, any contents; 0 for a shape recon_relation_logits_supported refuses and
+ * for M == 0. */
+size_t recon_relation_logits_workspace_bytes(int64_t M, int32_t n_blocks, int32_t Kt, int32_t N, int32_t backward);
+/* Forward (models/models.py:213, :234, :275, :693-697, :954-966): [M][Kt] x [Kt][N] in 64 x 64 tiles with the bias (NULL: none) in the
+ * epilogue.  The reduction walks the blocks in order, 32 columns per step, a step inside ONE block (a block's last step is filled with
+ * zeros); whether a staged row is present in the scattered block is one binary search over positions per thread.  M == 0: nothing is
+ * launched.  One launch. */
+int recon_relation_logits_fwd(const float* const* blocks, const int64_t* ld, const int32_t* widths, int32_t n_blocks, const float* scattered,
+                              int64_t ld_s, int32_t K_s, const int64_t* positions, int64_t Mnz, const float* weight, const float* bias, int64_t M,
+                              int32_t N, float* out, recon_stream_t stream);
+/* Backward (models/models.py:213, :234, :275, :693-697, :954-966); it destroys nothing (any number of backwards per forward, the same bits
+ * each time).  g_blocks: HOST array of n_blocks device pointers, g_blocks[i] [M][K_i] contiguous = g_out W[:, cols_i], or NULL (g_blocks
+ * itself or an entry: not wanted, no work is done for it); g_scattered [Mnz][K_s] contiguous or NULL: row i = g_out[positions[i]]
+ * W[:, cols_s] (zeros for a position outside [0, M)); one launch over the column tiles of the wanted blocks, skipped when there is none.
+ * g_w [N][Kt] and g_b [N] (NULL: not wanted; both NULL: both launches are skipped) = g_out^T (cat | 1): workgroup (column tile, row tile,
+ * z) writes its part of slab z of the workspace over row group z — for the scattered block over the present rows of the group alone —
+ * then the slabs are added in group order.  M == 0 writes zeros to every wanted gradient and launches no kernel.  At most three launches. */
+int recon_relation_logits_bwd(const float* const* blocks, const int64_t* ld, const int32_t* widths, int32_t n_blocks, const float* scattered,
+                              int64_t ld_s, int32_t K_s, const int64_t* positions, int64_t Mnz, const float* weight, const float* g_out, int64_t M,
+                              int32_t N, float* const* g_blocks, float* g_scattered, float* g_w, float* g_b, void* workspace,
+                              size_t workspace_bytes, recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
  *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
  * ------------------------------------------------------------------------------------------*/

@@ -7,3 +7,4 @@ from .char_features import char_word_features  # noqa: E402,F401
 from .context_lstm import context_line_states  # noqa: E402,F401
 from .sentence_lstm import pair_sentence_states  # noqa: E402,F401
 from .transitions import pair_transitions  # noqa: E402,F401
+from .relation_head import relation_logits  # noqa: E402,F401

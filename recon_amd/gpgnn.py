@@ -4,8 +4,10 @@ representation_to_adj[.i].weight/bias, identity_transformation, start_embedding,
 linear3.*), so a checkpoint written by the reference's train.py:415-416 loads unchanged.  The sentence encoder's
 embeddings and LSTM run as `pair_sentence_states` (csrc/sent_lstm.hip; the stock PyTorch-ROCm ops where it does not apply), its
 per-hop projections as `pair_transitions` (csrc/pair_trans.hip; `F.linear` and the activation where it does not apply); the
-block-adjacency construction and the L-hop propagation with its fused head*tail gather run on the HIP kernels of csrc/prop.hip.
-SURVEY.md 8f row N3."""
+block-adjacency construction and the L-hop propagation with its fused head*tail gather run on the HIP kernels of csrc/prop.hip.  The
+classifier behind them is `classify`: `linear3` alone where the propagation features are its only input (GPGNN, RECON_EAC), and
+`relation_logits` (csrc/rel_head.hip) over the feature blocks where they lie — no `cat`, no `zeros`, no `index_put` — in RECON_EAC_KGGAT
+and RECON when `fused_classifier` is on (the stock ops otherwise).  SURVEY.md 8f row N3."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -16,6 +18,7 @@ from .char_features import char_word_features, draw_packed_keep
 from .context_lstm import context_line_states
 from .sentence_lstm import pair_sentence_states
 from .transitions import pair_transitions
+from .relation_head import relation_logits
 
 
 class GPGNN(nn.Module):
@@ -108,6 +111,32 @@ class GPGNN(nn.Module):
                 Ts.append(T)
         return Ts * L if self.tied else Ts
 
+    # fused_classifier: run the classifier as `relation_logits` (csrc/rel_head.hip) whenever linear3 is a plain nn.Linear and there is
+    # something to fuse, a second feature block or the scattered one; DESIGN.md section 23 says why this is the default it is.
+    fused_classifier = True
+
+    def classify(self, relation, gat=None, scores=None, positions=None):
+        """The logits of the feature blocks, in relation's leading shape: `relation` [..., 2d L] alone (models/models.py:213, :234, :275), with the
+        KB-GAT columns `gat` behind it (:693-697), and with the scattered block of `scores` [Mnz, n_out] at the rows `positions` behind both
+        (:954-966; relation and gat are then [M, .] as `RECON.forward` reshapes them: the positions count rows).  `scores` may be a function without arguments that returns the tensor: the stock lines call it where they call
+        `translation_scores` today, after the `zeros` and only when there is a position.  One block is one GEMM and has nothing to fuse
+        (DESIGN.md section 22 found the same for the tied projection): it always runs `linear3`."""
+        lin = self.linear3
+        if self.fused_classifier and type(lin) is nn.Linear and (gat is not None or positions is not None):
+            if positions is not None:
+                positions = positions.to(relation.device)
+                if positions.shape[0] == 0:
+                    scores = relation.new_zeros((0, self.W_ent2rel.shape[0]))
+                elif callable(scores):
+                    scores = scores()
+            return relation_logits([relation] if gat is None else [relation, gat], lin.weight, lin.bias, scores, positions)
+        if positions is None:
+            return lin(relation if gat is None else torch.cat([relation, gat], dim=-1))                                       # :693-694
+        block = torch.zeros(relation.shape[:-1] + (self.W_ent2rel.shape[0],), device=relation.device, dtype=relation.dtype)   # :954-958
+        if positions.shape[0] > 0:
+            block = block.index_put((positions.to(relation.device),), scores() if callable(scores) else scores)
+        return lin(torch.cat([relation, gat, block], dim=-1))                                                                # :960-961
+
     def forward(self, sentence_input, entity_markers, num_entities=None):
         """(B, max_sent_len), (B, C, max_sent_len) -> (B*C, n_out).  Unlike the reference, any batch size works
         (its head/tail index tensors bake in 50, models/models.py:138-142; the kernels take the [C,2d] pattern)."""
@@ -118,7 +147,7 @@ class GPGNN(nn.Module):
         Ts = self.transitions(rnn_result)
         # :240-274 — block adjacency + propagation; fused (A_l never materialised) where the kernels allow, else build_block_adjacency + propagate
         relation = propagate_blocks(Ts, self.identity_transformation, n, self.start_embedding, p['non-linear1'], self.head_indices[0], self.tail_indices[0])
-        return self.linear3(relation).view(B * self.MAX_EDGES_PER_GRAPH, -1)
+        return self.classify(relation).view(B * self.MAX_EDGES_PER_GRAPH, -1)
 
 
 class CharEmbeddings(nn.Module):
@@ -202,7 +231,8 @@ class RECON_EAC(GPGNN):
     """The reference's `RECON_EAC` (models/models.py:279-487): GPGNN whose start embedding is built PER BATCH from the entity
     attribute context (`EntityEmbedding` -> `make_start_entity_embeddings`, utils/context_utils.py:387-426) instead of the
     fixed one-hot template.  Same constructor, forward signature and state_dict keys (GPGNN's plus entity_embedding_module.*).
-    The per-batch start vectors, the block adjacency and the L-hop propagation run on the HIP kernels of csrc/prop.hip.
+    The per-batch start vectors, the block adjacency and the L-hop propagation run on the HIP kernels of csrc/prop.hip; the classifier
+    is `linear3` alone (`classify` with one block: one GEMM has nothing to fuse).
 
     Two places where the reference's code cannot be followed literally: its tied-projection branch (:401-445) hard-codes
     9 nodes AND ignores the context embeddings (it propagates the fixed template) — kept as is, through GPGNN.forward; and its
@@ -236,13 +266,15 @@ class RECON_EAC(GPGNN):
             return GPGNN.forward(self, sentence_input, entity_markers, num_entities)
         relation = self.relation_features(sentence_input, entity_markers, context_words, context_chars, context_mask, entities_position,
                                           max_occurred_entity_in_batch_pos)
-        return self.linear3(relation).view(relation.size(0) * self.MAX_EDGES_PER_GRAPH, -1)
+        return self.classify(relation).view(relation.size(0) * self.MAX_EDGES_PER_GRAPH, -1)
 
 
 class RECON_EAC_KGGAT(RECON_EAC):
     """The reference's `RECON_EAC_KGGAT` (models/models.py:489-701): RECON_EAC whose classifier also sees the stage-A KB-GAT
     embeddings of each pair's head and tail entity (`gat_entity_embeddings` [B, C, 2 * gat_entity_embedding_dim], concatenated
-    behind the propagation features, :693-697).  Same constructor, forward signature and state_dict keys as the reference.
+    behind the propagation features, :693-697).  With `fused_classifier` on, `classify` runs `linear3` over the two blocks where they
+    lie (`relation_logits`, csrc/rel_head.hip: no `cat`, no gradient for the KB-GAT columns); otherwise `cat` and `linear3` as there.
+    Same constructor, forward signature and state_dict keys as the reference.
 
     The reference's tied-projection branch (:597-649) feeds the propagation features alone to a classifier sized for the
     concatenation and fails in `linear3`; here it fails with the same exception type before any work is done."""
@@ -259,15 +291,17 @@ class RECON_EAC_KGGAT(RECON_EAC):
                                % (self.p['embedding_dim'] * 2 * self.p['layer_number'], self.linear3.in_features))
         relation = self.relation_features(sentence_input, entity_markers, context_words, context_chars, context_mask, entities_position,
                                           max_occurred_entity_in_batch_pos)
-        both = torch.cat([relation, gat_entity_embeddings.to(relation.dtype)], dim=-1)                                      # :693-694
-        return self.linear3(both).view(relation.size(0) * self.MAX_EDGES_PER_GRAPH, -1)
+        logits = self.classify(relation, gat_entity_embeddings.to(relation.dtype))                                         # :693-697
+        return logits.view(relation.size(0) * self.MAX_EDGES_PER_GRAPH, -1)
 
 
 class RECON(RECON_EAC):
     """The reference's full model `RECON` (models/models.py:703-968): RECON_EAC + the KB-GAT entity embeddings of every pair +
     a per-relation triple score in the relation space of GAT_sep_space: for each pair with known embeddings,
     `|| tanh(head W_r) + g_r - tanh(tail W_r) ||_1` for every output relation r (:940-958), scattered into a [B*C, n_out]
-    block behind the other features.  Constructor arguments, forward signature and state_dict keys follow the reference
+    block behind the other features.  With `fused_classifier` on, `classify` hands the scores and their positions to `relation_logits`
+    (csrc/rel_head.hip), which runs `linear3` over the three blocks without the `zeros`, the `index_put` or the `cat`; otherwise the
+    stock lines.  Constructor arguments, forward signature and state_dict keys follow the reference
     (`gat_relation_embeddings` trainable, `W_ent2rel` frozen; head / tail index tensors are plain attributes there, :759-768,
     and non-persistent buffers here so that `.to(device)` moves them and checkpoints stay key-compatible).
 
@@ -316,7 +350,6 @@ class RECON(RECON_EAC):
         rows = relation.size(0) * self.MAX_EDGES_PER_GRAPH
         relation = relation.reshape(rows, -1)                                                                               # :926
         gat = gat_entity_embeddings.to(relation.dtype).reshape(rows, -1)                                                    # :927
-        scores = torch.zeros(rows, self.W_ent2rel.shape[0], device=relation.device, dtype=relation.dtype)                  # :954-958
-        if nonzero_gat_entity_embeddings.shape[0] > 0:
-            scores = scores.index_put((nonzero_entity_pos.to(relation.device),), self.translation_scores(nonzero_gat_entity_embeddings))
-        return self.linear3(torch.cat([relation, gat, scores], dim=-1))                                                     # :960-961
+        # (no pair with known embeddings: an all-zero score block, whatever the positions hold)
+        positions = nonzero_entity_pos if nonzero_gat_entity_embeddings.shape[0] > 0 else nonzero_entity_pos[:0]
+        return self.classify(relation, gat, lambda: self.translation_scores(nonzero_gat_entity_embeddings), positions)     # :954-966
