@@ -1215,6 +1215,41 @@ int recon_relation_logits_bwd(const float* const* blocks, const int64_t* ld, con
                               size_t workspace_bytes, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * E12 The entity-level tail of the entity-context encoder (csrc/line_pool.hip): conv1d_entity over the line states, the line mask and
+ *     the max over the lines (models/models.py:73-81) as one op:
+ *     out[u][e] = max over unmasked p of  bias[e] + sum_{j < k} sum_c weight[e][c][j] states[u][p + j][c],   P = Ln - k + 1 positions.
+ *     states: U Ln rows of C floats at ONE row stride ld >= C (elements), entity u's line l at row u Ln + l; weight [E][C][k]
+ *     (nn.Conv1d's layout), bias [E], out and g_out [U][E], all fp32 and contiguous but for ld; mask [U][P] bytes, nonzero = padding
+ *     position, any pattern.  An exact tie takes the lowest position; an entity without an unmasked position gives -inf and no gradient;
+ *     a NaN at an unmasked position gives NaN.  positions [U][E] bytes: the winning position, 255 for none.  Everything is fp32 on the
+ *     VALU, without atomics, every sum in an order the shapes alone decide: bitwise identical from run to run.  Neither the [U][E][P]
+ *     convolution output nor its masked copy exists.  Status codes and the 16-byte alignment of workspace are those of the E8 - E11
+ *     entries; nothing is allocated inside the library.
+ * ------------------------------------------------------------------------------------------*/
+/* Shapes the kernels take (models/models.py:73-81): 0 <= U <= 2^30, 1 <= k <= Ln, P = Ln - k + 1 <= 255 (the position byte), C k <= 1024,
+ * 1 <= E <= 64.  Everything else answers RECON_ERR_UNSUPPORTED and writes nothing; the caller then runs the stock ops. */
+int recon_line_pool_supported(int64_t U, int32_t Ln, int32_t C, int32_t E, int32_t k);
+/* Bytes of the backward's workspace (models/models.py:73-81): G slabs of E (C k + 1) floats, one per entity group, where
+ * per = ceil(U / min(256, U)) consecutive entities make a group and G = ceil(U / per): a function of U alone.  16-byte aligned, any
+ * contents; 0 for a shape recon_line_pool_supported refuses and for U == 0.  The forward needs none. */
+size_t recon_line_pool_workspace_bytes(int64_t U, int32_t Ln, int32_t C, int32_t E, int32_t k);
+/* Forward (models/models.py:73-81): one workgroup per entity stages the weight and the entity's line states in LDS (in chunks where they
+ * do not fit), forms every (position, channel) sum as one fma chain over j then c, adds the bias and keeps the first maximum among the
+ * unmasked positions.  positions may be NULL (no backward will follow): then only out is written.  U == 0: nothing is launched.  One
+ * launch. */
+int recon_line_pool_fwd(const float* states, int64_t ld, const float* weight, const float* bias, const void* mask, int64_t U, int32_t Ln,
+                        int32_t C, int32_t E, int32_t k, float* out, void* positions, recon_stream_t stream);
+/* Backward (models/models.py:73-81); it destroys nothing (any number of backwards per forward, the same bits each time).
+ * g_states [U][Ln][C] contiguous or NULL: d_states[u][l][c] = sum over e ascending of [0 <= l - pos[u][e] < k] g_out[u][e]
+ * weight[e][c][l - pos[u][e]]; every cell is written once, zeros included.  g_w [E][C][k] and g_b [E] (NULL: not wanted; both NULL: the
+ * slab work and the second launch are skipped): d_weight[e][c][j] = sum_u g_out[u][e] states[u][pos[u][e] + j][c], d_bias[e] = sum_u
+ * [pos[u][e] != 255] g_out[u][e], each entity group summed upwards into its slab of the workspace, the slabs added in group order.
+ * U == 0 writes zeros to g_w and g_b and launches no kernel.  At most two launches. */
+int recon_line_pool_bwd(const float* states, int64_t ld, const float* weight, const float* g_out, const void* positions, int64_t U,
+                        int32_t Ln, int32_t C, int32_t E, int32_t k, float* g_states, float* g_w, float* g_b, void* workspace,
+                        size_t workspace_bytes, recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
  *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
  * ------------------------------------------------------------------------------------------*/

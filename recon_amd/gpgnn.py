@@ -19,6 +19,7 @@ from .context_lstm import context_line_states
 from .sentence_lstm import pair_sentence_states
 from .transitions import pair_transitions
 from .relation_head import relation_logits
+from .line_pool import entity_line_pool
 
 
 class GPGNN(nn.Module):
@@ -182,13 +183,16 @@ class EntityEmbedding(nn.Module):
     vectors + char-CNN features) run through an LSTM; the final states of all lines of one entity are convolved and max-pooled
     over the unmasked lines into one vector per entity.  The char-CNN is `char_word_features` (csrc/char_cnn.hip), the word gather and
     the LSTM are `context_line_states` (csrc/ctx_lstm.hip; the stock ops when word_embeddings is not a plain nn.Embedding); the entity-level
-    convolution is a stock PyTorch-ROCm op: this is the encoder in front of the propagation path, not the path.
+    convolution, the line mask and the max over the lines are `entity_line_pool` (csrc/line_pool.hip) when `fused_line_pool` is on and
+    conv1d_entity is a plain nn.Conv1d (stride 1, no padding, dilation 1, groups 1, with a bias), the stock ops otherwise.
     Keys: word_embeddings.weight (the caller's table, shared), char_embeddings.embeddings.weight, lstm.*, conv1d.*, conv1d_entity.*.
     packed_char_dropout (default False): draw the char embedding's dropout as packed bits (`CharEmbeddings.draw_packed_keep`), so that
     training batches run the masked char-CNN kernels instead of the op chain.  Same distribution, another random stream than the
     reference's nn.Dropout call: an opt-in, like `iid_keep_draws` of models.SpKBGATModified."""
 
     packed_char_dropout = False
+    # fused_line_pool: run the last three lines of `forward` as `entity_line_pool` (DESIGN.md section 24 has the measurement behind the default)
+    fused_line_pool = True
 
     def __init__(self, input_dim, hidden_dim, layers, is_bidirectional, drop_out_rate, entity_embed_dim, conv_filter_size,
                  entity_conv_filter_size, word_embeddings, char_embed_dim, max_word_len_entity, char_vocab, char_feature_size):
@@ -222,6 +226,10 @@ class EntityEmbedding(nn.Module):
             _, (h_n, _) = self.lstm(torch.cat((word_vec, char_feat), -1))
             # last layer, both directions side by side (the reference reshapes to (layers, 2, batch, hidden): bidirectional only)
             h_n = h_n.view(self.layers, 2, U * lines, self.hidden_dim)[-1].permute(1, 0, 2).reshape(U, lines, 2 * self.hidden_dim)
+        ce = self.conv1d_entity
+        if (self.fused_line_pool and type(ce) is nn.Conv1d and ce.bias is not None and ce.stride == (1,) and ce.padding == (0,)
+                and ce.dilation == (1,) and ce.groups == 1):                                                                # :73-81
+            return entity_line_pool(h_n, ce.weight, ce.bias, conv_mask)
         conv = self.conv1d_entity(h_n.permute(0, 2, 1))
         conv = conv.masked_fill(conv_mask.unsqueeze(1), -float('inf'))
         return conv.max(dim=2).values
