@@ -1250,6 +1250,52 @@ int recon_line_pool_bwd(const float* states, int64_t ld, const float* weight, co
                         size_t workspace_bytes, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * E13 The stage-B objective between the logits and the optimiser (csrc/objective.hip): CrossEntropyLoss(ignore_index) over [M][n_out],
+ *     torch.max's indices, the softmax probability of the prediction and the counters of evaluate_instance_based (train.py:232,
+ *     :309-324, test.py:274-291, utils/evaluation_utils.py:17-59) without the [M][n_out] log-softmax and without a host read:
+ *     lse[m] = log sum_c exp(x[m][c] - max_m) (the row's log-sum-exp LESS its maximum: with the maximum added in fp32 the backward's
+ *     softmax would carry the maximum's rounding; the backward takes the maximum, which is exact, from the row again),
+ *     term[m] = lse[m] - (x[m][labels[m]] - max_m), loss = (sum of the kept rows' terms, row order, fp64, rounded once) / kept, where a
+ *     row is kept when labels[m] != ignore_index; predicted[m] = the lowest index of the row's
+ *     maximum, a NaN counting as the maximum (the lowest NaN); confidence[m] = 1 / sum_c exp(x[m][c] - max_m); counts = {kept, n_pred,
+ *     n_gold, n_ok} over the kept rows: predicted != empty_label, labels != empty_label, predicted == labels != empty_label;
+ *     prec = n_ok / n_pred and rec = n_ok / n_gold (0 where the denominator is 0), f1 = 2.0 prec rec / (prec + rec) in that order in
+ *     fp64 (0 where prec + rec == 0).  kept == 0: loss NaN (0 / 0).  A kept row whose label lies outside [0, n_out) has the term NaN, a
+ *     zero gradient row and counts as gold; its label is never used as an address.  +inf, -inf and NaN in a row go through the plain
+ *     arithmetic above, which is log_softmax's.  logits: M rows of n_out floats at ONE row stride ld >= n_out (elements); labels [M]
+ *     int64; predicted [M] int64; confidence, lse [M] fp32; loss [1] fp32; counts [4] int64; f1 [1] fp64; g_logits [M][n_out] contiguous.
+ *     No atomics, every sum in an order M and n_out decide: bitwise identical from run to run.  Status codes and the 16-byte alignment of
+ *     workspace are those of the E8 - E12 entries; nothing is allocated inside the library.
+ * ------------------------------------------------------------------------------------------*/
+/* Shapes the kernels take (train.py:232, train.py:309-324, test.py:274-291, utils/evaluation_utils.py:17-59): 0 <= M <= 2^30,
+ * 1 <= n_out <= 8192 (a row up to 512 wide is held in registers, a wider one is walked twice).  Everything else answers
+ * RECON_ERR_UNSUPPORTED and writes nothing; the caller then runs the stock ops. */
+int recon_relation_objective_supported(int64_t M, int32_t n_out);
+/* Bytes of the forward's workspace (train.py:232, train.py:309-324, test.py:274-291, utils/evaluation_utils.py:17-59): the M row terms,
+ * fp32.  16-byte aligned, any contents; 0 for a shape recon_relation_objective_supported refuses and for M == 0.  Not needed with
+ * labels == NULL.  The backward needs none. */
+size_t recon_relation_objective_workspace_bytes(int64_t M, int32_t n_out);
+/* Forward (train.py:232, train.py:309-324, test.py:274-291, utils/evaluation_utils.py:17-59).  First launch: a wavefront per row writes
+ * predicted, confidence, the row's term into the workspace and, when lse != NULL (a backward will follow), the row's lse as defined above.
+ * Second launch: one workgroup adds the kept rows' terms in a fixed order, counts, and writes loss, counts and f1; with acc_counts [4]
+ * int64, acc_f1_sum [1] fp64 and acc_batches [1] int64 (all three or none) it also adds counts, f1 and 1 to them, so that an epoch's
+ * sums stay on the device: acc_f1_sum holds the bits of the reference's `f1 += add_f1` over the same batches in the same order.
+ * labels == NULL is the test-time form: predicted and confidence alone, one launch; loss, lse, counts, f1 and the accumulator must then
+ * be NULL.  M == 0: nothing is launched and nothing is written. */
+int recon_relation_objective_fwd(const float* logits, int64_t ld, const int64_t* labels, int64_t M, int32_t n_out, int64_t ignore_index,
+                                 int64_t empty_label, float* loss, int64_t* predicted, float* confidence, float* lse, int64_t* counts,
+                                 double* f1, int64_t* acc_counts, double* acc_f1_sum, int64_t* acc_batches, void* workspace,
+                                 size_t workspace_bytes, recon_stream_t stream);
+/* Backward (train.py:232, train.py:309-324, test.py:274-291, utils/evaluation_utils.py:17-59); it destroys nothing (any number of
+ * backwards per forward, the same bits each time).  g_logits[m][c] = g_loss[0] (exp((x[m][c] - max_m) - lse[m]) - [c == labels[m]]) / counts[0] for
+ * a kept row with a label inside [0, n_out); a zero row for an ignored row and for a label outside; all zeros when counts[0] == 0.
+ * g_loss [1] fp32 (the incoming gradient of loss) and counts (the forward's) are read on the device: the host never learns kept.  Every
+ * cell is written exactly once.  M == 0: nothing is launched.  One launch. */
+int recon_relation_objective_bwd(const float* logits, int64_t ld, const int64_t* labels, const float* lse, const float* g_loss,
+                                 const int64_t* counts, int64_t M, int32_t n_out, int64_t ignore_index, float* g_logits,
+                                 recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * E2  KG training of the ConvKB scorer (csrc/kg_train.hip): stage B of KB-GAT, train_conv (GAT/main.py:707-860), over frozen tables.
  *     Indices: int32 or int64 [rows][3] = (head, relation, tail), index_bytes = 4 or 8.
  * ------------------------------------------------------------------------------------------*/

@@ -9,3 +9,4 @@ from .sentence_lstm import pair_sentence_states  # noqa: E402,F401
 from .transitions import pair_transitions  # noqa: E402,F401
 from .relation_head import relation_logits  # noqa: E402,F401
 from .line_pool import entity_line_pool  # noqa: E402,F401
+from .objective import RelationMetrics, relation_objective  # noqa: E402,F401

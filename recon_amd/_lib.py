@@ -255,6 +255,11 @@ SYMBOLS = [
     ("recon_line_pool_fwd", C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_void_p, C.c_int64] + [C.c_int32] * 4 + [c_f32p, C.c_void_p, C.c_void_p]),
     ("recon_line_pool_bwd", C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_void_p, C.c_int64] + [C.c_int32] * 4 + [c_f32p] * 3
                                      + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("recon_relation_objective_supported", C.c_int, [C.c_int64, C.c_int32]),
+    ("recon_relation_objective_workspace_bytes", C.c_size_t, [C.c_int64, C.c_int32]),
+    ("recon_relation_objective_fwd", C.c_int, [c_f32p, C.c_int64, c_i64p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, c_f32p, c_i64p, c_f32p, c_f32p,
+                                              c_i64p, C.c_void_p, c_i64p, C.c_void_p, c_i64p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("recon_relation_objective_bwd", C.c_int, [c_f32p, C.c_int64, c_i64p, c_f32p, c_f32p, c_i64p, C.c_int64, C.c_int32, C.c_int64, c_f32p, C.c_void_p]),
     ("recon_start_entity_embeddings", C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p,
                                                 C.c_void_p]),
     ("recon_start_entity_embeddings_bwd", C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_void_p, C.c_void_p]),
