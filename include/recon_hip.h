@@ -631,13 +631,15 @@ typedef struct {
 
 typedef struct {
     recon_gcn_b16_args fwd;
-    const void* grad_out; int64_t ldg;   /* [B*n, ldg] bf16                                                      */
-    void* g_support;                /* [B*n, fwd.lds] bf16 workspace                                             */
+    const void* grad_out; int64_t ldg;   /* [B*n, ldg] bf16; ldg % 8 == 0 and >= out rounded up to 8                */
+    void* g_support;                /* [B*n, fwd.lds] bf16 workspace, 16-byte aligned: fwd.lds % 8 == 0 and >= out *
+                                     * rounded up to 8 also where the forward ran with support == NULL; columns    *
+                                     * out .. fwd.lds are written as zeros                                          */
     float* partial;                 /* recon_gcn_b16_bwd_partial_floats() floats; ragged batch:                  *
                                      * recon_gcn_b16_bwd_partial_floats(1, total_rows, in, out) + B * out floats  */
     void* g_x; int64_t ldgx;        /* [B*n, ldgx] bf16 or NULL                                                  */
-    void* g_adj;                    /* [B, n, n] bf16 or NULL                                                    */
-    void* g_weight;                 /* [in, out] bf16 or NULL                                                    */
+    void* g_adj;                    /* [B, n, n] bf16 or NULL; reads fwd.support (RECON_ERR_INVALID without it)   */
+    void* g_weight;                 /* [in, out] bf16 or NULL; reads x in rows of fwd.ldx % 8 == 0 elements       */
     void* g_bias;                   /* [out] bf16 or NULL                                                        */
     const void* zeros;              /* >= 1 KiB of zero bytes, 16-byte aligned (K tails of the k-major GEMM)     */
 } recon_gcn_b16_bwd_args;
@@ -647,10 +649,28 @@ int recon_gcn_b16_fwd(const recon_gcn_b16_args* args, recon_stream_t stream);
 size_t recon_gcn_b16_bwd_partial_floats(int32_t B, int32_t n, int32_t in_features, int32_t out_features);
 int recon_gcn_b16_bwd(const recon_gcn_b16_bwd_args* args, recon_stream_t stream);
 
+/* Which kernels a call launches: recon_gcn_b16_fwd_instance() for recon_gcn_b16_fwd(args), recon_gcn_b16_bwd_instance() for
+ * recon_gcn_b16_bwd(args).  Computed by the plan the launchers dispatch on (csrc/gcn_b16.hip gcn_fwd_plan / gcn_bwd_plan), RECON_GCN_FUSED
+ * and RECON_GCN_FUSED_BWD included; host arithmetic only: no device is needed and the pointers are looked at for null and for alignment,
+ * never followed.  Returns -1 where the call would be refused, 0 where it launches nothing (B == 0, total_rows == 0), else
+ *   forward   1  k_gcn_b16_fused_fwd<4, true>   (support == NULL; n % 4 == 0, out % 4 == 0, adj and bias 8-byte aligned: 8-byte loads)
+ *             2  k_gcn_b16_fused_fwd<2, false>  (support == NULL; element loads of adj and bias)
+ *             3  k_gemm_b16 + k_gcn_b16_aggregate (support given)
+ *             4  the same over a ragged batch (node_ptr given)
+ *   backward  path * 100000 + g_adj * 10000 + bias * 1000 + splits
+ *             path    1 k_gcn_b16_fused_bwd (g_support and g_x in one launch), 2 k_gcn_b16_aggregate (+ k_gemm_b16 for g_x)
+ *             g_adj   1 where k_gcn_b16_grad_adj is launched
+ *             bias    0 no g_bias, 1 its second pass rides in k_b16_reduce behind the weight gradient, 2 k_gcn_b16_bias_reduce alone
+ *             splits  split-K count of k_gemm_b16_kmajor for g_weight (1 .. 64), 0 without g_weight
+ * e.g. 101017 = fused backward, g_bias in the reduce, 17 splits. */
+int32_t recon_gcn_b16_fwd_instance(const recon_gcn_b16_args* args);
+int32_t recon_gcn_b16_bwd_instance(const recon_gcn_b16_bwd_args* args);
+
 /* L GraphConvolutions that share one adjacency (models/layers.py:57-63 applied L times, as the reference's stacks do), INFERENCE, in one
  * launch: the activations of a graph stay in LDS between the layers ("fused 3-hop, H resident in LDS").  Results are bit-equal
  * to L calls of recon_gcn_b16_fwd's fused form.  Layer 0: in_features -> hidden; layers 1 .. L-1: hidden -> hidden.  Shapes: n <= 32,
- * n % 4 == 0, hidden % 4 == 0, hidden <= 320; everything else answers RECON_ERR_UNSUPPORTED (the caller then runs layer by layer). */
+ * n % 4 == 0, hidden % 4 == 0, hidden <= 320, L <= 8, in_features <= 384 (L > 4: <= 352 — the activations of four graphs and the layers'
+ * bias rows share the LDS); everything else answers RECON_ERR_UNSUPPORTED (the caller then runs layer by layer). */
 typedef struct {
     int32_t B, n, in_features, hidden, L;
     const void* x; int64_t ldx;     /* [B*n, ldx] bf16, any even ldx >= in_features (the K tail is masked)                      */
@@ -679,11 +699,12 @@ typedef struct {
     const void* const* bias;            /* HOST array of L device pointers [hidden] bf16 (entries, or the array, may be NULL)                  */
     void* const* planes;                /* HOST array of L workspaces of recon_gcn_b16_planes_bytes(in_l, hidden) bytes: written by the        *
                                          * forward, read by the backward                                                                      */
-    void* const* acts; int64_t ldo;     /* HOST array of L buffers [B*n, ldo] bf16 (ldo % 8 == 0): the result of every layer, acts[L-1] = the  *
-                                         * stack's result; columns hidden .. ldo are written as zeros                                         */
+    void* const* acts; int64_t ldo;     /* HOST array of L buffers [B*n, ldo] bf16 (ldo % 8 == 0, ldo <= hidden rounded up to 32, else        *
+                                         * RECON_ERR_UNSUPPORTED): the result of every layer, acts[L-1] = the stack's result; columns         *
+                                         * hidden .. ldo are written as zeros                                                                 */
     /* ---- backward only ---- */
     const void* grad_out; int64_t ldg;  /* [B*n, ldg] bf16: gradient of acts[L-1]; any even ldg >= hidden, 4-byte aligned (read in place)      */
-    void* const* g_support;             /* HOST array of L workspaces [B*n, ldo] bf16                                                          */
+    void* const* g_support;             /* HOST array of L workspaces [B*n, ldo] bf16; columns hidden .. ldo are written as zeros              */
     float* partial;                     /* recon_gcn_b16_stack_bwd_partial_floats() floats                                                     */
     void* g_x; int64_t ldgx;            /* [B*n, ldgx] bf16 or NULL; ldgx % 4 == 0, >= in_features rounded up to 4, 8-byte aligned              */
     void* const* g_weight;              /* HOST array of L device pointers [in_l][hidden] bf16 (entries, or the array, may be NULL)            */

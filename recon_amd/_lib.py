@@ -272,6 +272,8 @@ SYMBOLS = [
     ("recon_gcn_b16_fwd", C.c_int, [C.POINTER(GcnB16Args), C.c_void_p]),
     ("recon_gcn_b16_bwd_partial_floats", C.c_size_t, [C.c_int32] * 4),
     ("recon_gcn_b16_bwd", C.c_int, [C.POINTER(GcnB16BwdArgs), C.c_void_p]),
+    ("recon_gcn_b16_fwd_instance", C.c_int32, [C.POINTER(GcnB16Args)]),
+    ("recon_gcn_b16_bwd_instance", C.c_int32, [C.POINTER(GcnB16BwdArgs)]),
     ("recon_gcn_b16_stack_fwd", C.c_int, [C.POINTER(GcnB16StackArgs), C.c_void_p]),
     ("recon_gcn_b16_transposed_planes", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     ("recon_gcn_b16_stack_train_fwd", C.c_int, [C.POINTER(GcnB16StackTrainArgs), C.c_void_p]),

@@ -12,7 +12,7 @@
 namespace recon {
 int32_t b16_kp(int32_t K);
 int b16_pad_planes(const void* src, int64_t ld, bool transposed, int32_t rows, int32_t K, void* dst, hipStream_t st);
-int gemm_b16(int32_t M, int32_t N, int32_t K, const void* A, int64_t lda, const void* Bp, void* C, int64_t ldc, bool out_bf16, hipStream_t st);
+int gemm_b16(int32_t M, int32_t N, int32_t K, const void* A, int64_t lda, const void* Bp, void* C, int64_t ldc, bool out_bf16, hipStream_t st, bool zero_pad);
 int b16_kmajor_splits(int32_t M, int32_t N, int32_t K);
 int b16_pad_planes_both(const void* src, int64_t ld, int32_t M, int32_t N, void* dst_t, void* dst_n, hipStream_t st);
 int gemm_b16_kmajor(int32_t M, int32_t N, int32_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* out, int64_t ldo, float* partial,
@@ -220,7 +220,6 @@ struct GcnFusedK {
     const uint16_t* adj; const uint16_t* wt; const uint16_t* bias;      // wt: W^T planes [O][Ip]
     uint16_t* out; int64_t ldo;
     int32_t B, n, I, Ip, O, nt;                                          // nt = ceil(ldo / 16) <= kFusedNT
-    int32_t adj_vec, bias_vec;                                           // 8-byte loads of adj rows / bias are possible
 };
 
 __device__ __forceinline__ int gf_lds_off(int row, int kq) { return row * 64 + (((kq + 2 * (row >> 3)) & 3) << 4); }
@@ -1113,12 +1112,33 @@ extern "C" size_t recon_gcn_b16_planes_bytes(int32_t in_features, int32_t out_fe
     return planes_part(out_features, in_features) + planes_part(in_features, out_features);
 }
 
+// What recon_gcn_b16_fwd launches: the launcher dispatches on this plan and recon_gcn_b16_fwd_instance() reports it
+enum GcnFwdPath { kGcnFwdNone = 0, kGcnFwdFused4 = 1, kGcnFwdFused2 = 2, kGcnFwdGemm = 3, kGcnFwdRagged = 4 };
+struct GcnFwdPlan { int rc; int path; };
+static GcnFwdPlan gcn_fwd_plan(const recon_gcn_b16_args* a) {
+    const int rc = check(a);
+    if (rc != RECON_OK) return {rc, kGcnFwdNone};
+    if (a->B == 0) return {RECON_OK, kGcnFwdNone};
+    if (a->node_ptr && (a->total_rows == 0 || a->total_rows > 0x7fffffffLL)) return {a->total_rows == 0 ? RECON_OK : RECON_ERR_UNSUPPORTED, kGcnFwdNone};
+    if (!a->support) {
+        // four column parts with 8-byte loads of adj rows and bias; the element-wise loads of odd shapes need the registers of the two-part form
+        const bool adj_vec = a->n % 4 == 0 && (reinterpret_cast<uintptr_t>(a->adj) & 7) == 0;
+        const bool bias_vec = !a->bias || (a->out_features % 4 == 0 && (reinterpret_cast<uintptr_t>(a->bias) & 7) == 0);
+        return {RECON_OK, adj_vec && bias_vec ? kGcnFwdFused4 : kGcnFwdFused2};
+    }
+    return {RECON_OK, a->node_ptr ? kGcnFwdRagged : kGcnFwdGemm};
+}
+
+extern "C" int32_t recon_gcn_b16_fwd_instance(const recon_gcn_b16_args* a) {
+    const GcnFwdPlan pl = gcn_fwd_plan(a);
+    return pl.rc != RECON_OK ? -1 : pl.path;
+}
+
 extern "C" int recon_gcn_b16_fwd(const recon_gcn_b16_args* a, recon_stream_t stream) {
-    int rc = check(a);
-    if (rc != RECON_OK) return rc;
-    if (a->B == 0) return RECON_OK;
+    const GcnFwdPlan pl = gcn_fwd_plan(a);
+    if (pl.rc != RECON_OK || pl.path == kGcnFwdNone) return pl.rc;
+    int rc = RECON_OK;
     hipStream_t st = as_stream(stream);
-    if (a->node_ptr && (a->total_rows == 0 || a->total_rows > 0x7fffffffLL)) return a->total_rows == 0 ? RECON_OK : RECON_ERR_UNSUPPORTED;
     const int32_t rows = a->node_ptr ? static_cast<int32_t>(a->total_rows) : a->B * a->n, I = a->in_features, O = a->out_features;
     char* wp = static_cast<char*>(a->w_planes);
     // W^T [O][kp(I)] for this product, W [I][kp(O)] for g_x in the backward (both zero padded along k)
@@ -1126,23 +1146,20 @@ extern "C" int recon_gcn_b16_fwd(const recon_gcn_b16_args* a, recon_stream_t str
         rc = b16_pad_planes_both(a->weight, O, I, O, wp, wp + planes_part(O, I), st);      // one launch for both layouts
         if (rc != RECON_OK) return rc;
     }
-    if (!a->support) {                                               // fused: one kernel, `support` stays in registers
+    if (pl.path == kGcnFwdFused4 || pl.path == kGcnFwdFused2) {      // fused: one kernel, `support` stays in registers
         GcnFusedK k;
         k.x = static_cast<const uint16_t*>(a->x); k.ldx = a->ldx; k.adj = static_cast<const uint16_t*>(a->adj);
         k.wt = reinterpret_cast<const uint16_t*>(wp); k.bias = static_cast<const uint16_t*>(a->bias);
         k.out = static_cast<uint16_t*>(a->out); k.ldo = a->ldo;
         k.B = a->B; k.n = a->n; k.I = I; k.Ip = b16_kp(I); k.O = O; k.nt = static_cast<int32_t>(ceil_div64(a->ldo, 16));
-        k.adj_vec = (a->n % 4 == 0 && (reinterpret_cast<uintptr_t>(a->adj) & 7) == 0) ? 1 : 0;
-        k.bias_vec = (!a->bias || (O % 4 == 0 && (reinterpret_cast<uintptr_t>(a->bias) & 7) == 0)) ? 1 : 0;
         const dim3 fg(static_cast<unsigned>(ceil_div64(a->B, 4)));
-        // four column parts with 8-byte loads; the element-wise loads of odd shapes need the registers of the two-part form
-        if (k.adj_vec && k.bias_vec) hipLaunchKernelGGL((k_gcn_b16_fused_fwd<4, true>), fg, dim3(1024), 0, st, k);
+        if (pl.path == kGcnFwdFused4) hipLaunchKernelGGL((k_gcn_b16_fused_fwd<4, true>), fg, dim3(1024), 0, st, k);
         else hipLaunchKernelGGL((k_gcn_b16_fused_fwd<2, false>), fg, dim3(512), 0, st, k);
         RECON_CHECK_LAUNCH();
         return RECON_OK;
     }
     // support = x @ W      (models/layers.py:58)
-    rc = gemm_b16(rows, O, I, a->x, a->ldx, wp, a->support, a->lds, true, st);
+    rc = gemm_b16(rows, O, I, a->x, a->ldx, wp, a->support, a->lds, true, st, true);      // pad columns O .. lds: zeros
     if (rc != RECON_OK) return rc;
     // out = relu(adj @ support + bias)     (:59-63)
     dim3 grid(static_cast<unsigned>(ceil_div64(a->ldo, 64)), static_cast<unsigned>(a->B), static_cast<unsigned>(ceil_div64(a->n, 32)));
@@ -1162,27 +1179,69 @@ extern "C" size_t recon_gcn_b16_bwd_partial_floats(int32_t B, int32_t n, int32_t
     return gcn_b16_gw_partial_floats(B, n, in_features, out_features) + static_cast<size_t>(B > 0 ? B : 0) * (out_features > 0 ? out_features : 0) + 1;
 }
 
-extern "C" int recon_gcn_b16_bwd(const recon_gcn_b16_bwd_args* b, recon_stream_t stream) {
-    if (!b) return RECON_ERR_INVALID;
+// What recon_gcn_b16_bwd launches: the launcher dispatches on this plan and recon_gcn_b16_bwd_instance() reports it.  Every refusal is
+// taken here, before the first launch.
+enum GcnBiasMode { kGcnBiasNone = 0, kGcnBiasRides = 1, kGcnBiasAlone = 2 };
+struct GcnBwdPlan { int rc; bool nothing, fused, g_adj; int bias_mode, splits; int32_t rows; };
+static GcnBwdPlan gcn_bwd_plan(const recon_gcn_b16_bwd_args* b) {
+    GcnBwdPlan pl{RECON_ERR_INVALID, true, false, false, kGcnBiasNone, 0, 0};
+    if (!b) return pl;
     const recon_gcn_b16_args* a = &b->fwd;
-    int rc = check(a);
-    if (rc != RECON_OK) return rc;
-    if (!b->grad_out || !b->g_support || !b->partial || !b->zeros || (b->ldg & 7) || (b->ldgx & 7)) return RECON_ERR_INVALID;
-    if (a->B == 0) return RECON_OK;
+    pl.rc = check(a);
+    if (pl.rc != RECON_OK) return pl;
+    pl.rc = RECON_ERR_INVALID;
+    if (!b->grad_out || !b->g_support || !b->partial || !b->zeros || (b->ldg & 7) || (b->ldgx & 7)) return pl;
+    const int32_t I = a->in_features, O = a->out_features, n = a->n;
+    const int64_t i8 = (I + 7) / 8 * 8, o8 = (O + 7) / 8 * 8;
+    if (a->B == 0) { pl.rc = RECON_OK; return pl; }
+    // g_support has rows of fwd.lds elements whether or not the forward kept `support`; d adj reads `support`
+    if ((a->lds & 7) || a->lds < o8 || b->ldg < o8 || (b->g_adj && !a->support)) return pl;
+    if (a->node_ptr && (a->total_rows == 0 || a->total_rows > 0x7fffffffLL)) { pl.rc = a->total_rows == 0 ? RECON_OK : RECON_ERR_UNSUPPORTED; return pl; }
+    const int32_t rows = a->node_ptr ? static_cast<int32_t>(a->total_rows) : a->B * a->n;
+    const bool fused_bwd_off = cfg_char(CFG_GCN_FUSED_BWD) == '0';
+    // (the fused kernel writes g_support in K steps of 32 columns: a row stride past kp(out) would leave pad columns unwritten)
+    pl.fused = !fused_bwd_off && !a->node_ptr && !b->g_adj && b->g_x && n <= 32 && a->lds <= kFusedNT * 16 && a->lds <= b16_kp(O) && i8 <= kFusedNT * 16 && b->ldgx >= i8 &&
+               (b->ldgx & 3) == 0 && (a->lds & 3) == 0 && (b->ldg & 7) == 0 && (a->ldo & 7) == 0 &&
+               ((reinterpret_cast<uintptr_t>(b->g_x) | reinterpret_cast<uintptr_t>(b->grad_out) | reinterpret_cast<uintptr_t>(a->out)) & 15) == 0 &&
+               static_cast<int64_t>(rows) * (a->lds > b->ldgx ? a->lds : b->ldgx) * 2 < 0x7fffffffLL &&
+               static_cast<int64_t>(rows) * (b->ldg > a->ldo ? b->ldg : a->ldo) * 2 < 0x7fffffffLL;
+    // g_x = g_support @ W^T on the GEMM: rows the GEMM can write
+    if (b->g_x && !pl.fused && (b->ldgx < i8 || (reinterpret_cast<uintptr_t>(b->g_x) & 15))) return pl;
+    if (reinterpret_cast<uintptr_t>(b->g_support) & 15) return pl;
+    if (b->g_weight) {
+        // the k-major GEMM reads x and g_support with 16-byte loads (gemm_b16_kmajor_multi refuses the same)
+        if (reinterpret_cast<uintptr_t>(b->zeros) & 15) return pl;
+        if ((a->ldx & 7) || a->ldx < i8) { pl.rc = RECON_ERR_UNSUPPORTED; return pl; }
+        pl.splits = b16_kmajor_splits(I, O, rows);
+    }
+    pl.rc = RECON_OK;
+    pl.nothing = false;
+    pl.g_adj = b->g_adj != nullptr;
+    pl.bias_mode = !b->g_bias ? kGcnBiasNone : (b->g_weight ? kGcnBiasRides : kGcnBiasAlone);
+    pl.rows = rows;
+    return pl;
+}
+
+extern "C" int32_t recon_gcn_b16_bwd_instance(const recon_gcn_b16_bwd_args* b) {
+    const GcnBwdPlan pl = gcn_bwd_plan(b);
+    if (pl.rc != RECON_OK) return -1;
+    if (pl.nothing) return 0;
+    return (pl.fused ? 1 : 2) * 100000 + (pl.g_adj ? 1 : 0) * 10000 + pl.bias_mode * 1000 + pl.splits;
+}
+
+extern "C" int recon_gcn_b16_bwd(const recon_gcn_b16_bwd_args* b, recon_stream_t stream) {
+    const GcnBwdPlan pl = gcn_bwd_plan(b);
+    if (pl.rc != RECON_OK || pl.nothing) return pl.rc;
+    const recon_gcn_b16_args* a = &b->fwd;
+    int rc = RECON_OK;
     hipStream_t st = as_stream(stream);
-    if (a->node_ptr && (a->total_rows == 0 || a->total_rows > 0x7fffffffLL)) return a->total_rows == 0 ? RECON_OK : RECON_ERR_UNSUPPORTED;
-    const int32_t rows = a->node_ptr ? static_cast<int32_t>(a->total_rows) : a->B * a->n, I = a->in_features, O = a->out_features, n = a->n;
+    const int32_t rows = pl.rows, I = a->in_features, O = a->out_features, n = a->n;
     const uint16_t* gout = static_cast<const uint16_t*>(b->grad_out);
     const uint16_t* fout = static_cast<const uint16_t*>(a->out);
     // [B][O] per-graph column sums of gpre, behind the split-K partials (ragged batch: the partials of a product over total_rows rows)
     float* colsum = b->partial + (a->node_ptr ? gcn_b16_gw_partial_floats(1, rows, I, O) : gcn_b16_gw_partial_floats(a->B, n, I, O));
-    const bool fused_bwd_off = cfg_char(CFG_GCN_FUSED_BWD) == '0';
     const int64_t i8f = (I + 7) / 8 * 8;
-    const bool fused_bwd = !fused_bwd_off && !a->node_ptr && !b->g_adj && b->g_x && n <= 32 && a->lds <= kFusedNT * 16 && i8f <= kFusedNT * 16 && b->ldgx >= i8f &&
-                           (b->ldgx & 3) == 0 && (a->lds & 3) == 0 && (b->ldg & 7) == 0 && (a->ldo & 7) == 0 &&
-                           ((reinterpret_cast<uintptr_t>(b->g_x) | reinterpret_cast<uintptr_t>(b->grad_out) | reinterpret_cast<uintptr_t>(a->out)) & 15) == 0 &&
-                           static_cast<int64_t>(rows) * (a->lds > b->ldgx ? a->lds : b->ldgx) * 2 < 0x7fffffffLL &&
-                           static_cast<int64_t>(rows) * (b->ldg > a->ldo ? b->ldg : a->ldo) * 2 < 0x7fffffffLL;
+    const bool fused_bwd = pl.fused;
     if (fused_bwd) {
         GcnFusedBwdK k;
         k.gout = gout; k.ldg = b->ldg; k.fout = fout; k.ldf = a->ldo; k.adj = static_cast<const uint16_t*>(a->adj);
@@ -1201,7 +1260,7 @@ extern "C" int recon_gcn_b16_bwd(const recon_gcn_b16_bwd_args* b, recon_stream_t
     hipLaunchKernelGGL((k_gcn_b16_aggregate<true, true, false>), grid, dim3(256), 0, st, static_cast<const uint16_t*>(a->adj), gout, b->ldg, fout, a->ldo,
                        nullptr, n, O, static_cast<uint16_t*>(b->g_support), a->lds, b->g_bias ? colsum : nullptr, a->node_ptr, a->adj_ptr);
     }
-    if (b->g_adj)
+    if (pl.g_adj)
         hipLaunchKernelGGL(k_gcn_b16_grad_adj, dim3(static_cast<unsigned>(ceil_div64(n * n, 256)), static_cast<unsigned>(a->B)), dim3(256), 0, st, gout,
                            b->ldg, fout, a->ldo, static_cast<const uint16_t*>(a->support), a->lds, n, O, static_cast<uint16_t*>(b->g_adj), a->node_ptr,
                            a->adj_ptr);
@@ -1210,21 +1269,28 @@ extern "C" int recon_gcn_b16_bwd(const recon_gcn_b16_bwd_args* b, recon_stream_t
     const B16ReduceJob bias_job{colsum, static_cast<uint16_t*>(b->g_bias), O, a->B, 1, O};
     // g_x = g_support @ W^T : B operand = W [I][kp(O)] (k = out contiguous)
     if (b->g_x && !fused_bwd) {
-        const int64_t i8 = (I + 7) / 8 * 8;
-        if (b->ldgx < i8 || (reinterpret_cast<uintptr_t>(b->g_x) & 15)) return RECON_ERR_INVALID;
-        rc = gemm_b16(rows, I, O, b->g_support, a->lds, static_cast<const char*>(a->w_planes) + planes_part(O, I), b->g_x, b->ldgx, true, st);
+        rc = gemm_b16(rows, I, O, b->g_support, a->lds, static_cast<const char*>(a->w_planes) + planes_part(O, I), b->g_x, b->ldgx, true, st, false);
         if (rc != RECON_OK) return rc;                                // (pad columns of g_x stay unwritten: every reader of a gradient stops at the feature count)
     }
     // g_W = x^T @ g_support   (k-major, split-K over the B*n rows, fixed-order second pass)
     if (b->g_weight) {
         rc = gemm_b16_kmajor(I, O, rows, a->x, a->ldx, b->g_support, a->lds, b->g_weight, O, b->partial, b->zeros, st, b->g_bias ? &bias_job : nullptr);
         if (rc != RECON_OK) return rc;
-    } else if (b->g_bias) {
+    } else if (pl.bias_mode == kGcnBiasAlone) {
         hipLaunchKernelGGL(k_gcn_b16_bias_reduce, dim3(static_cast<unsigned>(ceil_div64(O, 16))), dim3(1024), 0, st, colsum, a->B, O,
                            static_cast<uint16_t*>(b->g_bias));
         RECON_CHECK_LAUNCH();
     }
     return RECON_OK;
+}
+
+// LDS of k_gcn_b16_stack_fwd: W^T slabs | four activation images of nki K steps | scratch | the layers' bias rows.  The bias region holds
+// kMaxStack rows where that fits; an image of 12 K steps (in_features = 384) leaves room for the rows of the L <= 4 layers the kernel reads
+// (it indexes the region by layer and never past row L - 1).
+static size_t stack_fwd_lds(int64_t nki, int32_t L) {
+    const size_t base = 3ull * kFusedNT * 16 * 64 + 4ull * nki * 2048 + 1024;
+    const size_t full = base + static_cast<size_t>(kMaxStack) * kFusedNT * 32;
+    return full <= 160 * 1024 ? full : base + static_cast<size_t>(L) * kFusedNT * 32;
 }
 
 // four column parts per graph, one graph per wave: sixteen waves
@@ -1234,7 +1300,8 @@ static void launch_stack_fwd(const GcnStackK& k, size_t lds, hipStream_t st) {
 }
 
 extern "C" int recon_gcn_b16_stack_fwd(const recon_gcn_b16_stack_args* a, recon_stream_t stream) {
-    if (!a || a->B < 0 || a->n <= 0 || a->in_features <= 0 || a->hidden <= 0 || a->L < 1 || a->L > kMaxStack) return RECON_ERR_INVALID;
+    if (!a || a->B < 0 || a->n <= 0 || a->in_features <= 0 || a->hidden <= 0 || a->L < 1) return RECON_ERR_INVALID;
+    if (a->L > kMaxStack) return RECON_ERR_UNSUPPORTED;                 // more layers than one launch holds: layer by layer
     if (!a->x || !a->adj || !a->out || !a->w_planes) return RECON_ERR_INVALID;
     for (int l = 0; l < a->L; ++l) if (!a->w_planes[l]) return RECON_ERR_INVALID;
     const int64_t o8 = (a->hidden + 7) / 8 * 8;
@@ -1257,8 +1324,8 @@ extern "C" int recon_gcn_b16_stack_fwd(const recon_gcn_b16_stack_args* a, recon_
     k.out = static_cast<uint16_t*>(a->out); k.ldo = a->ldo;
     k.B = a->B; k.n = a->n; k.I0 = a->in_features; k.D = a->hidden; k.L = a->L; k.nt = static_cast<int32_t>(ceil_div64(a->ldo, 16));
     const int64_t nki = ((a->in_features > a->hidden ? a->in_features : a->hidden) + 31) / 32;
-    const size_t lds = 3ull * kFusedNT * 16 * 64 + static_cast<size_t>(kMaxStack) * kFusedNT * 32 + 4ull * nki * 2048 + 1024;
-    if (lds > 160 * 1024) return RECON_ERR_UNSUPPORTED;                 // in_features > 384: layer by layer
+    const size_t lds = stack_fwd_lds(nki, a->L);
+    if (lds > 160 * 1024) return RECON_ERR_UNSUPPORTED;                 // in_features > 384 (above four layers: > 352): layer by layer
     launch_stack_fwd(k, lds, as_stream(stream));
     RECON_CHECK_LAUNCH();
     return RECON_OK;
@@ -1266,7 +1333,8 @@ extern "C" int recon_gcn_b16_stack_fwd(const recon_gcn_b16_stack_args* a, recon_
 
 // ---- the stack with gradients: forward = the kernel above keeping every layer's result, backward = k_gcn_b16_stack_bwd + one k-major GEMM per layer
 static int stack_train_check(const recon_gcn_b16_stack_train_args* a, bool bwd) {
-    if (!a || a->B < 0 || a->n <= 0 || a->in_features <= 0 || a->hidden <= 0 || a->L < 1 || a->L > kMaxStack) return RECON_ERR_INVALID;
+    if (!a || a->B < 0 || a->n <= 0 || a->in_features <= 0 || a->hidden <= 0 || a->L < 1) return RECON_ERR_INVALID;
+    if (a->L > kMaxStack) return RECON_ERR_UNSUPPORTED;                 // more layers than one launch holds: layer by layer
     if (!a->x || !a->adj || !a->weight || !a->planes || !a->acts) return RECON_ERR_INVALID;
     const int64_t o8 = (a->hidden + 7) / 8 * 8, i8 = (a->in_features + 7) / 8 * 8;
     if ((a->ldo & 7) || a->ldo < o8) return RECON_ERR_INVALID;
@@ -1281,6 +1349,8 @@ static int stack_train_check(const recon_gcn_b16_stack_train_args* a, bool bwd) 
     }
     if (a->n > 32 || (a->n & 3) || a->ldo > kFusedNT * 16 || (a->hidden & 3) || a->B > 65535 * 4) return RECON_ERR_UNSUPPORTED;
     if (a->in_features > 16 * kFusedNT) return RECON_ERR_UNSUPPORTED;                 // g_x of layer 0 is a tile of at most 320 columns
+    // the backward writes g_support (rows of ldo elements) in K steps of 32 columns: a row stride past kp(hidden) would leave pad columns unwritten
+    if (a->ldo > b16_kp(a->hidden)) return RECON_ERR_UNSUPPORTED;
     if (static_cast<int64_t>(a->B) * a->n * a->ldx * 2 >= 0x7fffffffLL || static_cast<int64_t>(a->B) * a->n * a->ldo * 2 >= 0x7fffffffLL) return RECON_ERR_UNSUPPORTED;
     if ((al & 15) || (reinterpret_cast<uintptr_t>(a->adj) & 7)) return RECON_ERR_UNSUPPORTED;
     if (bwd) {
@@ -1327,7 +1397,7 @@ extern "C" int recon_gcn_b16_stack_train_fwd(const recon_gcn_b16_stack_train_arg
     k.xcopy = static_cast<uint16_t*>(a->x_rows); k.ldxc = a->ldxr;
     k.B = a->B; k.n = a->n; k.I0 = a->in_features; k.D = D; k.L = a->L; k.nt = static_cast<int32_t>(ceil_div64(a->ldo, 16));
     const int64_t nki = ((a->in_features > D ? a->in_features : D) + 31) / 32;
-    const size_t lds = 3ull * kFusedNT * 16 * 64 + static_cast<size_t>(kMaxStack) * kFusedNT * 32 + 4ull * nki * 2048 + 1024;
+    const size_t lds = stack_fwd_lds(nki, a->L);
     if (lds > 160 * 1024) return RECON_ERR_UNSUPPORTED;
     launch_stack_fwd(k, lds, st);
     RECON_CHECK_LAUNCH();

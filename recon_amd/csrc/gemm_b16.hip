@@ -20,6 +20,7 @@ struct B16Args {
     int64_t lda, ldb;              // elements; ldb = Kp
     void* C; int64_t ldc;          // bf16 or fp32 rows of ldc elements
     int32_t M, N, K;
+    int32_t zend;                  // bf16 results: columns N <= col < zend of every row are written as zeros (N: none)
 };
 
 __device__ __forceinline__ uint16_t f2bf(float v) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(v)); }
@@ -131,7 +132,10 @@ __global__ void __launch_bounds__(NT, 2) k_gemm_b16(const B16Args p) {
                     } else {
                         const float vv[4] = {v0, v1, v2, v3};
 #pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) if (col + jj < p.N) crow[col + jj] = f2bf(vv[jj]);
+                        for (int jj = 0; jj < 4; ++jj) {
+                            if (col + jj < p.N) crow[col + jj] = f2bf(vv[jj]);
+                            else if (col + jj < p.zend) crow[col + jj] = 0;
+                        }
                     }
                 } else {
                     float* crow = static_cast<float*>(p.C) + static_cast<int64_t>(row) * p.ldc;
@@ -147,6 +151,8 @@ __global__ void __launch_bounds__(NT, 2) k_gemm_b16(const B16Args p) {
             if (col < p.N) {
                 if constexpr (OUT_BF16) static_cast<uint16_t*>(p.C)[static_cast<int64_t>(row) * p.ldc + col] = f2bf(acc[i][12][r]);
                 else static_cast<float*>(p.C)[static_cast<int64_t>(row) * p.ldc + col] = acc[i][12][r];
+            } else if (OUT_BF16 && col < p.zend) {
+                static_cast<uint16_t*>(p.C)[static_cast<int64_t>(row) * p.ldc + col] = 0;
             }
         }
 }
@@ -461,8 +467,9 @@ int b16_pad_planes_both_multi(int32_t count, const void* const* src, const int32
     return RECON_OK;
 }
 
-// C[M,N] = A[M,K] . Bp[N,kp(K)]^T; A bf16 with lda % 8 == 0 and a 16-byte aligned base; C bf16 (out_bf16) or fp32
-int gemm_b16(int32_t M, int32_t N, int32_t K, const void* A, int64_t lda, const void* Bp, void* C, int64_t ldc, bool out_bf16, hipStream_t st) {
+// C[M,N] = A[M,K] . Bp[N,kp(K)]^T; A bf16 with lda % 8 == 0 and a 16-byte aligned base; C bf16 (out_bf16) or fp32.  zero_pad (bf16 results):
+// the pad columns N .. ldc of every row are written as zeros — by the last column tile where it reaches them, else by a strided memset
+int gemm_b16(int32_t M, int32_t N, int32_t K, const void* A, int64_t lda, const void* Bp, void* C, int64_t ldc, bool out_bf16, hipStream_t st, bool zero_pad) {
     if (M < 0 || N < 0 || K < 0) return RECON_ERR_INVALID;
     if (M == 0 || N == 0) return RECON_OK;
     if (!A || !Bp || !C) return RECON_ERR_INVALID;
@@ -471,6 +478,12 @@ int gemm_b16(int32_t M, int32_t N, int32_t K, const void* A, int64_t lda, const 
     a.A = static_cast<const uint16_t*>(A); a.Bp = static_cast<const uint16_t*>(Bp); a.lda = lda; a.ldb = b16_kp(K);
     if (static_cast<int64_t>(N) * a.ldb >= (1LL << 31)) return RECON_ERR_UNSUPPORTED;
     a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
+    const int64_t covered = ceil_div64(N, BN) * BN;                     // columns the grid's tiles span
+    zero_pad = zero_pad && out_bf16 && ldc > N;
+    a.zend = zero_pad ? static_cast<int32_t>(ldc < covered ? ldc : covered) : N;
+    if (zero_pad && ldc > covered &&
+        hipMemset2DAsync(static_cast<uint16_t*>(C) + covered, static_cast<size_t>(ldc) * 2, 0, static_cast<size_t>(ldc - covered) * 2, static_cast<size_t>(M), st) != hipSuccess)
+        return RECON_ERR_LAUNCH;
     const dim3 grid(static_cast<unsigned>(ceil_div64(N, BN)), static_cast<unsigned>(ceil_div64(M, BM)), 1);
     if (out_bf16) hipLaunchKernelGGL((k_gemm_b16<true>), grid, dim3(NT), 0, st, a);
     else hipLaunchKernelGGL((k_gemm_b16<false>), grid, dim3(NT), 0, st, a);
