@@ -7,17 +7,13 @@
 //                                                          added in group order by k_pt_reduce)
 // Everything is fp32 on v_mfma_f32_16x16x4_f32 (an exact fp32 fma chain), no atomics, every sum in an order the shape alone decides.
 //
-// One tile scheme for the three products: 64 x 64 outputs per workgroup, 32 of the reduction index per step, four waves as 2 x 2, each
-// 2 x 2 MFMA tiles (four independent accumulators per wave: the 40-cycle dependent latency of the 32-cycle instruction is covered).
-// Operands go global -> registers -> LDS, two register stages and two LDS buffers deep (pt_pipeline; one barrier per step), and lie k-major in LDS: row k holds the 64 m (or n)
-// values at k * 80 + (k / 4) * 8.  The row length 80 puts the two k rows a 32-lane group of a fragment read touches (k = 4 ks + g, g = 0, 1)
-// 16 banks apart: ds_read_b32 is conflict free; the skew of 8 per four rows does the same for the transposed stores of operands that
-// are contiguous along k in memory (a lane group writes rows 4 q + j, q = 0..3, for 8 consecutive m).  Operands contiguous along m / n
-// are stored as float4.  At the reference's widths (M = 3 600, K = 512, N1 = 256, L = 3) each product is 2.83 GFLOP against 20 MB of
-// traffic: matrix-pipe bound, so the tiles are sized for the number of workgroups (684 / 456 / 768 on 256 CUs), not for bytes.
+// One tile scheme for the three products, gemm_tile32.h's (the 64 x 64 x 32 tile, its k-major LDS layout, the register-staged pipeline
+// and the branch-free staging loads are explained there).  At the reference's widths (M = 3 600, K = 512, N1 = 256, L = 3) each product
+// is 2.83 GFLOP against 20 MB of traffic: matrix-pipe bound, so the tiles are sized for the number of workgroups (684 / 456 / 768 on
+// 256 CUs), not for bytes.
 //
 // The per-layer device pointers travel by value in the kernel arguments (L <= 8), as the segment descriptors of optim.hip do.
-#include "recon_common.h"
+#include "gemm_tile32.h"
 
 namespace recon {
 namespace {
@@ -25,15 +21,9 @@ namespace {
 constexpr int kPtMaxLayers = 8;          // L <= 8: three pointer lists of eight fit the kernel arguments
 constexpr int kPtMaxGroups = 8;          // WGRAD_MAX_ROW_GROUPS of recon_amd/transitions.py
 constexpr int kPtGroupRows = 32;         // a row group holds at least this many rows (one full step) unless M itself is smaller
-constexpr int NT = 256, BM = 64, BN = 64, BK = 32, LD = 80;
-constexpr int NP = BK / 16;              // float4 items per thread, operand and step
-constexpr int TILE = BK * LD + 8 * (BK / 4);     // + the skew of the last four rows, rounded
 // one step's operands in flight, as loaded: a (the forward's x; the backward's g_out), t (the backward's out), b, and which of them count:
 // bit 4 q + j for element j of a[q], bit 16 + q for b[q]
 struct PtStage { float4 a[NP], t[NP], b[NP]; uint32_t ok; };
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ int lds_at(int k, int c) { return k * LD + (k >> 2) * 8 + c; }
 
 __device__ __forceinline__ float pt_act(float v, int act) {
     if (act == RECON_ACT_RELU) return v > 0.f ? v : 0.f;
@@ -46,89 +36,8 @@ __device__ __forceinline__ float pt_dpre(float g, float t, int act) {
     if (act == RECON_ACT_TANH) return g * (1.f - t * t);
     return g;
 }
-// Staging loads are branch free: a load outside the operand reads a valid address instead (the operand's first elements), so that a
-// step's loads are issued back to back (behind a branch each, they waited for one another).  What was loaded is only looked at when the
-// stage is stored to LDS, a step later (each kernel's `finish`): zeros for what lies outside, g act'(T) for the backward's A operand.
-__device__ __forceinline__ float4 pt_keep(uint32_t m, float4 v) {
-    return make_float4((m & 1u) ? v.x : 0.f, (m & 2u) ? v.y : 0.f, (m & 4u) ? v.z : 0.f, (m & 8u) ? v.w : 0.f);
-}
 __device__ __forceinline__ float4 pt_dpre4(float4 g, float4 t, int act) {
     return make_float4(pt_dpre(g.x, t.x, act), pt_dpre(g.y, t.y, act), pt_dpre(g.z, t.z, act), pt_dpre(g.w, t.w, act));
-}
-
-// one staged step: BK / 4 k groups x (2 + 2 fragment reads, 4 MFMAs).  A[l & 15][k = l >> 4], B[k = l >> 4][l & 15].
-// ONES: a fifth and sixth MFMA against a B fragment whose column 0 is 1 — the column of ones behind x, for the wave that owns d_b.
-template <bool ONES>
-__device__ __forceinline__ void pt_mma(const float* __restrict__ As, const float* __restrict__ Bs, f32x4 (&acc)[2][2], f32x4 (&accb)[2], int mb, int nb,
-                                       int li, int g) {
-    const float one = li == 0 ? 1.f : 0.f;
-#pragma unroll
-    for (int ks = 0; ks < BK / 4; ++ks) {
-        const int kk = 4 * ks + g;
-        const float* ar = As + lds_at(kk, mb + li);
-        const float* br = Bs + lds_at(kk, nb + li);
-        const float a0 = ar[0], a1 = ar[16], b0 = br[0], b1 = br[16];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-        if constexpr (ONES) {
-            accb[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, one, accb[0], 0, 0, 0);
-            accb[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, one, accb[1], 0, 0, 0);
-        }
-    }
-}
-
-// an operand contiguous along k in memory: thread (row t / 4, k quad t % 4) holds 4 k of one row; transposed into the k-major tile
-__device__ __forceinline__ void pt_store_kminor(float* T, int t, const float4 (&r)[NP]) {
-    const int row = t >> 2;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        const int k = 16 * q + (t & 3) * 4;
-        T[lds_at(k, row)] = r[q].x; T[lds_at(k + 1, row)] = r[q].y; T[lds_at(k + 2, row)] = r[q].z; T[lds_at(k + 3, row)] = r[q].w;
-    }
-}
-// an operand contiguous along m / n: thread (k row t / 16, quad t % 16) holds 4 m of one k
-__device__ __forceinline__ void pt_store_kmajor(float* T, int t, const float4 (&r)[NP]) {
-#pragma unroll
-    for (int q = 0; q < NP; ++q) *reinterpret_cast<float4*>(T + lds_at(16 * q + (t >> 4), (t & 15) * 4)) = r[q];
-}
-
-#define PT_ZERO_ACC()                                                   \
-    f32x4 acc[2][2], accb[2];                                           \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                     \
-        accb[i] = f32x4{0.f, 0.f, 0.f, 0.f};                            \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; \
-    }
-
-// The reduction loop of the three products.  load(stage, i) issues the global loads of step i into a register stage, mma(A, B) runs a
-// staged step.  TWO stages are in flight: while step i is multiplied out of one LDS buffer, step i + 1 waits in registers for its store
-// into the other buffer and the loads of step i + 2 are on their way.  The loads in the loop are unconditional (past the end they read a
-// valid address and the stage is never stored): behind a condition the compiler cannot count what is in flight and every wait in the loop
-// becomes vmcnt(0).  With guarded loads and one stage the forward took 93 us at the reference's widths, 40 us this way.
-template <bool A_KMINOR, bool B_KMINOR, class Load, class Finish, class Mma>
-__device__ __forceinline__ void pt_pipeline(float (*As)[TILE], float (*Bs)[TILE], int t, int64_t n, Load load, Finish finish, Mma mma) {
-    auto store = [&](int buf, PtStage& s) {
-        finish(s);
-        if constexpr (A_KMINOR) pt_store_kminor(As[buf], t, s.a); else pt_store_kmajor(As[buf], t, s.a);
-        if constexpr (B_KMINOR) pt_store_kminor(Bs[buf], t, s.b); else pt_store_kmajor(Bs[buf], t, s.b);
-    };
-    PtStage s0, s1;
-    load(s0, 0);
-    load(s1, 1);                                                         // (a step past the end loads from a valid address and is never stored)
-    store(0, s0);
-    __syncthreads();
-    for (int64_t i = 0; i < n; i += 2) {
-        load(s0, i + 2);                                                 // unconditional, so that the counted waits know what is in flight
-        mma(As[0], Bs[0]);
-        if (i + 1 < n) store(1, s1);
-        __syncthreads();
-        if (i + 1 >= n) break;
-        load(s1, i + 3);
-        mma(As[1], Bs[1]);
-        if (i + 2 < n) store(0, s0);
-        __syncthreads();
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------ forward
@@ -142,8 +51,8 @@ struct PtFwdArgs {
 __global__ void __launch_bounds__(NT) k_pt_fwd(const PtFwdArgs p) {
     __shared__ __attribute__((aligned(16))) float As[2][TILE];
     __shared__ __attribute__((aligned(16))) float Bs[2][TILE];
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6, li = lane & 15, g = lane >> 4;
-    const int mb = (wid >> 1) * 32, nb = (wid & 1) * 32;
+    const Lane ln = tile_lane();
+    const int t = ln.t, li = ln.li, g = ln.g, mb = ln.mb, nb = ln.nb;
     const int64_t m0 = static_cast<int64_t>(blockIdx.x) * BM;
     const int n0 = blockIdx.y * BN, ncol = p.L * p.N1;
     const int lr = t >> 2, kq = (t & 3) * 4;
@@ -155,7 +64,7 @@ __global__ void __launch_bounds__(NT) k_pt_fwd(const PtFwdArgs p) {
     const int bl = b_ok ? bc / p.N1 : 0, bn = b_ok ? bc - bl * p.N1 : 0;
     const float* bp = p.w[bl] + static_cast<int64_t>(bn) * p.K + kq;
     const float* w0 = p.w[0];
-    PT_ZERO_ACC();
+    TILE32_ZERO_ACC();
     auto load = [&](PtStage& s, int64_t step) {
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
@@ -170,12 +79,12 @@ __global__ void __launch_bounds__(NT) k_pt_fwd(const PtFwdArgs p) {
     auto finish = [&](PtStage& s) {
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-            s.a[q] = pt_keep(s.ok >> (4 * q), s.a[q]);
-            s.b[q] = pt_keep((s.ok >> (16 + q)) & 1u ? 15u : 0u, s.b[q]);
+            s.a[q] = keep4(s.ok >> (4 * q), s.a[q]);
+            s.b[q] = keep4((s.ok >> (16 + q)) & 1u ? 15u : 0u, s.b[q]);
         }
     };
-    pt_pipeline<true, true>(As, Bs, t, (p.K + BK - 1) / BK, load, finish,
-                            [&](const float* A, const float* B) { pt_mma<false>(A, B, acc, accb, mb, nb, li, g); });
+    tile_pipeline<PtStage, true, true>(As, Bs, t, (p.K + BK - 1) / BK, NoInit{}, load, finish,
+                                       [&](const float* A, const float* B) { tile_mma<false>(A, B, acc, accb, mb, nb, li, g); });
     // C layout: column = lane & 15, row = 4 (lane >> 4) + r
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -208,8 +117,8 @@ template <bool V4>
 __global__ void __launch_bounds__(NT) k_pt_dx(const PtDxArgs p) {
     __shared__ __attribute__((aligned(16))) float As[2][TILE];
     __shared__ __attribute__((aligned(16))) float Bs[2][TILE];
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6, li = lane & 15, g = lane >> 4;
-    const int mb = (wid >> 1) * 32, nb = (wid & 1) * 32;
+    const Lane ln = tile_lane();
+    const int t = ln.t, li = ln.li, g = ln.g, mb = ln.mb, nb = ln.nb;
     const int64_t m0 = static_cast<int64_t>(blockIdx.x) * BM;
     const int c0 = blockIdx.y * BN, R = p.L * p.N1;
     const int lr = t >> 2, rq = (t & 3) * 4;                             // A: row, quad of r
@@ -219,7 +128,7 @@ __global__ void __launch_bounds__(NT) k_pt_dx(const PtDxArgs p) {
     const int kr = t >> 4, bcol = c0 + (t & 15) * 4;                     // B: r row, quad of output columns
     const bool b_ok = bcol < p.K;                                        // K % 4 == 0
     const int bcs = b_ok ? bcol : 0;
-    PT_ZERO_ACC();
+    TILE32_ZERO_ACC();
     auto load = [&](PtStage& s, int64_t step) {
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
@@ -251,12 +160,12 @@ __global__ void __launch_bounds__(NT) k_pt_dx(const PtDxArgs p) {
     auto finish = [&](PtStage& s) {
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-            s.a[q] = pt_keep(s.ok >> (4 * q), pt_dpre4(s.a[q], s.t[q], p.act));
-            s.b[q] = pt_keep((s.ok >> (16 + q)) & 1u ? 15u : 0u, s.b[q]);
+            s.a[q] = keep4(s.ok >> (4 * q), pt_dpre4(s.a[q], s.t[q], p.act));
+            s.b[q] = keep4((s.ok >> (16 + q)) & 1u ? 15u : 0u, s.b[q]);
         }
     };
-    pt_pipeline<true, false>(As, Bs, t, (R + BK - 1) / BK, load, finish,
-                             [&](const float* A, const float* B) { pt_mma<false>(A, B, acc, accb, mb, nb, li, g); });
+    tile_pipeline<PtStage, true, false>(As, Bs, t, (R + BK - 1) / BK, NoInit{}, load, finish,
+                                        [&](const float* A, const float* B) { tile_mma<false>(A, B, acc, accb, mb, nb, li, g); });
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int col = c0 + nb + 16 * j + li;
@@ -286,8 +195,8 @@ template <bool V4>
 __global__ void __launch_bounds__(NT) k_pt_wgrad(const PtWgArgs p) {
     __shared__ __attribute__((aligned(16))) float As[2][TILE];
     __shared__ __attribute__((aligned(16))) float Bs[2][TILE];
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6, li = lane & 15, g = lane >> 4;
-    const int mb = (wid >> 1) * 32, nb = (wid & 1) * 32;
+    const Lane ln = tile_lane();
+    const int t = ln.t, li = ln.li, g = ln.g, mb = ln.mb, nb = ln.nb;
     const int lc = blockIdx.y / p.ntiles, n0 = (blockIdx.y - lc * p.ntiles) * BM, c0 = blockIdx.x * BN;
     const int64_t m_begin = static_cast<int64_t>(blockIdx.z) * p.per, m_end = min(p.M, m_begin + p.per);
     const bool ones = blockIdx.x == 0 && nb == 0;                        // wave-uniform
@@ -297,7 +206,7 @@ __global__ void __launch_bounds__(NT) k_pt_wgrad(const PtWgArgs p) {
     const int an = n0 + q4, bc = c0 + q4;
     const bool b_ok = bc < p.K;
     const int bcc = b_ok ? bc : 0;
-    PT_ZERO_ACC();
+    TILE32_ZERO_ACC();
     auto load = [&](PtStage& s, int64_t step) {
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
@@ -329,13 +238,13 @@ __global__ void __launch_bounds__(NT) k_pt_wgrad(const PtWgArgs p) {
     auto finish = [&](PtStage& s) {
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-            s.a[q] = pt_keep(s.ok >> (4 * q), pt_dpre4(s.a[q], s.t[q], p.act));
-            s.b[q] = pt_keep((s.ok >> (16 + q)) & 1u ? 15u : 0u, s.b[q]);
+            s.a[q] = keep4(s.ok >> (4 * q), pt_dpre4(s.a[q], s.t[q], p.act));
+            s.b[q] = keep4((s.ok >> (16 + q)) & 1u ? 15u : 0u, s.b[q]);
         }
     };
-    pt_pipeline<false, false>(As, Bs, t, (m_end - m_begin + BK - 1) / BK, load, finish, [&](const float* A, const float* B) {
-        if (ones) pt_mma<true>(A, B, acc, accb, mb, nb, li, g);
-        else pt_mma<false>(A, B, acc, accb, mb, nb, li, g);
+    tile_pipeline<PtStage, false, false>(As, Bs, t, (m_end - m_begin + BK - 1) / BK, NoInit{}, load, finish, [&](const float* A, const float* B) {
+        if (ones) tile_mma<true>(A, B, acc, accb, mb, nb, li, g);
+        else tile_mma<false>(A, B, acc, accb, mb, nb, li, g);
     });
     const int64_t ldw = p.K + 1;
     float* slab = p.slab + (static_cast<int64_t>(blockIdx.z) * p.L + lc) * p.N1 * ldw;
@@ -378,15 +287,26 @@ __global__ void __launch_bounds__(256) k_pt_reduce(const PtRedArgs p) {
     *dst = s;
 }
 
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
-int64_t pt_groups(int64_t M) {                                           // a function of M alone
-    const int64_t g = ceil_div64(M, kPtGroupRows);
-    return g < 1 ? 1 : (g > kPtMaxGroups ? kPtMaxGroups : g);
-}
+int64_t pt_groups(int64_t M) { return row_groups(M, kPtGroupRows, kPtMaxGroups); }
 
 bool pt_shape_ok(int64_t M, int32_t K, int32_t N1, int32_t L) {
     return M >= 0 && M <= (int64_t{1} << 24) && K >= 4 && K <= 1024 && (K & 3) == 0 && N1 >= 1 && N1 <= 1024 && L >= 1 && L <= kPtMaxLayers;
+}
+
+// The argument checks the two entries share, in the order of their answers: signs and act (INVALID), the shape (UNSUPPORTED), then, for
+// M > 0 alone, the pointers (INVALID) and the alignment (UNSUPPORTED).  rest: the entry's further pointer arguments are there.
+int pt_check(const float* x, int64_t ld_x, const float* const* w, const float* const* out, bool rest, int64_t M, int32_t K, int32_t N1, int32_t L,
+             int32_t act) {
+    if (M < 0 || K < 0 || N1 < 0 || L < 0 || act < RECON_ACT_LINEAR || act > RECON_ACT_TANH) return RECON_ERR_INVALID;
+    if (!pt_shape_ok(M, K, N1, L)) return RECON_ERR_UNSUPPORTED;
+    if (M == 0) return RECON_OK;
+    if (!x || !w || !out || !rest || ld_x < K) return RECON_ERR_INVALID;
+    for (int l = 0; l < L; ++l)
+        if (!w[l] || !out[l]) return RECON_ERR_INVALID;
+    if ((ld_x & 3) || !aligned16(x)) return RECON_ERR_UNSUPPORTED;
+    for (int l = 0; l < L; ++l)
+        if (!aligned16(w[l])) return RECON_ERR_UNSUPPORTED;
+    return RECON_OK;
 }
 
 }  // namespace
@@ -403,15 +323,8 @@ extern "C" size_t recon_pair_transitions_workspace_bytes(int64_t M, int32_t K, i
 extern "C" int recon_pair_transitions_fwd(const float* x, int64_t ld_x, const float* const* w, const float* const* b, int64_t M, int32_t K, int32_t N1,
                                           int32_t L, int32_t act, float* const* out, recon_stream_t stream) {
     using namespace recon;
-    if (M < 0 || K < 0 || N1 < 0 || L < 0 || act < RECON_ACT_LINEAR || act > RECON_ACT_TANH) return RECON_ERR_INVALID;
-    if (!pt_shape_ok(M, K, N1, L)) return RECON_ERR_UNSUPPORTED;
-    if (M == 0) return RECON_OK;
-    if (!x || !w || !out || ld_x < K) return RECON_ERR_INVALID;
-    for (int l = 0; l < L; ++l)
-        if (!w[l] || !out[l]) return RECON_ERR_INVALID;
-    if ((ld_x & 3) || !aligned16(x)) return RECON_ERR_UNSUPPORTED;
-    for (int l = 0; l < L; ++l)
-        if (!aligned16(w[l])) return RECON_ERR_UNSUPPORTED;
+    const int rc = pt_check(x, ld_x, w, out, true, M, K, N1, L, act);
+    if (rc != RECON_OK || M == 0) return rc;
     PtFwdArgs a{};
     a.x = x; a.ld_x = ld_x; a.M = M; a.K = K; a.N1 = N1; a.L = L; a.act = act;
     for (int l = 0; l < L; ++l) { a.w[l] = w[l]; a.b[l] = b ? b[l] : nullptr; a.out[l] = out[l]; }
@@ -425,8 +338,8 @@ extern "C" int recon_pair_transitions_bwd(const float* x, int64_t ld_x, const fl
                                           int64_t M, int32_t K, int32_t N1, int32_t L, int32_t act, float* g_x, float* const* g_w,
                                           float* const* g_b, void* workspace, size_t workspace_bytes, recon_stream_t stream) {
     using namespace recon;
-    if (M < 0 || K < 0 || N1 < 0 || L < 0 || act < RECON_ACT_LINEAR || act > RECON_ACT_TANH) return RECON_ERR_INVALID;
-    if (!pt_shape_ok(M, K, N1, L)) return RECON_ERR_UNSUPPORTED;
+    const int rc = pt_check(x, ld_x, w, out, g_out != nullptr, M, K, N1, L, act);
+    if (rc != RECON_OK) return rc;
     hipStream_t st = as_stream(stream);
     bool params = false;
     for (int l = 0; l < L; ++l) params = params || (g_w && g_w[l]) || (g_b && g_b[l]);
@@ -437,12 +350,6 @@ extern "C" int recon_pair_transitions_bwd(const float* x, int64_t ld_x, const fl
         }
         return RECON_OK;
     }
-    if (!x || !w || !out || !g_out || ld_x < K) return RECON_ERR_INVALID;
-    for (int l = 0; l < L; ++l)
-        if (!w[l] || !out[l]) return RECON_ERR_INVALID;
-    if ((ld_x & 3) || !aligned16(x)) return RECON_ERR_UNSUPPORTED;
-    for (int l = 0; l < L; ++l)
-        if (!aligned16(w[l])) return RECON_ERR_UNSUPPORTED;
     if (params) {
         if (!workspace || !aligned16(workspace)) return RECON_ERR_INVALID;
         if (workspace_bytes < recon_pair_transitions_workspace_bytes(M, K, N1, L, 1)) return RECON_ERR_WORKSPACE;

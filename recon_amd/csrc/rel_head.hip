@@ -10,15 +10,14 @@
 // Everything is fp32 on v_mfma_f32_16x16x4_f32 (an exact fp32 fma chain), no atomics, every sum in an order the shapes, Mnz and the
 // positions' row groups decide.
 //
-// The tile scheme, the LDS layout, the register-staged pipeline and the flag-then-zero staging are those of pair_trans.hip (DESIGN.md
-// section 22), carried here as a copy: pair_trans.hip's stage also holds the saved output for act', its masks assume whole quads, and its
-// six kernels keep their register counts only if nothing in them moves.  What differs: widths, strides and bases
-// need no alignment (a block or a weight column range whose base, stride and width are 4-aligned is read as float4, any other element by
-// element, each element clamped to a valid address on its own; in the two backward products the choice is per block, in the forward,
-// where the block changes inside the loop, per operand and call), and a step or a column tile never straddles two blocks, so the block,
-// its base and its stride are uniform per step / per workgroup: no per-lane lookup.  Block pointers, strides and widths travel by value
-// in the kernel arguments.
-#include "recon_common.h"
+// The tile scheme, the LDS layout, the register-staged pipeline and the flag-then-zero staging are gemm_tile32.h's, shared with
+// pair_trans.hip (DESIGN.md sections 22 and 23).  What differs from that op: the stage (no saved output, one flag per element of both
+// operands, the prefetched positions); widths, strides and bases need no alignment (a block or a weight column range whose base, stride
+// and width are 4-aligned is read as float4, any other element by element, each element clamped to a valid address on its own; in the
+// two backward products the choice is per block, in the forward, where the block changes inside the loop, per operand and call); and a
+// step or a column tile never straddles two blocks, so the block, its base and its stride are uniform per step / per workgroup: no
+// per-lane lookup.  Block pointers, strides and widths travel by value in the kernel arguments.
+#include "gemm_tile32.h"
 
 #include <type_traits>
 
@@ -30,13 +29,9 @@ constexpr int kRhMaxBlocks = 5;          // + the scattered one
 constexpr int kRhMaxGroups = 8;          // WGRAD_MAX_ROW_GROUPS of recon_amd/relation_head.py
 constexpr int kRhGroupRows = 32;         // a row group holds at least this many rows (one full step) unless M itself is smaller
 constexpr int kRhMaxWidth = 2048, kRhMaxOut = 1024;
-constexpr int NT = 256, BM = 64, BN = 64, BK = 32, LD = 80;
-constexpr int NP = BK / 16;              // float4 items per thread, operand and step
-constexpr int TILE = BK * LD + 8 * (BK / 4);
 // one step's operands in flight, as loaded, and which of their elements count: bit 4 q + j for element j of a[q], bit 8 + 4 q + j for b[q]
 // pi: the positions of the step's rows, fetched two steps ahead of their use (the weight gradient's scattered block alone)
 struct RhStage { float4 a[NP], b[NP]; int64_t pi[NP]; uint32_t ok; };
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // The column blocks of the concatenated operand, as one kernel walks them.  `end` is the running total of the kernel's units per block:
 // reduction steps of 32 (forward), column tiles of 64 (the two backward products).  sb: the scattered block's place in the list, or -1.
@@ -47,8 +42,6 @@ struct RhCols {
     uint32_t vec, wvec;                  // bit b: block b is read as float4; the weight's columns of block b are
     const int64_t* pos; int64_t Mnz;
 };
-
-__device__ __forceinline__ int lds_at(int k, int c) { return k * LD + (k >> 2) * 8 + c; }
 
 // the block unit u (a step, a column tile) belongs to; uniform where u is.  A unit past the end belongs to the last block.
 __device__ __forceinline__ int rh_block_of(const RhCols& c, int u) {
@@ -72,7 +65,7 @@ __device__ __forceinline__ int64_t rh_lower(const int64_t* __restrict__ pos, int
 // Staging loads never leave the operand: elements k .. k + 3 of a row of K, an element outside read from the row's first instead, and
 // m says which were inside.  VEC: the row start is 16-byte aligned and K % 4 == 0, so a quad is inside or outside as a whole.  Which of
 // the two forms a reduction loop runs is decided outside the loop (a kernel's template argument, or a workgroup-uniform branch around
-// the whole loop): a branch around a load inside it would cost the counted waits pair_trans.hip's pipeline lives on.
+// the whole loop): a branch around a load inside it would cost the counted waits gemm_tile32.h's pipeline lives on.
 template <bool VEC>
 __device__ __forceinline__ float4 rh_ld4(const float* __restrict__ row, int k, int K, uint32_t& m) {
     if constexpr (VEC) {
@@ -90,95 +83,19 @@ __device__ __forceinline__ float4 rh_ld4(const float* __restrict__ row, int k, i
     }
     return make_float4(v[0], v[1], v[2], v[3]);
 }
-__device__ __forceinline__ float4 rh_keep(uint32_t m, float4 v) {
-    return make_float4((m & 1u) ? v.x : 0.f, (m & 2u) ? v.y : 0.f, (m & 4u) ? v.z : 0.f, (m & 8u) ? v.w : 0.f);
-}
-__device__ __forceinline__ void rh_finish(RhStage& s) {
+// what a stage stores: zeros where a flag is clear (tile_pipeline's `finish`, the same for the three products)
+struct RhFinish {
+    __device__ __forceinline__ void operator()(RhStage& s) const {
 #pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        s.a[q] = rh_keep(s.ok >> (4 * q), s.a[q]);
-        s.b[q] = rh_keep(s.ok >> (8 + 4 * q), s.b[q]);
-    }
-}
-
-// one staged step: BK / 4 k groups x (2 + 2 fragment reads, 4 MFMAs).  A[l & 15][k = l >> 4], B[k = l >> 4][l & 15].
-// ONES: a fifth and sixth MFMA against a B fragment whose column 0 is 1 — the column of ones behind the blocks, for the wave that owns d_b.
-template <bool ONES>
-__device__ __forceinline__ void rh_mma(const float* __restrict__ As, const float* __restrict__ Bs, f32x4 (&acc)[2][2], f32x4 (&accb)[2], int mb, int nb,
-                                       int li, int g) {
-    const float one = li == 0 ? 1.f : 0.f;
-#pragma unroll
-    for (int ks = 0; ks < BK / 4; ++ks) {
-        const int kk = 4 * ks + g;
-        const float* ar = As + lds_at(kk, mb + li);
-        const float* br = Bs + lds_at(kk, nb + li);
-        const float a0 = ar[0], a1 = ar[16], b0 = br[0], b1 = br[16];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-        if constexpr (ONES) {
-            accb[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, one, accb[0], 0, 0, 0);
-            accb[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, one, accb[1], 0, 0, 0);
+        for (int q = 0; q < NP; ++q) {
+            s.a[q] = keep4(s.ok >> (4 * q), s.a[q]);
+            s.b[q] = keep4(s.ok >> (8 + 4 * q), s.b[q]);
         }
     }
-}
+};
 
-// an operand contiguous along k in memory: thread (row t / 4, k quad t % 4) holds 4 k of one row; transposed into the k-major tile
-__device__ __forceinline__ void rh_store_kminor(float* T, int t, const float4 (&r)[NP]) {
-    const int row = t >> 2;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        const int k = 16 * q + (t & 3) * 4;
-        T[lds_at(k, row)] = r[q].x; T[lds_at(k + 1, row)] = r[q].y; T[lds_at(k + 2, row)] = r[q].z; T[lds_at(k + 3, row)] = r[q].w;
-    }
-}
-// an operand contiguous along m / n: thread (k row t / 16, quad t % 16) holds 4 m of one k
-__device__ __forceinline__ void rh_store_kmajor(float* T, int t, const float4 (&r)[NP]) {
-#pragma unroll
-    for (int q = 0; q < NP; ++q) *reinterpret_cast<float4*>(T + lds_at(16 * q + (t >> 4), (t & 15) * 4)) = r[q];
-}
-
-struct RhNoInit { __device__ __forceinline__ void operator()(RhStage&, int64_t) const {} };
 using rh_yes = std::true_type;
 using rh_no = std::false_type;
-
-#define RH_ZERO_ACC()                                                   \
-    f32x4 acc[2][2], accb[2];                                           \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                     \
-        accb[i] = f32x4{0.f, 0.f, 0.f, 0.f};                            \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; \
-    }
-
-// The reduction loop of the three products, as pt_pipeline of pair_trans.hip: two register stages and two LDS buffers, one barrier per
-// step, unconditional loads (a step past the end loads from valid addresses and is never stored).
-// init(stage, i) prepares the stages of steps 0 and 1 before their loads (the weight gradient's position prefetch).
-template <bool A_KMINOR, bool B_KMINOR, class Init, class Load, class Mma>
-__device__ __forceinline__ void rh_pipeline(float (*As)[TILE], float (*Bs)[TILE], int t, int64_t n, Init init, Load load, Mma mma) {
-    auto store = [&](int buf, RhStage& s) {
-        rh_finish(s);
-        if constexpr (A_KMINOR) rh_store_kminor(As[buf], t, s.a); else rh_store_kmajor(As[buf], t, s.a);
-        if constexpr (B_KMINOR) rh_store_kminor(Bs[buf], t, s.b); else rh_store_kmajor(Bs[buf], t, s.b);
-    };
-    RhStage s0, s1;
-    init(s0, 0);
-    init(s1, 1);
-    load(s0, 0);
-    load(s1, 1);
-    store(0, s0);
-    __syncthreads();
-    for (int64_t i = 0; i < n; i += 2) {
-        load(s0, i + 2);
-        mma(As[0], Bs[0]);
-        if (i + 1 < n) store(1, s1);
-        __syncthreads();
-        if (i + 1 >= n) break;
-        load(s1, i + 3);
-        mma(As[1], Bs[1]);
-        if (i + 2 < n) store(0, s0);
-        __syncthreads();
-    }
-}
 
 // ------------------------------------------------------------------------------------------------------------------ forward
 struct RhFwdArgs {
@@ -195,8 +112,8 @@ __global__ void __launch_bounds__(NT) k_rh_fwd(const RhFwdArgs p) {
     __shared__ __attribute__((aligned(16))) float As[2][TILE];
     __shared__ __attribute__((aligned(16))) float Bs[2][TILE];
     const RhCols& c = p.c;
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6, li = lane & 15, g = lane >> 4;
-    const int mb = (wid >> 1) * 32, nb = (wid & 1) * 32;
+    const Lane ln = tile_lane();
+    const int t = ln.t, li = ln.li, g = ln.g, mb = ln.mb, nb = ln.nb;
     const int64_t m0 = static_cast<int64_t>(blockIdx.x) * BM;
     const int n0 = blockIdx.y * BN;
     const int lr = t >> 2, kq = (t & 3) * 4;
@@ -214,7 +131,7 @@ __global__ void __launch_bounds__(NT) k_rh_fwd(const RhFwdArgs p) {
     const int bc = n0 + lr;
     const bool b_ok = bc < p.N;
     const float* wrow = p.w + static_cast<int64_t>(b_ok ? bc : 0) * p.Kt;
-    RH_ZERO_ACC();
+    TILE32_ZERO_ACC();
     auto load = [&](RhStage& s, int64_t step) {
         const int st = static_cast<int>(step), b = rh_block_of(c, st);
         const int kbase = (st - (b ? c.end[b - 1] : 0)) * BK, Kb = c.K[b];
@@ -231,7 +148,7 @@ __global__ void __launch_bounds__(NT) k_rh_fwd(const RhFwdArgs p) {
             s.ok |= (r_ok ? ma << (4 * q) : 0u) | (b_ok ? mw << (8 + 4 * q) : 0u);
         }
     };
-    rh_pipeline<true, true>(As, Bs, t, c.end[c.nb - 1], RhNoInit{}, load, [&](const float* A, const float* B) { rh_mma<false>(A, B, acc, accb, mb, nb, li, g); });
+    tile_pipeline<RhStage, true, true>(As, Bs, t, c.end[c.nb - 1], NoInit{}, load, RhFinish{}, [&](const float* A, const float* B) { tile_mma<false>(A, B, acc, accb, mb, nb, li, g); });
     // C layout: column = lane & 15, row = 4 (lane >> 4) + r
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -265,8 +182,8 @@ __global__ void __launch_bounds__(NT) k_rh_dblock(const RhDbArgs p) {
     __shared__ __attribute__((aligned(16))) float As[2][TILE];
     __shared__ __attribute__((aligned(16))) float Bs[2][TILE];
     const RhCols& c = p.c;
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6, li = lane & 15, g = lane >> 4;
-    const int mb = (wid >> 1) * 32, nb = (wid & 1) * 32;
+    const Lane ln = tile_lane();
+    const int t = ln.t, li = ln.li, g = ln.g, mb = ln.mb, nb = ln.nb;
     const int b = rh_block_of(c, blockIdx.y);
     const bool sc = b == c.sb;
     const int64_t R = sc ? c.Mnz : p.M, m0 = static_cast<int64_t>(blockIdx.x) * BM;
@@ -284,7 +201,7 @@ __global__ void __launch_bounds__(NT) k_rh_dblock(const RhDbArgs p) {
     const float* ar = p.g + gi * p.N;
     const int kr = t >> 4, bcol = c0 + (t & 15) * 4;                     // B: n row, quad of output columns
     const float* wb = p.w + c.cb[b];
-    RH_ZERO_ACC();
+    TILE32_ZERO_ACC();
     auto run = [&](auto wv) {                                            // the whole reduction loop, for one form of the weight's loads
         constexpr bool WV = decltype(wv)::value;
         auto load = [&](RhStage& s, int64_t step) {
@@ -300,8 +217,8 @@ __global__ void __launch_bounds__(NT) k_rh_dblock(const RhDbArgs p) {
                 s.ok |= (a_ok ? ma << (4 * q) : 0u) | (n_ok ? mw << (8 + 4 * q) : 0u);
             }
         };
-        rh_pipeline<true, false>(As, Bs, t, (p.N + BK - 1) / BK, RhNoInit{}, load,
-                                 [&](const float* A, const float* B) { rh_mma<false>(A, B, acc, accb, mb, nb, li, g); });
+        tile_pipeline<RhStage, true, false>(As, Bs, t, (p.N + BK - 1) / BK, NoInit{}, load, RhFinish{},
+                                            [&](const float* A, const float* B) { tile_mma<false>(A, B, acc, accb, mb, nb, li, g); });
     };
     if ((c.wvec >> b) & 1u) run(rh_yes{}); else run(rh_no{});           // workgroup-uniform
     float* d = p.d[b];
@@ -336,8 +253,8 @@ __global__ void __launch_bounds__(NT) k_rh_wgrad(const RhWgArgs p) {
     __shared__ __attribute__((aligned(16))) float As[2][TILE];
     __shared__ __attribute__((aligned(16))) float Bs[2][TILE];
     const RhCols& c = p.c;
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6, li = lane & 15, g = lane >> 4;
-    const int mb = (wid >> 1) * 32, nb = (wid & 1) * 32;
+    const Lane ln = tile_lane();
+    const int t = ln.t, li = ln.li, g = ln.g, mb = ln.mb, nb = ln.nb;
     const int b = rh_block_of(c, blockIdx.x);
     const bool sc = b == c.sb;
     const int c0 = (static_cast<int>(blockIdx.x) - (b ? c.end[b - 1] : 0)) * BN, Kb = c.K[b], n0 = blockIdx.y * BM;
@@ -349,7 +266,7 @@ __global__ void __launch_bounds__(NT) k_rh_wgrad(const RhWgArgs p) {
     const int64_t* __restrict__ pos = c.pos;
     const int kr = t >> 4, q4 = (t & 15) * 4;
     const int an = n0 + q4, bc = c0 + q4;
-    RH_ZERO_ACC();
+    TILE32_ZERO_ACC();
     auto run = [&](auto xv, auto scat) {                                 // the whole reduction loop, for one form of the block's loads
         constexpr bool XV = decltype(xv)::value, SC = decltype(scat)::value;
         // row r of the reduction, clamped to a row that exists (row 0: M > 0, and Mnz > 0 where there is a scattered block)
@@ -387,9 +304,9 @@ __global__ void __launch_bounds__(NT) k_rh_wgrad(const RhWgArgs p) {
             }
             prefetch(s, step + 2);
         };
-        rh_pipeline<false, false>(As, Bs, t, (r_end - r_begin + BK - 1) / BK, prefetch, load, [&](const float* A, const float* B) {
-            if (ones) rh_mma<true>(A, B, acc, accb, mb, nb, li, g);
-            else rh_mma<false>(A, B, acc, accb, mb, nb, li, g);
+        tile_pipeline<RhStage, false, false>(As, Bs, t, (r_end - r_begin + BK - 1) / BK, prefetch, load, RhFinish{}, [&](const float* A, const float* B) {
+            if (ones) tile_mma<true>(A, B, acc, accb, mb, nb, li, g);
+            else tile_mma<false>(A, B, acc, accb, mb, nb, li, g);
         });
     };
     const bool xv = (c.vec >> b) & 1u;                                   // workgroup-uniform, like sc
@@ -431,12 +348,7 @@ __global__ void __launch_bounds__(256) k_rh_reduce(const RhRedArgs p) {
     *dst = s;
 }
 
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
-int64_t rh_groups(int64_t M) {                                           // a function of M alone
-    const int64_t g = ceil_div64(M, kRhGroupRows);
-    return g < 1 ? 1 : (g > kRhMaxGroups ? kRhMaxGroups : g);
-}
+int64_t rh_groups(int64_t M) { return row_groups(M, kRhGroupRows, kRhMaxGroups); }
 
 bool rh_shape_ok(int64_t M, int32_t n_blocks, int32_t Kt, int32_t N) {
     return M >= 0 && M <= (int64_t{1} << 24) && n_blocks >= 1 && n_blocks <= kRhMaxDense && Kt >= 1 && Kt <= kRhMaxWidth && N >= 1 && N <= kRhMaxOut;
