@@ -1396,6 +1396,56 @@ int recon_optim_adam(void* const* params, const void* const* grads, void* const*
                      int32_t n_segments, double lr, double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
                      double bias_correction2, const float* clip_scale, recon_stream_t stream);
 
+/* --------------------------------------------------------------------------------------------
+ * E14  The stage-B entity-context batch (csrc/ctx_batch.hip): what train.py:250-258 (again :337-344, and test.py) builds on the host for
+ *      every batch — utils/context_utils.py:62-84 get_batch_unique_entities, :293-301 get_entity_location_unique_entities, :365-385
+ *      get_context_indices, :444-475 get_gat_entity_embeddings / get_selected_gat_entity_embeddings — from tables built once per dataset
+ *      (recon_amd/context_batch.py).  Selection, ordering and copying only: integers to the value, floats to the bit.
+ *      tables: a HOST array of 11 DEVICE pointers, int32 unless said otherwise, none of them empty —
+ *        0 ent_line_ptr [Ne + 2]   the table lines of entity id e are [ptr[e + 1], ptr[e + 2]); e = -1 (ALL_ZERO) is row 0
+ *        1 ent_max_len  [Ne + 1]   tokens of the longest table line of id e, at e + 1 (0 without lines; -1: no entity has this id)
+ *        2 line_start, 3 line_len [L]    a line's tokens are tok_flat[start .. start + len), len already cut at max_sent_len
+ *        4 sf_start, 5 sf_len [S]        the same for a surface form; surface 0 is ['ALL_ZERO']
+ *        6 tok_flat     token ids       7 tok_word [V] word id of a token (embedding_utils.get_idx)
+ *        8 tok_chars [V][max_char_len]   char ids of its first max_char_len characters, the pad char behind its end
+ *        9 gat_row [Ne + 1]   at e + 1: row of gat_emb, -1: a zero row, -2: not in gat_entity2idx (NULL without a GAT table)
+ *       10 gat_emb fp32 [Ng][G]          (NULL without a GAT table)
+ *      dims: a HOST array of 12 int64 — Ne, S, V, L, len(tok_flat), max_sent_len, max_num_contexts, max_char_len, conv_filter_size,
+ *        the pad char id, G, Ng.  Both arrays are read during the call only.
+ *      Every entry: RECON_ERR_INVALID for a NULL pointer, n_pairs < 1 or a dimension out of range, RECON_ERR_UNSUPPORTED above
+ *      recon_ctx_batch_supported's limit, both before any launch.  No allocation, no global atomics, bitwise reproducible.
+ * ------------------------------------------------------------------------------------------*/
+/* 1 when a batch of n_ids = 2 B C entity ids runs in the kernels (train.py:250-258): n_ids even, 2 <= n_ids <= 8192 (16 bytes of LDS hash
+ * table per id plus 2 KiB of bitmap and scan, of the 160 KiB of a workgroup; the reference's batch is 7200), num_entities < 2^31 - 1,
+ * 1 <= num_surfaces < 2^31. */
+int recon_ctx_batch_supported(int64_t n_ids, int64_t num_entities, int64_t num_surfaces);
+/* get_batch_unique_entities + get_entity_location_unique_entities (train.py:250-258; utils/context_utils.py:62-84, :293-301) and the
+ * presence scan of get_selected_gat_entity_embeddings (:455-475), one workgroup, one launch.  entity_indices int64 [n_pairs][2] with
+ * values -1 .. Ne - 1, surface_ids int32 [n_pairs][2].  Writes unique_entities int64 [<= 2 n_pairs + 1]: -1, then the ids in order of
+ * first occurrence; unique_info int32 [<= 2 n_pairs + 1][2] = (lines of the entity with its surface form, surface id of its LAST
+ * occurrence; 0 for a -1 that does not occur); entities_position int64 [n_pairs][2]; with gat_mode 2 ('selected')
+ * nonzero_entity_pos int64 [<= n_pairs], the pairs with a half other than -1 in row order, and pair_slot int32 [n_pairs], a pair's row
+ * among them or -1 (all -1 for gat_mode 0, none, and 1, 'all'); header int32 [8] = U, T_b, P_b, Mnz, the position of the first maximum
+ * of the occurrence counts, flags, 0, 0.  Flags: 1 an id outside [-1, Ne) or without an entity, 2 a surface id outside [0, S), 4 a pair with exactly one -1
+ * half (gat_mode 2), 8 an entity whose gat_row is -2 (gat_mode 1, 2).  A flagged value is never used as an address; its outputs are
+ * unspecified and the host must not launch the other two entries. */
+int recon_ctx_batch_index(const void* const* tables, const int64_t* dims, const int64_t* entity_indices, const int32_t* surface_ids,
+                          int64_t n_pairs, int32_t gat_mode, int64_t* unique_entities, int32_t* unique_info, int64_t* entities_position,
+                          int64_t* nonzero_entity_pos, int32_t* pair_slot, int32_t* header, recon_stream_t stream);
+/* get_context_indices (train.py:250-258; utils/context_utils.py:365-385 over :120-152, :256-291) for the U unique entities of
+ * recon_ctx_batch_index: context_words [U][P_b][T_b] and context_chars [U][P_b][cfs - 1 + T_b (max_char_len + cfs - 1)] of
+ * index_bytes = 4 or 8 (int32 / int64), context_mask bool [U][P_b] (1 from the entity's line count on).  Line 0 is the surface form,
+ * lines 1.. the table's; pad word 0, pad char dims[9].  Every cell is written exactly once, as runs of 16-byte stores (element stores
+ * at an unaligned array's two ends).  RECON_ERR_UNSUPPORTED for a char block of 2^31 - 4096 cells or more.  One launch. */
+int recon_ctx_batch_fill(const void* const* tables, const int64_t* dims, const int64_t* unique_entities, const int32_t* unique_info, int64_t U,
+                         int32_t P_b, int32_t T_b, int32_t index_bytes, void* context_words, void* context_chars, void* context_mask,
+                         recon_stream_t stream);
+/* get_gat_entity_embeddings / get_selected_gat_entity_embeddings (train.py:250-258; utils/context_utils.py:444-475):
+ * gat_entity_embeddings fp32 [n_pairs][2 G] = (gat_emb[gat_row[head]] | gat_emb[gat_row[tail]]), a zero half for a row below 0; with
+ * nonzero_gat_entity_embeddings [Mnz][2 G] (optional) the same row again at pair_slot[pair] >= 0.  Any G >= 1.  One launch. */
+int recon_ctx_batch_gat(const void* const* tables, const int64_t* dims, const int64_t* entity_indices, int64_t n_pairs, const int32_t* pair_slot,
+                        float* gat_entity_embeddings, float* nonzero_gat_entity_embeddings, recon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -351,6 +351,12 @@ SYMBOLS = [
     ("recon_optim_grad_sumsq", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("recon_optim_sgd", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, c_f32p, C.c_void_p]),
     ("recon_optim_adam", C.c_int, [C.c_void_p] * 5 + [C.c_int32] + [C.c_double] * 7 + [c_f32p, C.c_void_p]),
+    ("recon_ctx_batch_supported", C.c_int, [C.c_int64] * 3),
+    ("recon_ctx_batch_index", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), c_i64p, c_i32p, C.c_int64, C.c_int32, c_i64p, c_i32p, c_i64p, c_i64p,
+                                        c_i32p, c_i32p, C.c_void_p]),
+    ("recon_ctx_batch_fill", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), c_i64p, c_i32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("recon_ctx_batch_gat", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), c_i64p, C.c_int64, c_i32p, c_f32p, c_f32p, C.c_void_p]),
 ]
 
 _lib = None
