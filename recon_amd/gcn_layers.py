@@ -13,6 +13,7 @@ the adjacency in 32 x 32 blocks); B <= 65 535 graphs per call."""
 import ctypes as C
 import os
 import math
+from collections import namedtuple
 
 import torch
 from torch.nn.parameter import Parameter
@@ -20,6 +21,12 @@ from torch.nn.modules.module import Module
 
 from . import _lib
 from . import gat_layers as _gl        # the GEMM-family switch (_GEMM_BX3) is ONE module-level setting for GAT and GCN
+
+
+def _f32_args(B, n, I, O, x3, adj3, weight, bias, sup, out, w_split):
+    """recon_gcn_args (include/recon_hip.h) of a launch, and of a backward's `fwd` field."""
+    return _lib.GcnArgs(B=B, n=n, in_features=I, out_features=O, x=x3.data_ptr(), adj=adj3.data_ptr(), weight=weight.data_ptr(),
+                        bias=_lib.ptr(bias), support=sup.data_ptr(), out=out.data_ptr(), w_split=_lib.ptr(w_split))
 
 
 class _GcnFunction(torch.autograd.Function):
@@ -42,8 +49,7 @@ class _GcnFunction(torch.autograd.Function):
         mode = _gl._GEMM_BX3                                  # split-precision GEMMs (fp32-accurate, csrc/gemm_bx3.hip): auto | 1 | 0
         if mode == "1" or (mode != "0" and 2.0 * B * n * I * O >= 2.0e9):    # small products do not pay for the term-plane launches
             w_split = torch.empty(_lib.lib().recon_gcn_split_bytes(I, O), dtype=torch.uint8, device=dev)
-        args = _lib.GcnArgs(B, n, I, O, x3.data_ptr(), adj3.data_ptr(), weight.data_ptr(), _lib.ptr(bias),
-                            sup.data_ptr(), out.data_ptr(), _lib.ptr(w_split))
+        args = _f32_args(B, n, I, O, x3, adj3, weight, bias, sup, out, w_split)
         with _lib.on_device(dev):
             _lib.check(_lib.lib().recon_gcn_fwd(C.byref(args), _lib.current_stream()), "recon_gcn_fwd")
         ctx.save_for_backward(x3, adj3, weight, bias, sup, out, w_split)
@@ -66,22 +72,31 @@ class _GcnFunction(torch.autograd.Function):
         g_adj = torch.empty(B, n, n, **f32) if nadj else None
         g_w = torch.empty(I, O, **f32) if nw else None
         g_b = torch.empty(O, **f32) if (nb and bias is not None) else None
-        fwd = _lib.GcnArgs(B, n, I, O, x3.data_ptr(), adj3.data_ptr(), weight.data_ptr(), _lib.ptr(bias), sup.data_ptr(),
-                           out.data_ptr(), _lib.ptr(w_split))
         gs_split = (torch.empty(L.recon_gcn_bwd_split_bytes(B, n, O), dtype=torch.uint8, device=dev)
                     if (w_split is not None and g_w is not None) else None)
-        args = _lib.GcnBwdArgs(fwd, gout.data_ptr(), g_sup.data_ptr(), partial.data_ptr(), _lib.ptr(g_x), _lib.ptr(g_adj),
-                               _lib.ptr(g_w), _lib.ptr(g_b), _lib.ptr(gs_split))
+        args = _lib.GcnBwdArgs(fwd=_f32_args(B, n, I, O, x3, adj3, weight, bias, sup, out, w_split), grad_out=gout.data_ptr(),
+                               g_support=g_sup.data_ptr(), partial=partial.data_ptr(), g_x=_lib.ptr(g_x), g_adj=_lib.ptr(g_adj),
+                               g_weight=_lib.ptr(g_w), g_bias=_lib.ptr(g_b), gs_split=_lib.ptr(gs_split))
         with _lib.on_device(dev):
             _lib.check(L.recon_gcn_bwd(C.byref(args), _lib.current_stream()), "recon_gcn_bwd")
         xs, adjs = ctx.shapes
         return (g_x.view(xs) if g_x is not None else None, g_adj.view(adjs) if g_adj is not None else None, g_w, g_b)
 
 
-def _rows_view(t, feat, pads_read=True):
-    """(data_ptr-compatible 2-D view info) of a [..., n, feat] bf16 tensor whose rows are feat contiguous elements at a regular
-    row stride ld with ld % 8 == 0 and ld >= feat rounded up to 8 — the layout the bf16 kernels read in place (a contiguous tensor
-    with feat % 8 == 0, or the padded views this module hands out).  Returns ld, or None if the tensor has to be repacked."""
+def _up8(v):
+    return (v + 7) // 8 * 8
+
+
+# the layouts a kernel reads in place, as rules: (row stride a multiple of, byte alignment of the first row, pad columns are multiplied)
+_MFMA = (8, 16, True)            # the GEMMs' rows: ld % 8 == 0, ld >= up8(feat), 16-byte aligned, and the pad columns feat .. up8(feat) are READ
+_MFMA_UNREAD = (8, 16, False)    # the same rows where nothing multiplies the pad columns (a gradient's, or a kernel that masks its K tail)
+_MASKED = (2, 4, False)          # rows a kernel with masked row tails reads: ld even, ld >= feat, 4-byte aligned
+
+
+def _row_stride(t, feat, rule):
+    """Row stride ld of a [..., n, feat] bf16 tensor whose rows are feat contiguous elements at ONE regular stride that `rule` admits — a
+    contiguous tensor with feat % 8 == 0, or the padded views this module hands out.  None: the tensor has to be repacked."""
+    mult, align, pads_read = rule
     if t.dim() < 2 or t.stride(-1) != 1:
         return None
     if pads_read and feat % 8 and not getattr(t, "_recon_padded", False):
@@ -89,7 +104,7 @@ def _rows_view(t, feat, pads_read=True):
         # zeros there — somebody else's `buf[..., :feat]` may carry inf / NaN in them, and 0 * NaN would poison the result
         return None
     ld = t.stride(-2)
-    if ld % 8 or ld < (feat + 7) // 8 * 8 or t.data_ptr() % 16:
+    if ld % mult or ld < feat or t.data_ptr() % align:         # a multiple of 8 that is >= feat is >= up8(feat)
         return None
     rows = t.shape[-2]
     for d in range(t.dim() - 3, -1, -1):                       # leading dims must continue the same row sequence
@@ -99,25 +114,13 @@ def _rows_view(t, feat, pads_read=True):
     return ld
 
 
-def _rows_in_place(t, feat):
-    """Row stride of a [..., n, feat] bf16 tensor a kernel with masked row tails can read where it lies: rows of feat contiguous elements
-    at a regular EVEN stride >= feat, 4-byte aligned.  None: repack."""
-    if t.dim() < 2 or t.stride(-1) != 1:
-        return None
-    ld = t.stride(-2)
-    if ld % 2 or ld < feat or t.data_ptr() % 4:
-        return None
-    rows = t.shape[-2]
-    for d in range(t.dim() - 3, -1, -1):
-        if t.shape[d] != 1 and t.stride(d) != rows * ld:
-            return None
-        rows *= t.shape[d]
-    return ld
+def _rows_view(t, feat, pads_read=True):
+    return _row_stride(t, feat, _MFMA if pads_read else _MFMA_UNREAD)
 
 
 def _packed_rows(t, feat, zero_pad):
     """[rows, ld] bf16 buffer holding t's rows (ld = feat rounded up to 8); pad columns zeroed when the kernels multiply them."""
-    ld = (feat + 7) // 8 * 8
+    ld = _up8(feat)
     t2 = t.reshape(-1, feat)
     if ld == feat:
         return t2.contiguous(), ld
@@ -126,20 +129,188 @@ def _packed_rows(t, feat, zero_pad):
     return buf, ld
 
 
+def _rows_or_packed(t, feat, rule, zero_pad):
+    """(tensor, ld): t's rows where they lie if `rule` admits them, else a packed copy."""
+    ld = _row_stride(t, feat, rule)
+    return (t, ld) if ld is not None else _packed_rows(t, feat, zero_pad)
+
+
+def _grad_rows(gout, feat, rule):
+    """(tensor, ld) of a gradient as bf16 rows; its pad columns are never read, so a copy leaves them unwritten."""
+    if gout.dtype != torch.bfloat16:
+        gout = gout.to(torch.bfloat16)
+    return _rows_or_packed(gout, feat, rule, False)
+
+
+def _strides(lead, ld):
+    """Strides of a [*lead, feat] view over rows of stride ld (lead = leading dims ending with the row dim)."""
+    st, acc = [], ld
+    for d in reversed(lead):
+        st.append(acc)
+        acc *= d
+    return tuple(reversed(st)) + (1,)
+
+
+def _padded_result(out_p, lead, feat, ld, zero_tail):
+    """The [rows, ld] result buffer as the caller's [*lead, feat]: a plain view, or (feat < ld) a strided one tagged `_recon_padded`, whose
+    pad columns the next layer and the backward read in place (zero_tail: the kernel did not write them as zeros itself).  The view
+    starts where out_p starts (as_strided keeps the storage offset: the last layer of a stack's buffer)."""
+    if ld == feat:
+        return out_p.view(lead + (feat,))
+    if zero_tail:
+        out_p[:, feat:].zero_()
+    out = out_p.as_strided(lead + (feat,), _strides(lead, ld))
+    out._recon_padded = True
+    return out
+
+
+def _grad_view(g, shape, feat, ld):
+    """A [rows, ld] gradient buffer (or None) in the caller's `shape`; untagged: nothing reads a gradient's pad columns, which stay unwritten."""
+    if g is None:
+        return None
+    return g.view(shape) if ld == feat else g.as_strided(shape, _strides(shape[:-1], ld))
+
+
 _FUSED = os.environ.get("RECON_GCN_FUSED", "1") != "0"
+_FUSED_MAX_N = 32            # csrc/gcn_b16.hip gcn_fused_ok / recon_gcn_b16_stack_fwd: `a->n <= 32` (one 32-row tile per graph)
+_FUSED_MAX_WIDTH = 320       # csrc/gcn_b16.hip `kFusedNT * 16` (kFusedNT = 20 column tiles): `a->ldo <= kFusedNT * 16`
 
 
-class _NoGradCtx:
-    """Stands in for autograd's ctx when a forward runs outside autograd (torch.no_grad())."""
-    needs_input_grad = (False, False, False, False, False)
-
-    def save_for_backward(self, *tensors):
-        pass
+def _fits_int32(B, n, I, O):        # csrc/gcn_b16.hip gcn_fused_ok: `B * n * ld * 2 < 0x7fffffff` for ldx and ldo (the fused kernels index bytes in 32 bits)
+    return B * n * _up8(max(I, O)) * 2 < 2 ** 31 - 1
 
 
-_NO_GRAD_CTX = _NoGradCtx()
+class _PlaneCache(dict):
+    """Repacked weights kept across calls: (weight data_ptr, version, in, out, device) -> (planes, weight).  The key is identity + version:
+    an in-place update through the tensor bumps the version and misses; one through `.data` does NOT — drop() / clear() are for that.  The
+    entry keeps `weight` alive (its data_ptr is the key); at 64 entries the next insertion empties the cache first."""
+
+    def find(self, weight, I, O, dev):
+        """(key, the planes kept under it or None)"""
+        key = (weight.data_ptr(), weight._version, I, O, dev)
+        return key, self.get(key, (None,))[0]
+
+    def put(self, key, planes, weight):
+        if len(self) >= 64:
+            self.clear()
+        self[key] = (planes, weight)
+
+    def drop(self, weight):
+        """Forget what belongs to this weight tensor (by identity, or by address)."""
+        for k in [k for k, v in self.items() if v[1] is weight or k[0] == weight.data_ptr()]:
+            self.pop(k, None)
+
+
 _PLANES_CACHE = os.environ.get("RECON_GCN_PLANES_CACHE", "1") != "0"
-_PLANES = {}        # (weight data_ptr, version, in, out, device) -> (planes, weight): repacked weights of frozen layers
+_PLANES = _PlaneCache()            # the layer's planes (recon_gcn_b16_fwd's w_planes) of frozen eval()-mode layers: invalidate_planes()
+_STACK_PLANES = _PlaneCache()      # gcn_stack()'s transposed planes (recon_gcn_b16_transposed_planes): invalidate_stack_planes()
+
+
+def invalidate_stack_planes():
+    """Drop the repacked weights gcn_stack() keeps (after an in-place write through `weight.data`)."""
+    _STACK_PLANES.clear()
+
+
+# stands in for autograd's ctx when a forward body runs outside autograd (torch.no_grad()): the bodies only READ needs_input_grad, and this
+# value cannot be written to — one instance serves every call
+_NO_GRAD_CTX = namedtuple("_NoGradCtx", "needs_input_grad")((False,) * 5)
+
+
+def _require_bf16(message, *tensors):
+    for t in tensors:
+        if t is not None and (not t.is_cuda or t.dtype != torch.bfloat16):
+            raise TypeError(message)
+
+
+def _b16_args(B, n, I, O, xr, ldx, adj, weight, bias, sup, out_p, o8, planes, planes_ready, ragged=None, total_rows=0):
+    """recon_gcn_b16_args (include/recon_hip.h) of a launch and of a backward's `fwd` field (planes_ready = 1: the forward filled them)."""
+    a = _lib.GcnB16Args(B=B, n=n, in_features=I, out_features=O, x=xr.data_ptr(), ldx=ldx, adj=adj.data_ptr(),
+                        weight=weight.data_ptr(), bias=_lib.ptr(bias), support=_lib.ptr(sup), lds=o8, out=out_p.data_ptr(), ldo=o8,
+                        w_planes=planes.data_ptr(), w_planes_valid=planes_ready)
+    if ragged is not None:
+        a.node_ptr, a.adj_ptr, a.total_rows = ragged[0].data_ptr(), ragged[1].data_ptr(), total_rows
+    return a
+
+
+# The geometry value that tells a dense batch from a ragged one in the two bodies below: (rows, B, n, ragged, lead, adj_shape, partial, what).
+# rows: node rows of x; B, n: graphs and (largest) graph size; ragged: the ragged batch's (node_ptr, adj_ptr) tensors, else None; lead: the leading
+# shape of x and of the result; adj_shape: g_adj's; partial: (B, n, extra) for the backward's scratch, recon_gcn_b16_bwd_partial_floats(B, n, in,
+# out) + extra * out floats; what: suffix of the entries' names.  A plain tuple, unpacked once per body: building a named one cost the no_grad
+# layer path a microsecond per call
+def _b16_forward(ctx, geo, x, adj, weight, bias, keep_planes):
+    """The forward of both bf16 Functions.  Reads ctx.needs_input_grad and nothing else of ctx; returns (result, tensors to save, meta)."""
+    rows, B, n, ragged, lead, _, _, what = geo
+    need = ctx.needs_input_grad
+    I, O, dev, L = x.shape[-1], weight.shape[1], x.device, _lib.lib()
+    o8, bf = _up8(O), dict(dtype=torch.bfloat16, device=dev)
+    # `support` = x @ W is only needed again for d adj; without it the dense forward is ONE kernel (k_gcn_b16_fused_fwd) that keeps it in registers
+    fused = ragged is None and not need[1] and n <= _FUSED_MAX_N and o8 <= _FUSED_MAX_WIDTH and _fits_int32(B, n, I, O) and _FUSED
+    # inference through the fused kernel: it masks the K tail, so what lies behind a row's last feature is never multiplied — anybody's
+    # padded rows, and unpadded ones (4-byte aligned), are read in place; training keeps rows it can hand to the weight-gradient GEMM
+    masked = fused and not any(need)
+    rule = _MFMA_UNREAD if masked else _MFMA
+    xr, ldx = x, _row_stride(x, I, rule)
+    if ldx is None and masked and I % 2 == 0 and x.is_contiguous() and x.data_ptr() % 16 == 0:
+        ldx = I                                                # ... contiguous even rows too, which no rule admits
+    elif ldx is None:
+        xr, ldx = _packed_rows(x, I, zero_pad=True)
+    sup = None if fused else torch.empty(rows, o8, **bf)
+    out_p = torch.empty(rows, o8, **bf)
+    weight = weight.contiguous()
+    # W^T / W repacked for the matrix cores: every call, or kept across calls for a module in eval() mode (`keep_planes`, _PLANES)
+    frozen = _PLANES_CACHE and keep_planes and not need[2]
+    key, planes = _PLANES.find(weight, I, O, dev) if frozen else (None, None)
+    hit = planes is not None
+    if not hit:
+        planes = torch.empty(L.recon_gcn_b16_planes_bytes(I, O), dtype=torch.uint8, device=dev)
+    args = _b16_args(B, n, I, O, xr, ldx, adj, weight, bias, sup, out_p, o8, planes, 1 if hit else 0, ragged, rows)
+    with _lib.on_device(dev):
+        _lib.check(L.recon_gcn_b16_fwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_fwd" + what)
+    if frozen and not hit:
+        _PLANES.put(key, planes, weight)
+    return (_padded_result(out_p, lead, O, o8, not fused), (xr, adj, weight, bias, sup, out_p, planes), (geo, I, O, ldx, o8))
+
+
+def _b16_backward(ctx, gout):
+    """The backward of both bf16 Functions: (g_x, g_adj, g_weight, g_bias, None for the fifth argument)."""
+    xr, adj, weight, bias, sup, out_p, planes = ctx.saved_tensors
+    geo, I, O, ldx, o8 = ctx.meta
+    rows, B, n, ragged, lead, adj_shape, (pB, pn, extra), what = geo
+    dev, L = gout.device, _lib.lib()
+    bf = dict(dtype=torch.bfloat16, device=dev)
+    nx, nadj, nw, nb = ctx.needs_input_grad[:4]
+    gr, ldg = _grad_rows(gout, O, _MFMA_UNREAD)
+    i8 = _up8(I)
+    g_sup = torch.empty(rows, o8, **bf)
+    partial = torch.empty(L.recon_gcn_b16_bwd_partial_floats(pB, pn, I, O) + extra * O, dtype=torch.float32, device=dev)
+    g_x = torch.empty(rows, i8, **bf) if nx else None
+    g_adj = torch.empty(adj_shape, **bf) if nadj else None
+    g_w = torch.empty(I, O, **bf) if nw else None
+    g_b = torch.empty(O, **bf) if (nb and bias is not None) else None
+    args = _lib.GcnB16BwdArgs(fwd=_b16_args(B, n, I, O, xr, ldx, adj, weight, bias, sup, out_p, o8, planes, 1, ragged, rows), grad_out=gr.data_ptr(), ldg=ldg,
+                              g_support=g_sup.data_ptr(), partial=partial.data_ptr(), g_x=_lib.ptr(g_x), ldgx=i8, g_adj=_lib.ptr(g_adj),
+                              g_weight=_lib.ptr(g_w), g_bias=_lib.ptr(g_b), zeros=_lib.zero_page(dev).data_ptr())
+    with _lib.on_device(dev):
+        _lib.check(L.recon_gcn_b16_bwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_bwd" + what)
+    return _grad_view(g_x, lead + (I,), I, i8), g_adj, g_w, g_b, None
+
+
+def _keep(ctx, result):
+    """A forward body's (result, tensors, meta) onto autograd's ctx."""
+    out, saved, ctx.meta = result
+    ctx.save_for_backward(*saved)
+    return out
+
+
+def _dense_forward(ctx, x, adj, weight, bias, keep_planes=False):
+    _require_bf16("recon_amd: the bfloat16 GraphConvolution path needs bfloat16 GPU tensors for input, adj, weight and bias", x, adj, weight, bias)
+    n, I = x.shape[-2], x.shape[-1]
+    B = x.numel() // (n * I) if x.numel() else 0
+    adj3 = adj.contiguous().view(-1, n, n) if adj.numel() else adj.reshape(0, n, n)
+    if adj3.shape[0] != B or weight.shape[0] != I:
+        raise ValueError("GraphConvolution: inconsistent shapes")
+    geo = (B * n, B, n, None, x.shape[:-1], tuple(adj.shape), (B, n, 0), "")
+    return _b16_forward(ctx, geo, x, adj3, weight, bias, keep_planes)
 
 
 class _GcnB16Function(torch.autograd.Function):
@@ -149,92 +320,9 @@ class _GcnB16Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, adj, weight, bias, keep_planes=False):
-        for t in (x, adj, weight, bias):
-            if t is not None and (not t.is_cuda or t.dtype != torch.bfloat16):
-                raise TypeError("recon_amd: the bfloat16 GraphConvolution path needs bfloat16 GPU tensors for input, adj, weight and bias")
-        n, I = x.shape[-2], x.shape[-1]
-        O = weight.shape[1]
-        B = x.numel() // (n * I) if x.numel() else 0
-        adj3 = adj.contiguous().view(-1, n, n) if adj.numel() else adj.reshape(0, n, n)
-        if adj3.shape[0] != B or weight.shape[0] != I:
-            raise ValueError("GraphConvolution: inconsistent shapes")
-        dev = x.device
-        L = _lib.lib()
-        o8 = (O + 7) // 8 * 8
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        # `support` = x @ W is only needed again for d adj; without it the forward is ONE kernel (csrc/gcn_b16.hip k_gcn_b16_fused_fwd:
-        # n <= 32, out <= 320) that keeps it in registers
-        fused = (not ctx.needs_input_grad[1]) and n <= 32 and o8 <= 320 and B * n * max((I + 7) // 8 * 8, o8) * 2 < 2 ** 31 - 1 and _FUSED
-        # inference through the fused kernel: it masks the K tail, so what lies behind a row's last feature is never multiplied — anybody's
-        # padded rows, and unpadded ones (4-byte aligned), are read in place; training keeps rows it can hand to the weight-gradient GEMM
-        masked = fused and not any(ctx.needs_input_grad)
-        ldx = _rows_view(x, I, pads_read=not masked)
-        xr = x
-        if ldx is None and masked and I % 2 == 0 and x.is_contiguous() and x.data_ptr() % 16 == 0:
-            ldx = I
-        elif ldx is None:
-            xr, ldx = _packed_rows(x, I, zero_pad=True)
-        sup = None if fused else torch.empty(B * n, o8, **bf)
-        out_p = torch.empty(B * n, o8, **bf)
-        weight = weight.contiguous()
-        # W^T / W repacked for the matrix cores: the weight of a module in eval() mode keeps its planes across calls (`keep_planes`), keyed
-        # on identity + version (an in-place update through the tensor bumps the version; one through `.data` does NOT — the module drops
-        # its planes in reset_parameters / load_state_dict / _apply and offers invalidate_planes()); otherwise repacked every call
-        key = (weight.data_ptr(), weight._version, I, O, str(dev))
-        frozen = _PLANES_CACHE and keep_planes and not ctx.needs_input_grad[2]
-        hit = _PLANES.get(key) if frozen else None
-        planes = hit[0] if hit is not None else torch.empty(L.recon_gcn_b16_planes_bytes(I, O), dtype=torch.uint8, device=dev)
-        args = _lib.GcnB16Args(B, n, I, O, xr.data_ptr(), ldx, adj3.data_ptr(), weight.data_ptr(), _lib.ptr(bias), _lib.ptr(sup), o8,
-                               out_p.data_ptr(), o8, planes.data_ptr(), 1 if hit is not None else 0, None, None, 0)
-        with _lib.on_device(dev):
-            _lib.check(L.recon_gcn_b16_fwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_fwd")
-        if hit is None and frozen:
-            if len(_PLANES) >= 64:
-                _PLANES.clear()
-            _PLANES[key] = (planes, weight)                              # keeps `weight` alive: its data_ptr is the key
-        ctx.save_for_backward(xr, adj3, weight, bias, sup, out_p, planes)
-        ctx.meta = (B, n, I, O, ldx, o8, tuple(x.shape), tuple(adj.shape))
-        if o8 == O:
-            return out_p.view(x.shape[:-1] + (O,))
-        if not fused:                                                     # the next layer (and the backward) read these columns in place;
-            out_p[:, O:].zero_()                                          # the fused kernel writes them as zeros itself
-        out = out_p.as_strided(x.shape[:-1] + (O,), _strides(x.shape[:-1], o8))
-        out._recon_padded = True
-        return out
+        return _keep(ctx, _dense_forward(ctx, x, adj, weight, bias, keep_planes))
 
-    @staticmethod
-    def backward(ctx, gout):
-        xr, adj3, weight, bias, sup, out_p, planes = ctx.saved_tensors
-        B, n, I, O, ldx, o8, xs, adjs = ctx.meta
-        dev = gout.device
-        L = _lib.lib()
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        nx, nadj, nw, nb = ctx.needs_input_grad[:4]
-        if gout.dtype != torch.bfloat16:
-            gout = gout.to(torch.bfloat16)
-        ldg = _rows_view(gout, O, pads_read=False)                 # pad columns of a gradient are never read
-        gr = gout
-        if ldg is None:
-            gr, ldg = _packed_rows(gout, O, zero_pad=False)     # pad columns of a gradient are never read
-        i8 = (I + 7) // 8 * 8
-        g_sup = torch.empty(B * n, o8, **bf)
-        partial = torch.empty(L.recon_gcn_b16_bwd_partial_floats(B, n, I, O), dtype=torch.float32, device=dev)
-        g_x = torch.empty(B * n, i8, **bf) if nx else None
-        g_adj = torch.empty(B, n, n, **bf) if nadj else None
-        g_w = torch.empty(I, O, **bf) if nw else None
-        g_b = torch.empty(O, **bf) if (nb and bias is not None) else None
-        fwd = _lib.GcnB16Args(B, n, I, O, xr.data_ptr(), ldx, adj3.data_ptr(), weight.data_ptr(), _lib.ptr(bias), _lib.ptr(sup), o8,
-                              out_p.data_ptr(), o8, planes.data_ptr(), 1, None, None, 0)
-        args = _lib.GcnB16BwdArgs(fwd, gr.data_ptr(), ldg, g_sup.data_ptr(), partial.data_ptr(), _lib.ptr(g_x), i8, _lib.ptr(g_adj),
-                                  _lib.ptr(g_w), _lib.ptr(g_b), _lib.zero_page(dev).data_ptr())
-        with _lib.on_device(dev):
-            _lib.check(L.recon_gcn_b16_bwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_bwd")
-        if g_x is not None:
-            if i8 == I:
-                g_x = g_x.view(xs)
-            else:                       # pad columns stay unwritten and the view untagged: nothing reads the pad columns of a gradient
-                g_x = g_x.as_strided(xs, _strides(xs[:-1], i8))   # (_rows_view(..., pads_read=False) in the producer layer's backward)
-        return g_x, (g_adj.view(adjs) if g_adj is not None else None), g_w, g_b, None
+    backward = staticmethod(_b16_backward)
 
 
 class RaggedAdjacency:
@@ -274,82 +362,16 @@ class _GcnB16RaggedFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, values, weight, bias, ragged):
-        for t in (x, values, weight, bias):
-            if t is not None and (not t.is_cuda or t.dtype != torch.bfloat16):
-                raise TypeError("recon_amd: the ragged GraphConvolution path needs bfloat16 GPU tensors for input, adjacency values, weight and bias")
+        _require_bf16("recon_amd: the ragged GraphConvolution path needs bfloat16 GPU tensors for input, adjacency values, weight and bias", x, values, weight, bias)
         if x.dim() != 2 or x.shape[0] != ragged.total_rows or weight.shape[0] != x.shape[1]:
             raise ValueError("GraphConvolution (ragged): input must be [total nodes, in_features]")
         if ragged.B > _lib.MAX_BATCH:
             raise NotImplementedError("GraphConvolution (ragged): more than %d graphs per call" % _lib.MAX_BATCH)
-        N, I = x.shape
-        O = weight.shape[1]
-        dev = x.device
-        L = _lib.lib()
-        o8 = (O + 7) // 8 * 8
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        ldx = _rows_view(x, I)
-        xr = x
-        if ldx is None:
-            xr, ldx = _packed_rows(x, I, zero_pad=True)
-        values = values.contiguous()
-        sup = torch.empty(N, o8, **bf)
-        out_p = torch.empty(N, o8, **bf)
-        weight = weight.contiguous()
-        planes = torch.empty(L.recon_gcn_b16_planes_bytes(I, O), dtype=torch.uint8, device=dev)
-        args = _lib.GcnB16Args(ragged.B, ragged.n_max, I, O, xr.data_ptr(), ldx, values.data_ptr(), weight.data_ptr(), _lib.ptr(bias), sup.data_ptr(), o8,
-                               out_p.data_ptr(), o8, planes.data_ptr(), 0, ragged.node_ptr.data_ptr(), ragged.adj_ptr.data_ptr(), N)
-        with _lib.on_device(dev):
-            _lib.check(L.recon_gcn_b16_fwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_fwd (ragged)")
-        ctx.save_for_backward(xr, values, weight, bias, sup, out_p, planes)
-        ctx.ragged = ragged
-        ctx.meta = (N, I, O, ldx, o8)
-        if o8 == O:
-            return out_p
-        out_p[:, O:].zero_()
-        out = out_p.as_strided((N, O), (o8, 1))
-        out._recon_padded = True
-        return out
+        N = x.shape[0]
+        geo = (N, ragged.B, ragged.n_max, (ragged.node_ptr, ragged.adj_ptr), (N,), tuple(values.shape), (1, N, ragged.B), " (ragged)")
+        return _keep(ctx, _b16_forward(ctx, geo, x, values.contiguous(), weight, bias, False))
 
-    @staticmethod
-    def backward(ctx, gout):
-        xr, values, weight, bias, sup, out_p, planes = ctx.saved_tensors
-        N, I, O, ldx, o8 = ctx.meta
-        rg = ctx.ragged
-        dev = gout.device
-        L = _lib.lib()
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        nx, nadj, nw, nb, _ = ctx.needs_input_grad
-        if gout.dtype != torch.bfloat16:
-            gout = gout.to(torch.bfloat16)
-        ldg = _rows_view(gout, O, pads_read=False)
-        gr = gout
-        if ldg is None:
-            gr, ldg = _packed_rows(gout, O, zero_pad=False)
-        i8 = (I + 7) // 8 * 8
-        g_sup = torch.empty(N, o8, **bf)
-        partial = torch.empty(L.recon_gcn_b16_bwd_partial_floats(1, N, I, O) + rg.B * O, dtype=torch.float32, device=dev)
-        g_x = torch.empty(N, i8, **bf) if nx else None
-        g_adj = torch.empty_like(values) if nadj else None
-        g_w = torch.empty(I, O, **bf) if nw else None
-        g_b = torch.empty(O, **bf) if (nb and bias is not None) else None
-        fwd = _lib.GcnB16Args(rg.B, rg.n_max, I, O, xr.data_ptr(), ldx, values.data_ptr(), weight.data_ptr(), _lib.ptr(bias), sup.data_ptr(), o8,
-                              out_p.data_ptr(), o8, planes.data_ptr(), 1, rg.node_ptr.data_ptr(), rg.adj_ptr.data_ptr(), N)
-        args = _lib.GcnB16BwdArgs(fwd, gr.data_ptr(), ldg, g_sup.data_ptr(), partial.data_ptr(), _lib.ptr(g_x), i8, _lib.ptr(g_adj),
-                                  _lib.ptr(g_w), _lib.ptr(g_b), _lib.zero_page(dev).data_ptr())
-        with _lib.on_device(dev):
-            _lib.check(L.recon_gcn_b16_bwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_bwd (ragged)")
-        if g_x is not None and i8 != I:
-            g_x = g_x.as_strided((N, I), (i8, 1))
-        return g_x, g_adj, g_w, g_b, None
-
-
-def _strides(lead, ld):
-    """Strides of a [*lead, feat] view over rows of stride ld (lead = leading dims ending with the row dim)."""
-    st, acc = [], ld
-    for d in reversed(lead):
-        st.append(acc)
-        acc *= d
-    return tuple(reversed(st)) + (1,)
+    backward = staticmethod(_b16_backward)
 
 
 class SparseMM(torch.autograd.Function):
@@ -378,16 +400,16 @@ def _mm(a, b, a_t, b_t):
     return torch.mm(a.t() if a_t else a, b.t() if b_t else b)
 
 
-_STACK_PLANES = {}     # (weight data_ptr, version, in, out, device) -> (W^T planes, weight)
-
-
-def invalidate_stack_planes():
-    """Drop the repacked weights gcn_stack() keeps (after an in-place write through `weight.data`)."""
-    _STACK_PLANES.clear()
-
-
 def _ptrs(base, offsets):
     return (C.c_void_p * len(offsets))(*[base + o for o in offsets])
+
+
+def _stack_args(B, n, I, D, nl, x, ldx, x_rows, ldxr, adj3, ws, bs, planes, poff, acts, o8, **backward):
+    """recon_gcn_b16_stack_train_args (include/recon_hip.h) as the forward fills it; the backward adds its own fields by name (`backward`).
+    x / ldx: the rows layer 0 reads; x_rows / ldxr: where the kernel leaves their aligned copy (None: x already is one)."""
+    return _lib.GcnB16StackTrainArgs(B=B, n=n, in_features=I, hidden=D, L=nl, x=x.data_ptr(), ldx=ldx, x_rows=_lib.ptr(x_rows), ldxr=ldxr,
+                                     adj=adj3.data_ptr(), weight=_lib.ptr_array(ws), bias=_lib.ptr_array(bs), planes=_ptrs(planes.data_ptr(), poff),
+                                     acts=_ptrs(acts.data_ptr(), [l * B * n * o8 * 2 for l in range(nl)]), ldo=o8, **backward)
 
 
 class _GcnB16StackFunction(torch.autograd.Function):
@@ -401,20 +423,17 @@ class _GcnB16StackFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, adj, n_layers, *params):
         ws, bs = list(params[0::2]), list(params[1::2])
-        n, I = x.shape[-2], x.shape[-1]
-        D = ws[0].shape[1]
+        n, I, D = x.shape[-2], x.shape[-1], ws[0].shape[1]
         B = x.numel() // (n * I)
-        dev = x.device
-        L = _lib.lib()
-        o8 = (D + 7) // 8 * 8
+        dev, L, o8 = x.device, _lib.lib(), _up8(D)
         # rows the weight-gradient GEMM of layer 0 can read: 16-byte aligned, stride % 8 == 0 (its pad columns only reach rows of the product
         # that are never stored, so they need no zeros; the forward kernel masks its own K tail)
         ldx = _rows_view(x, I, pads_read=False)
         xr, xin, ldin = x, x, ldx
         if ldx is None:
-            ldin = _rows_in_place(x, I)
+            ldin = _row_stride(x, I, _MASKED)
             if ldin is not None and x.data_ptr() % 16 == 0:          # the forward kernel reads x where it lies and leaves the aligned copy itself
-                ldx = (I + 7) // 8 * 8
+                ldx = _up8(I)
                 xr = torch.empty(B * n, ldx, dtype=torch.bfloat16, device=dev)
             else:
                 xr, ldx = _packed_rows(x, I, zero_pad=False)
@@ -425,41 +444,24 @@ class _GcnB16StackFunction(torch.autograd.Function):
         pb = [(L.recon_gcn_b16_planes_bytes(w.shape[0], D) + 255) // 256 * 256 for w in ws]
         poff = [sum(pb[:l]) for l in range(n_layers)]
         planes = torch.empty(sum(pb), dtype=torch.uint8, device=dev)
-        args = _lib.GcnB16StackTrainArgs(B, n, I, D, n_layers, xin.data_ptr(), ldin, xr.data_ptr() if xr is not xin else None, ldx, adj3.data_ptr(),
-                                         _lib.ptr_array(ws), _lib.ptr_array(bs),
-                                         _ptrs(planes.data_ptr(), poff), _ptrs(acts.data_ptr(), [l * B * n * o8 * 2 for l in range(n_layers)]), o8)
+        args = _stack_args(B, n, I, D, n_layers, xin, ldin, xr if xr is not xin else None, ldx, adj3, ws, bs, planes, poff, acts, o8)
         with _lib.on_device(dev):
             _lib.check(L.recon_gcn_b16_stack_train_fwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_stack_train_fwd")
         ctx.save_for_backward(xr, adj3, acts, planes, *ws, *[b for b in bs if b is not None])
         ctx.meta = (B, n, I, D, n_layers, ldx, o8, tuple(x.shape), [b is not None for b in bs], poff)
-        out_p = acts[n_layers - 1]
-        if o8 == D:
-            return out_p.view(x.shape[:-1] + (D,))
-        out = out_p.as_strided(x.shape[:-1] + (D,), _strides(x.shape[:-1], o8), out_p.storage_offset())
-        out._recon_padded = True
-        return out
+        return _padded_result(acts[n_layers - 1], x.shape[:-1], D, o8, zero_tail=False)
 
     @staticmethod
     def backward(ctx, gout):
         B, n, I, D, nl, ldx, o8, xs, has_b, poff = ctx.meta
         sv = ctx.saved_tensors
-        xr, adj3, acts, planes = sv[0], sv[1], sv[2], sv[3]
-        ws = sv[4:4 + nl]
-        bs, it = [], iter(sv[4 + nl:])
-        for h in has_b:
-            bs.append(next(it) if h else None)
-        dev = gout.device
-        L = _lib.lib()
+        (xr, adj3, acts, planes), ws, it = sv[:4], sv[4:4 + nl], iter(sv[4 + nl:])
+        bs = [next(it) if h else None for h in has_b]
+        dev, L = gout.device, _lib.lib()
         bf = dict(dtype=torch.bfloat16, device=dev)
-        if gout.dtype != torch.bfloat16:
-            gout = gout.to(torch.bfloat16)
-        ldg = _rows_in_place(gout, D)                               # read in place through masked loads: any even row stride
-        gr = gout
-        if ldg is None:
-            gr, ldg = _packed_rows(gout, D, zero_pad=False)
-        i8 = I if I % 4 == 0 else (I + 7) // 8 * 8                  # g_x leaves the kernel as 8-byte stores: a dense [.., I] result where I % 4 == 0
-        need = ctx.needs_input_grad
-        rows = B * n
+        gr, ldg = _grad_rows(gout, D, _MASKED)                      # read in place through masked loads: any even row stride
+        i8 = I if I % 4 == 0 else _up8(I)                           # g_x leaves the kernel as 8-byte stores: a dense [.., I] result where I % 4 == 0
+        need, rows = ctx.needs_input_grad, B * n
         g_sup = torch.empty(nl, rows, o8, **bf)
         partial = torch.empty(L.recon_gcn_b16_stack_bwd_partial_floats(B, n, I, D, nl), dtype=torch.float32, device=dev)
         g_x = torch.empty(rows, i8, **bf) if need[0] else None
@@ -468,18 +470,37 @@ class _GcnB16StackFunction(torch.autograd.Function):
         gbuf = torch.empty(sum(wn) + nl * D, **bf)
         g_w = [gbuf[sum(wn[:l]):sum(wn[:l + 1])].view(ws[l].shape[0], D) if need[3 + 2 * l] else None for l in range(nl)]
         g_b = [gbuf[sum(wn) + l * D:sum(wn) + (l + 1) * D] if (bs[l] is not None and need[4 + 2 * l]) else None for l in range(nl)]
-        args = _lib.GcnB16StackTrainArgs(B, n, I, D, nl, xr.data_ptr(), ldx, None, 0, adj3.data_ptr(), _lib.ptr_array(ws), _lib.ptr_array(bs),
-                                         _ptrs(planes.data_ptr(), poff), _ptrs(acts.data_ptr(), [l * rows * o8 * 2 for l in range(nl)]), o8,
-                                         gr.data_ptr(), ldg, _ptrs(g_sup.data_ptr(), [l * rows * o8 * 2 for l in range(nl)]), partial.data_ptr(),
-                                         _lib.ptr(g_x), i8, _lib.ptr_array(g_w), _lib.ptr_array(g_b), _lib.zero_page(dev).data_ptr())
+        args = _stack_args(B, n, I, D, nl, xr, ldx, None, 0, adj3, ws, bs, planes, poff, acts, o8, grad_out=gr.data_ptr(), ldg=ldg,
+                           g_support=_ptrs(g_sup.data_ptr(), [l * rows * o8 * 2 for l in range(nl)]), partial=partial.data_ptr(), g_x=_lib.ptr(g_x),
+                           ldgx=i8, g_weight=_lib.ptr_array(g_w), g_bias=_lib.ptr_array(g_b), zeros=_lib.zero_page(dev).data_ptr())
         with _lib.on_device(dev):
             _lib.check(L.recon_gcn_b16_stack_train_bwd(C.byref(args), _lib.current_stream()), "recon_gcn_b16_stack_train_bwd")
-        if g_x is not None:
-            g_x = g_x.view(xs) if i8 == I else g_x.as_strided(xs, _strides(xs[:-1], i8))
-        grads = []
-        for l in range(nl):
-            grads += [g_w[l], g_b[l]]
-        return (g_x, None, None, *grads)
+        return (_grad_view(g_x, xs, I, i8), None, None, *[g for l in range(nl) for g in (g_w[l], g_b[l])])
+
+
+def _layer_loop(x, adj, layers):
+    for l in layers:
+        x = l(x, adj)
+    return x
+
+
+def _stack_form(x, adj, layers, need_grad):
+    """How gcn_stack() runs a dense batch: "train" (_GcnB16StackFunction), "infer" (recon_gcn_b16_stack_fwd), or None: layer by layer."""
+    if not (len(layers) >= 2 and len(layers) <= 8 and x.is_cuda and x.dtype == torch.bfloat16 and adj.dtype == torch.bfloat16
+            and x.dim() in (2, 3) and os.environ.get("RECON_GCN_STACK", "1") != "0" and not (need_grad and adj.requires_grad)):
+        return None
+    n, I, D = x.shape[-2], x.shape[-1], layers[0].out_features
+    B = x.numel() // (n * I) if x.numel() else 0
+    # the fused kernels' shapes with 8-byte adjacency / bias loads (csrc/gcn_b16.hip recon_gcn_b16_stack_fwd: n % 4, hidden % 4, `a->B > 65535 * 4`)
+    if not (B > 0 and n <= _FUSED_MAX_N and n % 4 == 0 and D % 4 == 0 and _up8(D) <= _FUSED_MAX_WIDTH and layers[0].in_features == I
+            and all(l.in_features == D and l.out_features == D for l in layers[1:])
+            and all(l.weight.dtype == torch.bfloat16 and (l.bias is None or l.bias.data_ptr() % 8 == 0) for l in layers)
+            and adj.is_contiguous() and adj.data_ptr() % 8 == 0
+            and adj.numel() == B * n * n and _fits_int32(B, n, I, D) and B <= 4 * _lib.MAX_BATCH):
+        return None
+    if need_grad:       # recon_gcn_b16_stack_train_bwd: `in_features > 16 * kFusedNT` is unsupported (g_x of layer 0 is one tile)
+        return "train" if _up8(I) <= _FUSED_MAX_WIDTH and os.environ.get("RECON_GCN_STACK_TRAIN", "1") != "0" else None
+    return "infer" if x.is_contiguous() and I % 2 == 0 and x.data_ptr() % 16 == 0 else None
 
 
 def gcn_stack(x, adj, layers):
@@ -491,68 +512,36 @@ def gcn_stack(x, adj, layers):
     and gradients are bit-equal to the loop, which is also what runs for every other case.  Repacked weights are kept per weight tensor (identity + version); call
     invalidate_stack_planes() after writing through `weight.data`."""
     layers = list(layers)
-    if isinstance(adj, RaggedAdjacency):                                    # graphs of different sizes: layer by layer (GEMM over all rows + aggregate per graph;
-        for l in layers:                                                    # the one-kernel form of a layer was measured and is no faster there, DESIGN 9)
-            x = l(x, adj)
-        return x
+    if isinstance(adj, RaggedAdjacency):        # graphs of different sizes: layer by layer (GEMM over all rows + aggregate per graph;
+        return _layer_loop(x, adj, layers)      # the one-kernel form of a layer was measured and is no faster there, DESIGN 9)
     need_grad = torch.is_grad_enabled() and (x.requires_grad or adj.requires_grad or any(p.requires_grad for l in layers for p in l.parameters()))
-    ok = (len(layers) >= 2 and len(layers) <= 8 and x.is_cuda and x.dtype == torch.bfloat16 and adj.dtype == torch.bfloat16
-          and x.dim() in (2, 3) and os.environ.get("RECON_GCN_STACK", "1") != "0" and not (need_grad and adj.requires_grad))
-    if ok:
-        n, I = x.shape[-2], x.shape[-1]
-        B = x.numel() // (n * I) if x.numel() else 0
-        D = layers[0].out_features
-        ok = (B > 0 and n <= 32 and n % 4 == 0 and D % 4 == 0 and (D + 7) // 8 * 8 <= 320 and layers[0].in_features == I
-              and all(l.in_features == D and l.out_features == D for l in layers[1:])
-              and all(l.weight.dtype == torch.bfloat16 and (l.bias is None or l.bias.data_ptr() % 8 == 0) for l in layers)
-              and adj.is_contiguous() and adj.data_ptr() % 8 == 0
-              and adj.numel() == B * n * n and B * n * max((I + 7) // 8 * 8, (D + 7) // 8 * 8) * 2 < 2 ** 31 - 1 and B <= 4 * _lib.MAX_BATCH)
-        if ok and need_grad:
-            ok = (I + 7) // 8 * 8 <= 320 and os.environ.get("RECON_GCN_STACK_TRAIN", "1") != "0"
-        elif ok:
-            ok = x.is_contiguous() and I % 2 == 0 and x.data_ptr() % 16 == 0
-    if ok and need_grad:
-        params = []
-        for l in layers:
-            params += [l.weight, l.bias]
-        return _GcnB16StackFunction.apply(x, adj, len(layers), *params)
-    if not ok:
-        for l in layers:
-            x = l(x, adj)
-        return x
-    dev = x.device
-    L = _lib.lib()
-    o8 = (D + 7) // 8 * 8
+    form = _stack_form(x, adj, layers, need_grad)
+    if form is None:
+        return _layer_loop(x, adj, layers)
+    if form == "train":
+        return _GcnB16StackFunction.apply(x, adj, len(layers), *[p for l in layers for p in (l.weight, l.bias)])
+    n, I, D = x.shape[-2], x.shape[-1], layers[0].out_features
+    B, dev, L, o8 = x.numel() // (n * I), x.device, _lib.lib(), _up8(D)
     planes = []
     with _lib.on_device(dev):
         for l in layers:
             w = l.weight
-            key = (w.data_ptr(), w._version, l.in_features, D, str(dev))
-            hit = _STACK_PLANES.get(key)
-            if hit is None:
+            key, pl = _STACK_PLANES.find(w, l.in_features, D, dev)
+            if pl is None:
                 kp = (l.in_features + 31) // 32 * 32
                 pl = torch.empty(D * kp, dtype=torch.bfloat16, device=dev)
                 _lib.check(L.recon_gcn_b16_transposed_planes(w.detach().contiguous().data_ptr(), l.in_features, D, pl.data_ptr(), _lib.current_stream()),
                            "recon_gcn_b16_transposed_planes")
-                if len(_STACK_PLANES) >= 64:
-                    _STACK_PLANES.clear()
-                hit = _STACK_PLANES[key] = (pl, w)
-            planes.append(hit[0])
+                _STACK_PLANES.put(key, pl, w)
+            planes.append(pl)
         out_p = torch.empty(B * n, o8, dtype=torch.bfloat16, device=dev)
-        parr = (C.c_void_p * len(layers))(*[pl.data_ptr() for pl in planes])
-        barr = (C.c_void_p * len(layers))(*[(l.bias.data_ptr() if l.bias is not None else None) for l in layers])
-        args = _lib.GcnB16StackArgs(B, n, I, D, len(layers), x.data_ptr(), I, adj.data_ptr(), parr, barr, out_p.data_ptr(), o8)
+        args = _lib.GcnB16StackArgs(B=B, n=n, in_features=I, hidden=D, L=len(layers), x=x.data_ptr(), ldx=I, adj=adj.data_ptr(),
+                                    w_planes=_lib.ptr_array(planes), bias=_lib.ptr_array([l.bias for l in layers]), out=out_p.data_ptr(), ldo=o8)
         rc = L.recon_gcn_b16_stack_fwd(C.byref(args), _lib.current_stream())
-    if rc == -2:                                                            # RECON_ERR_UNSUPPORTED: layer by layer
-        for l in layers:
-            x = l(x, adj)
-        return x
+    if rc == -2:                                # RECON_ERR_UNSUPPORTED: layer by layer
+        return _layer_loop(x, adj, layers)
     _lib.check(rc, "recon_gcn_b16_stack_fwd")
-    if o8 == D:
-        return out_p.view(x.shape[:-1] + (D,))
-    out = out_p.as_strided(x.shape[:-1] + (D,), _strides(x.shape[:-1], o8))
-    out._recon_padded = True
-    return out
+    return _padded_result(out_p, x.shape[:-1], D, o8, zero_tail=False)
 
 
 class GraphConvolution(Module):
@@ -578,9 +567,9 @@ class GraphConvolution(Module):
 
     def invalidate_planes(self):
         """Drop the repacked copies of `weight` an eval()-mode bfloat16 layer keeps across calls.  Needed after an in-place write through
-        `weight.data` (which autograd's version counter does not see); reset_parameters, load_state_dict and .to() / .cuda() call it."""
-        for k in [k for k, v in _PLANES.items() if v[1] is getattr(self, "weight", None) or k[0] == self.weight.data_ptr()]:
-            _PLANES.pop(k, None)
+        `weight.data` (which autograd's version counter does not see); reset_parameters, load_state_dict and .to() / .cuda() call it.
+        Only the layer's own planes: what gcn_stack() keeps of the same weight goes with invalidate_stack_planes()."""
+        _PLANES.drop(self.weight)
 
     def _load_from_state_dict(self, *args, **kwargs):
         super()._load_from_state_dict(*args, **kwargs)
@@ -601,8 +590,8 @@ class GraphConvolution(Module):
                               for b0 in range(0, B, _lib.MAX_BATCH)], dim=0)
         if fn is _GcnB16Function and not torch.is_grad_enabled():
             # inference: nothing is recorded, so the autograd.Function machinery (~10 us per call, a third of this layer's host time at
-            # cfg 3a) is skipped; the same forward runs with a context that saves nothing
-            return _GcnB16Function.forward(_NO_GRAD_CTX, input, adj, self.weight, self.bias, *extra)
+            # cfg 3a) is skipped; the same forward body runs with a context that says "no gradients" and stores nothing
+            return _dense_forward(_NO_GRAD_CTX, input, adj, self.weight, self.bias, *extra)[0]
         return fn.apply(input, adj, self.weight, self.bias, *extra)
 
     def __repr__(self):
