@@ -1446,6 +1446,41 @@ int recon_ctx_batch_fill(const void* const* tables, const int64_t* dims, const i
 int recon_ctx_batch_gat(const void* const* tables, const int64_t* dims, const int64_t* entity_indices, int64_t n_pairs, const int32_t* pair_slot,
                         float* gat_entity_embeddings, float* nonzero_gat_entity_embeddings, recon_stream_t stream);
 
+/* --------------------------------------------------------------------------------------------
+ * E15  A stage-B iteration's two ends over a device-resident dataset (csrc/stage_b.hip; recon_amd/stage_b.py): the batch's rows of the
+ *      arrays that graphs_to_indices returns (parsing/legacy_sp_models.py:276-333), and the rows of a test pass's result file.
+ *      Selection and copying only: integers to the value, confidence to the bit.  Every entry: RECON_ERR_INVALID for a NULL pointer, a
+ *      count or M below 1 or a range outside its array, RECON_ERR_UNSUPPORTED above recon_stage_b_supported's limit, both before any
+ *      launch.  No allocation, no workspace, no atomics, bitwise reproducible.
+ * ------------------------------------------------------------------------------------------*/
+/* 1 when a batch of `count` sentences with num_pairs = n (n - 1) entity pairs and sent_len tokens runs in recon_stage_b_slice
+ * (train.py:247-251): every extent at least 1 and the largest output — entity_markers [count][num_pairs][sent_len], or the id pairs
+ * [count][num_pairs][2] — below 2^31 - 4096 cells (flat output indices are int32).  The reference's batch is 50 x 72 x 36. */
+int recon_stage_b_supported(int64_t count, int64_t num_pairs, int64_t sent_len);
+/* train.py:247-251 with the casts of :261-262 and :309 (again :333-337, and test.py), one launch: batch row b is dataset row
+ * r(b) = order[start + b] (order NULL: start + b), order int64 [order_len] with start + count <= order_len (order NULL: <= N).  A value
+ * of `order` is CLAMPED into [0, N) before use and never becomes an address; validating it is the host's part.  Reads sentences int32
+ * [N][sent_len], markers int8 [N][num_pairs][sent_len], labels int16 [N][num_pairs], num_entities int32 [N] and, both or neither of a
+ * pair, entity_indices / surface_ids int32 [N][num_pairs][2] with their outputs.  Writes sentence_input [count][sent_len] and
+ * entity_markers [count][num_pairs][sent_len] of index_bytes = 4 or 8 (int32 / int64), labels_out int64 [count num_pairs] row-major,
+ * num_entities_out int32 [count], entity_indices_out int64 [count][num_pairs][2] (sign-extended: -1 stays -1), surface_ids_out int32
+ * [count][num_pairs][2] and rows_out int64 [count] = r(b).  Every cell is written exactly once, as runs of 16-byte stores (element
+ * stores at an unaligned array's two ends). */
+int recon_stage_b_slice(const int32_t* sentences, const int8_t* markers, const int16_t* labels, const int32_t* num_entities,
+                        const int32_t* entity_indices, const int32_t* surface_ids, int64_t N, int64_t num_pairs, int64_t sent_len,
+                        const int64_t* order, int64_t order_len, int64_t start, int64_t count, int32_t index_bytes, void* sentence_input,
+                        void* entity_markers, int64_t* labels_out, int32_t* num_entities_out, int64_t* entity_indices_out,
+                        int32_t* surface_ids_out, int64_t* rows_out, recon_stream_t stream);
+/* test.py:285-292 and the indices of :300-302, one launch of one workgroup: for every m < M with labels[m] != ignore_index, in row order,
+ * appends (rows[m / num_pairs] num_pairs + m % num_pairs, predicted[m], labels[m], confidence[m]) to the four output arrays of
+ * `capacity` elements, starting at state[0].  labels, predicted int64 [M], confidence fp32 [M], rows int64 [M / num_pairs] (M a multiple
+ * of num_pairs).  state int64 [2] on the device: [0] the count of rows appended so far, read at the start and stored at the end with
+ * plain loads and stores — the calls that share a state must run on ONE stream; [1] set to 1 when a row's place was at or beyond
+ * `capacity`: such a row is not stored, the count goes on.  The outputs may be NULL when capacity is 0. */
+int recon_stage_b_collect(const int64_t* labels, const int64_t* predicted, const float* confidence, const int64_t* rows, int64_t M,
+                          int64_t num_pairs, int64_t ignore_index, int64_t* state, int64_t capacity, int64_t* out_pair,
+                          int64_t* out_predicted, int64_t* out_gold, float* out_confidence, recon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -357,6 +357,11 @@ SYMBOLS = [
     ("recon_ctx_batch_fill", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), c_i64p, c_i32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("recon_ctx_batch_gat", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), c_i64p, C.c_int64, c_i32p, c_f32p, c_f32p, C.c_void_p]),
+    ("recon_stage_b_supported", C.c_int, [C.c_int64] * 3),
+    ("recon_stage_b_slice", C.c_int, [c_i32p, C.c_void_p, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_int64, C.c_int64, C.c_int64, c_i64p, C.c_int64,
+                                      C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, c_i64p, c_i32p, c_i64p, c_i32p, c_i64p, C.c_void_p]),
+    ("recon_stage_b_collect", C.c_int, [c_i64p, c_i64p, c_f32p, c_i64p, C.c_int64, C.c_int64, C.c_int64, c_i64p, C.c_int64, c_i64p, c_i64p, c_i64p,
+                                        c_f32p, C.c_void_p]),
 ]
 
 _lib = None
