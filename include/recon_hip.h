@@ -1481,6 +1481,43 @@ int recon_stage_b_collect(const int64_t* labels, const int64_t* predicted, const
                           int64_t num_pairs, int64_t ignore_index, int64_t* state, int64_t capacity, int64_t* out_pair,
                           int64_t* out_predicted, int64_t* out_gold, float* out_confidence, recon_stream_t stream);
 
+/* --------------------------------------------------------------------------------------------
+ * E16 ContextAware's attention over ghosts (csrc/pair_attn.hip): the per-sentence self-attention over the pair states with the diagonal
+ *     left out, between the encoder and the head of the baseline model (models/baselines.py:86-112):
+ *     S[b][i][j] = memory[b][i] . states[b][j] for j != i;  P[b][i][:] = softmax over j != i of S[b][i][:], P[b][i][i] = 0;
+ *     out[b][i] = (states[b][i] | sum_j P[b][i][j] states[b][j])                                                    [B][C][2 D]
+ *     states and memory (= states W^T: recon_pair_transitions_fwd with act linear and no bias forms it) are B C rows of D floats at
+ *     ONE row stride each (ld_s, ld_m >= D, elements), sentence b's pair i at row b C + i; out and g_out B C rows of 2 D floats at the
+ *     row strides ld_out, ld_g >= 2 D; P, g_states, g_memory and the workspace contiguous; all fp32.  Every pair attends over all the
+ *     others of its sentence, padding pairs included: there is no mask.  C == 1: P = 0, the right half of out is zero and nothing flows
+ *     through it.  Non-finite inputs are outside the contract: a NaN or an infinity in a row of scores gives NaN in that row's P.
+ *     Everything is fp32 on v_mfma_f32_16x16x4_f32, without atomics, every sum in an order the shape alone decides, every output cell
+ *     written exactly once by ordinary vector stores: bitwise identical from run to run.  Status codes and the 16-byte alignment of
+ *     workspace are those of the E8 - E12 entries; nothing is allocated inside the library.
+ * ------------------------------------------------------------------------------------------*/
+/* Shapes the kernels take (models/baselines.py:86-112): B >= 0, 1 <= C <= 160 pairs (n <= 13 entities), D a multiple of 4 in 4..1024,
+ * B C <= 2^24.  The fwd / bwd entries also need 16-byte aligned states, memory, out and g_out and row strides that are multiples of 4.
+ * Everything else answers RECON_ERR_UNSUPPORTED and writes nothing; the caller then runs the stock ops. */
+int recon_pair_attention_supported(int64_t B, int32_t C, int32_t D);
+/* Bytes of the workspace (models/baselines.py:86-112).  Forward (backward = 0): none.  Backward (backward = 1): g_S, B C C floats.
+ * 16-byte aligned, any contents; 0 for a shape recon_pair_attention_supported refuses and for B == 0. */
+size_t recon_pair_attention_workspace_bytes(int64_t B, int32_t C, int32_t D, int32_t backward);
+/* Forward (models/baselines.py:86-112), one launch: workgroup (sentence, tile of 16 target pairs) forms its 16 x C scores over D, the
+ * row softmax and its 16 rows of out, both halves (no cat is written).  P [B][C][C] or NULL (no backward will follow: it is not stored).
+ * B == 0: nothing is launched. */
+int recon_pair_attention_fwd(const float* states, int64_t ld_s, const float* memory, int64_t ld_m, int64_t B, int32_t C, int32_t D, float* out,
+                             int64_t ld_out, float* P, recon_stream_t stream);
+/* Backward (models/baselines.py:86-112) from g_out = (g_left | g_ctx), read in place; it destroys nothing (any number of backwards per
+ * forward, the same bits each time).  T[i][j] = g_ctx[i] . states[j], r[i] = sum_j P[i][j] T[i][j], g_S = P (T - r) into the workspace
+ * (first launch, workgroup (sentence, 16-row tile)); then workgroup (sentence, 64 columns of D) writes
+ * g_memory[:, chunk] = g_S states[:, chunk] and g_states[:, chunk] = g_left + (P^T g_ctx[:, chunk] + g_S^T memory[:, chunk]), each
+ * reduction over the pairs ascending.  g_states, g_memory [B][C][D] or NULL (not wanted: its passes are skipped; both NULL: nothing is
+ * launched).  g_states lacks the part through memory: that is recon_pair_transitions_bwd's d_x over g_memory.  B == 0: nothing is
+ * launched.  Two launches. */
+int recon_pair_attention_bwd(const float* states, int64_t ld_s, const float* memory, int64_t ld_m, const float* P, const float* g_out,
+                             int64_t ld_g, int64_t B, int32_t C, int32_t D, float* g_states, float* g_memory, void* workspace,
+                             size_t workspace_bytes, recon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

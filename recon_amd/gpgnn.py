@@ -22,6 +22,37 @@ from .relation_head import relation_logits
 from .line_pool import entity_line_pool
 
 
+def _fused_encode_applies(m, sentence_input, entity_markers, active):
+    we, pe = m.word_embedding, m.pos_embedding
+    plain = all(type(e) is nn.Embedding and e.max_norm is None and not e.sparse and not e.scale_grad_by_freq for e in (we, pe))
+    return (m.fused_sentence_encoder and plain and not we.weight.requires_grad and (not active or (m.packed_word_dropout and m.dropout1.p < 1))
+            and sentence_input.dim() == 2 and entity_markers.dim() == 3 and sentence_input.size(1) == m.max_sent_len
+            and tuple(entity_markers.shape) == (sentence_input.size(0), m.MAX_EDGES_PER_GRAPH, m.max_sent_len))
+
+
+def pair_states(m, sentence_input, entity_markers):
+    """models/models.py:160-183 (and models/baselines.py:62-84, the same lines): one LSTM pass per (sentence, ordered entity pair) of a model
+    with word_embedding, pos_embedding, dropout1 and rnn1; returns [B, C, 2*units1], what `GPGNN.encode` hands to its dropout2 and
+    `ContextAware` to its attention.  `pair_sentence_states` where `fused_sentence_encoder` / `packed_word_dropout` allow, the stock ops
+    otherwise."""
+    B, C = sentence_input.size(0), m.MAX_EDGES_PER_GRAPH
+    active = m.training and m.dropout1.p > 0
+    if _fused_encode_applies(m, sentence_input, entity_markers, active):
+        we = m.word_embedding
+        keep = draw_packed_keep(B * C, m.max_sent_len, we.embedding_dim, m.dropout1.p, sentence_input.device) if active else None
+        return pair_sentence_states(m.rnn1, sentence_input, entity_markers, we.weight, m.pos_embedding.weight, keep,
+                                    pos_padding_idx=m.pos_embedding.padding_idx)
+    expanded = torch.transpose(sentence_input.expand(C, B, m.max_sent_len), 0, 1)
+    word = m.word_embedding(expanded.contiguous().view(-1, m.max_sent_len)).view(B, C, m.max_sent_len, -1)
+    word = m.dropout1(word)
+    pos = m.pos_embedding(entity_markers.contiguous().view(-1, m.max_sent_len)).view(B, C, m.max_sent_len, -1)
+    merged = torch.cat([word, pos], dim=3)
+    merged = merged.view(-1, m.max_sent_len, merged.size(-1))
+    rnn_output, _ = m.rnn1(merged)
+    u = m.p['units1']
+    return torch.cat([rnn_output[:, -1, :u], rnn_output[:, 0, u:]], dim=1).view(B, C, -1)
+
+
 class GPGNN(nn.Module):
     def __init__(self, p, embeddings, max_sent_len, n_out, MAX_EDGES_PER_GRAPH=72):
         super().__init__()
@@ -64,32 +95,9 @@ class GPGNN(nn.Module):
     fused_sentence_encoder = True
     packed_word_dropout = False
 
-    def _fused_encode_applies(self, sentence_input, entity_markers, active):
-        we, pe = self.word_embedding, self.pos_embedding
-        plain = all(type(e) is nn.Embedding and e.max_norm is None and not e.sparse and not e.scale_grad_by_freq for e in (we, pe))
-        return (self.fused_sentence_encoder and plain and not we.weight.requires_grad and (not active or (self.packed_word_dropout and self.dropout1.p < 1))
-                and sentence_input.dim() == 2 and entity_markers.dim() == 3 and sentence_input.size(1) == self.max_sent_len
-                and tuple(entity_markers.shape) == (sentence_input.size(0), self.MAX_EDGES_PER_GRAPH, self.max_sent_len))
-
     def encode(self, sentence_input, entity_markers):
         """models/models.py:160-184: one LSTM pass per (sentence, ordered entity pair); returns [B, C, 2*units1]."""
-        B, C = sentence_input.size(0), self.MAX_EDGES_PER_GRAPH
-        active = self.training and self.dropout1.p > 0
-        if self._fused_encode_applies(sentence_input, entity_markers, active):
-            we = self.word_embedding
-            keep = draw_packed_keep(B * C, self.max_sent_len, we.embedding_dim, self.dropout1.p, sentence_input.device) if active else None
-            return self.dropout2(pair_sentence_states(self.rnn1, sentence_input, entity_markers, we.weight, self.pos_embedding.weight, keep,
-                                                      pos_padding_idx=self.pos_embedding.padding_idx))
-        expanded = torch.transpose(sentence_input.expand(C, B, self.max_sent_len), 0, 1)
-        word = self.word_embedding(expanded.contiguous().view(-1, self.max_sent_len)).view(B, C, self.max_sent_len, -1)
-        word = self.dropout1(word)
-        pos = self.pos_embedding(entity_markers.contiguous().view(-1, self.max_sent_len)).view(B, C, self.max_sent_len, -1)
-        merged = torch.cat([word, pos], dim=3)
-        merged = merged.view(-1, self.max_sent_len, merged.size(-1))
-        rnn_output, _ = self.rnn1(merged)
-        u = self.p['units1']
-        rnn_result = torch.cat([rnn_output[:, -1, :u], rnn_output[:, 0, u:]], dim=1).view(B, C, -1)
-        return self.dropout2(rnn_result)
+        return self.dropout2(pair_states(self, sentence_input, entity_markers))
 
     # fused_transitions: run the L per-hop projections of the pair states as `pair_transitions` (csrc/pair_trans.hip) whenever every
     # projection is a plain nn.Linear; DESIGN.md section 22 says why this is the default it is.
