@@ -1518,6 +1518,58 @@ int recon_pair_attention_bwd(const float* states, int64_t ld_s, const float* mem
                              int64_t ld_g, int64_t B, int32_t C, int32_t D, float* g_states, float* g_memory, void* workspace,
                              size_t workspace_bytes, recon_stream_t stream);
 
+/* --------------------------------------------------------------------------------------------
+ * E17 The sentence convolution and pool of the per-pair baselines CNN and PCNN (csrc/sent_conv.hip; models/baselines.py:237-247 and
+ *     :297-308): the three embedding gathers, the dropout product, cat, transpose, the Conv1d's, the max over the positions, the pooled
+ *     dropout and the activation.  Cin = Dw + 2 Dp:
+ *     x[b][t]         = (keep . word_table[sentence[b][t]] | pos_table_0[positions[b][0][t]] | pos_table_1[positions[b][1][t]])
+ *     conv_i[b][e][t] = bias_i[e] + sum_j sum_c w_i[e][c][j] x[b][t + j - pad_i][c],  x zero outside 0..T-1
+ *     segments NULL (CNN):  pad_i = 0, T_out = T - k_i + 1, pooled[b][i E + e] = max_t conv_i[b][e][t]
+ *     segments [B][3][T] (PCNN): n == 1, k odd, pad = k / 2, T_out = T, pooled[b][s E + e] = max_t conv[b][e][t] segments[b][s][t], a
+ *                           product: a position whose factor is 0 contributes exactly 0
+ *     out[b][:]       = act(pool_keep . pooled[b][:])        [B][n_out E], n_out = n (CNN) or 3 (PCNN); act 0 none, 1 tanh, 2 relu
+ *     An exact tie takes the lowest position.  max_at [B][n_out E] is one byte per output: the winning position, or 255 when the maximum
+ *     was the 0 of a zero-factor position (no gradient).  sentence [B][T] of sentence_bytes 4 or 8 (int32 / int64), positions [B][2][T]
+ *     of position_bytes 1, 4 or 8, both contiguous; word_table [V][Dw], pos_table_0/1 [P][Dp], weights[i] [E][Cin][k_i] (nn.Conv1d's
+ *     layout), biases[i] [E], ks[i] = k_i: `weights`, `biases`, `ks` and the g_ arrays are HOST arrays of n entries.  keep: at most one
+ *     of keep_bits (uint32 [B][T][ceil(Dw / 32)], factor = keep_scale where bit c % 32 of word c / 32 is set, else 0) and keep_factors
+ *     (fp32 [B][T][Dw]); pool_keep fp32 [B][n_out E] or NULL.  An id outside its table is never used as an address: row 0 is read in its
+ *     place and status[0] (device int32, zeroed by the caller) is set to 1.  x, its transpose, the convolution outputs and their masked
+ *     copies are never written.  fp32 on v_mfma_f32_16x16x4_f32 (forward) and the VALU (backward), no atomics, every sum in an order the
+ *     shape alone decides, every output cell written exactly once by ordinary vector stores.  Status codes and the 16-byte alignment of
+ *     workspace are those of the E8 - E16 entries; nothing is allocated inside the library.
+ * ------------------------------------------------------------------------------------------*/
+/* Shapes the kernels take (models/baselines.py:237-247, :297-308): 0 <= B <= 2^24, 1 <= T <= 128, Cin = Dw + 2 Dp <= 320, E <= 1024,
+ * 1 <= n <= 4 weights of 1 <= k_i <= 9, 2 P Dp <= 4096 and 2 T Dp <= 4096 (the position-table slabs of the backward).  T_out <= 128 is
+ * within the byte's 255.  RECON_ERR_INVALID shapes (k_i > T without segments; with segments n != 1 or an even k) answer 0 as well. */
+int recon_sent_conv_supported(int64_t B, int32_t T, int32_t Dw, int32_t Dp, int32_t P, int32_t E, const int32_t* ks, int32_t n,
+                              int32_t segmented);
+/* Bytes of the workspace (models/baselines.py:237-247, :297-308).  Forward (backward = 0): the weights K-major, sum_i
+ * ceil(Cin / 100 chunks) k_i pitch (E rounded up to 16) floats.  Backward: G slabs of (d_w | d_bias), G = min(32, B, 2^24 floats / slab),
+ * and min(256, B) slabs [2][P][Dp] of the position tables: bounded independently of B.  0 for a refused shape and for B == 0. */
+size_t recon_sent_conv_workspace_bytes(int64_t B, int32_t T, int32_t Dw, int32_t Dp, int32_t P, int32_t E, const int32_t* ks, int32_t n,
+                                       int32_t segmented, int32_t backward);
+/* Forward (models/baselines.py:237-247, :297-308), two launches: the weights K-major into the workspace; then workgroup (rows, 64 output
+ * channels, weight) stages its rows' gathered x in LDS, multiplies and pools.  max_at may be NULL (no backward will follow).  B == 0:
+ * nothing is launched. */
+int recon_sent_conv_fwd(const void* sentence, int32_t sentence_bytes, const void* positions, int32_t position_bytes, const float* word_table,
+                        int32_t V, const float* pos_table_0, const float* pos_table_1, int32_t P, const void* keep_bits, float keep_scale,
+                        const float* keep_factors, const float* segments, const void* const* weights, const void* const* biases,
+                        const int32_t* ks, int32_t n, const float* pool_keep, int32_t activation, int64_t B, int32_t T, int32_t Dw, int32_t Dp,
+                        int32_t E, float* out, void* max_at, int32_t* status, void* workspace, size_t workspace_bytes, recon_stream_t stream);
+/* Backward (models/baselines.py:237-247, :297-308) from g_out [B][n_out E], out and max_at; it destroys nothing (any number of backwards
+ * per forward, the same bits each time).  g = g_out act'(out) pool_keep f, f the segment factor at the winning position; x is gathered
+ * again.  d_w_i[e][c][j] = sum_b g x[b][t* + j - pad][c], d_bias_i[e] = sum_b g, rows ascending inside a group, groups ascending;
+ * d_pos_table_h[p] = sum over (b, t) with positions[b][h][t] = p of d_x[b][t][its columns], row pos_padding_idx (-1: none) left zero.
+ * Any g_ pointer (or entry of g_weights / g_biases, or either array) may be NULL: not wanted; nothing wanted: nothing is launched.  At
+ * most three launches.  B == 0: zeros in every wanted gradient. */
+int recon_sent_conv_bwd(const void* sentence, int32_t sentence_bytes, const void* positions, int32_t position_bytes, const float* word_table,
+                        int32_t V, const float* pos_table_0, const float* pos_table_1, int32_t P, const void* keep_bits, float keep_scale,
+                        const float* keep_factors, const float* segments, const void* const* weights, const int32_t* ks, int32_t n,
+                        const float* pool_keep, int32_t activation, int64_t B, int32_t T, int32_t Dw, int32_t Dp, int32_t E, const float* out,
+                        const void* max_at, const float* g_out, int32_t pos_padding_idx, float* g_pos_table_0, float* g_pos_table_1,
+                        void* const* g_weights, void* const* g_biases, void* workspace, size_t workspace_bytes, recon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

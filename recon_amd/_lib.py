@@ -368,6 +368,17 @@ SYMBOLS = [
                                           C.c_void_p]),
     ("recon_pair_attention_bwd", C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                           c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("recon_sent_conv_supported", C.c_int, [C.c_int64] + [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.c_int32, C.c_int32]),
+    ("recon_sent_conv_workspace_bytes", C.c_size_t, [C.c_int64] + [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32]),
+    ("recon_sent_conv_fwd", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, c_f32p, C.c_int32, c_f32p, c_f32p, C.c_int32, C.c_void_p,
+                                     C.c_float, c_f32p, c_f32p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32,
+                                     c_f32p, C.c_int32, C.c_int64] + [C.c_int32] * 4 + [c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                                                       C.c_void_p]),
+    ("recon_sent_conv_bwd", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, c_f32p, C.c_int32, c_f32p, c_f32p, C.c_int32, C.c_void_p,
+                                     C.c_float, c_f32p, c_f32p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, c_f32p, C.c_int32,
+                                     C.c_int64] + [C.c_int32] * 4 + [c_f32p, C.c_void_p, c_f32p, C.c_int32, c_f32p, c_f32p,
+                                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t,
+                                                                     C.c_void_p]),
 ]
 
 _lib = None
