@@ -1480,6 +1480,22 @@ int recon_stage_b_slice(const int32_t* sentences, const int8_t* markers, const i
 int recon_stage_b_collect(const int64_t* labels, const int64_t* predicted, const float* confidence, const int64_t* rows, int64_t M,
                           int64_t num_pairs, int64_t ignore_index, int64_t* state, int64_t capacity, int64_t* out_pair,
                           int64_t* out_predicted, int64_t* out_gold, float* out_confidence, recon_stream_t stream);
+/* 1 when a batch of `count` rows of the per-pair baselines' datasets (one entity pair per row; marker_rows 1: LSTM's markers [N][sent_len],
+ * 2: the relative positions [N][2][sent_len] of CNN and PCNN) runs in recon_pair_slice: every extent at least 1 and the largest output —
+ * the mask [count][3][sent_len]; the bound is the same without one — below 2^31 - 4096 cells.  The reference's batch is 50 x 36. */
+int recon_pair_slice_supported(int64_t count, int64_t marker_rows, int64_t sent_len);
+/* train.py:247-249 with the casts of :301-309 (again :333-335, :387-393) over what parsing/legacy_sp_models.py:67-97 and :503-603 return, one launch of
+ * k_sb_slice's scheme: batch row b is dataset row r(b) = order[start + b] (order NULL: start + b), CLAMPED into [0, N) as in
+ * recon_stage_b_slice, whose range rules hold.  Reads sentences int32 [N][sent_len], markers int8 [N][marker_rows][sent_len], labels int16
+ * [N] and, with pcnn_mask or not at all, segment_bits uint8 [N][sent_len]: bit s of byte [n][t] is the reference's pcnn_mask[n][s][t].
+ * Writes sentence_input [count][sent_len] and entity_markers [count][marker_rows][sent_len] of index_bytes = 4 or 8, sign-extended,
+ * pcnn_mask fp32 [count][3][sent_len] = ((segment_bits[r(b)][t] >> s) & 1) as 0.0f / 1.0f, labels_out int64 [count] and rows_out int64
+ * [count] = r(b).  The mask follows `order` like every other array (train.py:304 takes it from the unshuffled rows).  Every cell is
+ * written exactly once, as runs of 16-byte stores (element stores at an unaligned array's two ends). */
+int recon_pair_slice(const int32_t* sentences, const int8_t* markers, const int16_t* labels, const uint8_t* segment_bits, int64_t N,
+                     int64_t marker_rows, int64_t sent_len, const int64_t* order, int64_t order_len, int64_t start, int64_t count,
+                     int32_t index_bytes, void* sentence_input, void* entity_markers, float* pcnn_mask, int64_t* labels_out, int64_t* rows_out,
+                     recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * E16 ContextAware's attention over ghosts (csrc/pair_attn.hip): the per-sentence self-attention over the pair states with the diagonal

@@ -14,4 +14,5 @@ from .line_pool import entity_line_pool  # noqa: E402,F401
 from .objective import RelationMetrics, relation_objective  # noqa: E402,F401
 from .context_batch import ContextBatcher, ContextTables, StageBBatch  # noqa: E402,F401
 from .stage_b import EpochRows, StageBData, StageBSlice, run_epoch  # noqa: E402,F401
+from .pair_data import PairData, PairSlice  # noqa: E402,F401
 from .baselines import CNN, LSTM, PCNN, ContextAware  # noqa: E402,F401

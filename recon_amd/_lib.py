@@ -362,6 +362,9 @@ SYMBOLS = [
                                       C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, c_i64p, c_i32p, c_i64p, c_i32p, c_i64p, C.c_void_p]),
     ("recon_stage_b_collect", C.c_int, [c_i64p, c_i64p, c_f32p, c_i64p, C.c_int64, C.c_int64, C.c_int64, c_i64p, C.c_int64, c_i64p, c_i64p, c_i64p,
                                         c_f32p, C.c_void_p]),
+    ("recon_pair_slice_supported", C.c_int, [C.c_int64] * 3),
+    ("recon_pair_slice", C.c_int, [c_i32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, c_i64p, C.c_int64, C.c_int64,
+                                   C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, c_f32p, c_i64p, c_i64p, C.c_void_p]),
     ("recon_pair_attention_supported", C.c_int, [C.c_int64] + [C.c_int32] * 2),
     ("recon_pair_attention_workspace_bytes", C.c_size_t, [C.c_int64] + [C.c_int32] * 3),
     ("recon_pair_attention_fwd", C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_f32p, C.c_int64, c_f32p,

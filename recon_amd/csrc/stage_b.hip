@@ -3,15 +3,19 @@
 //                          dataset's compact arrays, widened to the dtypes the model and the objective take;
 //   recon_stage_b_collect  test.py:285-292 and the indices of :300-302: the rows whose label is not ignored, in row order, appended behind
 //                          what earlier batches of the pass left.
-// Selection and copying only: every output equals the reference's array to the value, `confidence` to the bit.
+//   recon_pair_slice       the same cut for the per-pair baselines' datasets (recon_amd/pair_data.py; parsing/legacy_sp_models.py:67-97,
+//                          :503-603, train.py:247-249, :301-309): one entity pair per row, and PCNN's segment mask unpacked from one byte per token.
+// Selection and copying only: every output equals the reference's array to the value, `confidence` and the mask to the bit.
 //
-// k_sb_slice: ONE launch for all seven outputs.  Each output is a flat run of 16-byte vectors, one per thread, the way k_cb_fill
-//   (ctx_batch.hip) writes its arrays: a wave's store instruction covers 1 KiB of consecutive bytes whatever the row width, and a base that
+// k_sb_slice<kSegments, kPlanes>: ONE launch for all outputs (seven of a StageBSlice: <7, false>; five of a PairSlice: <5, true>).
+//   Each output is a flat run of 16-byte vectors, one per thread, the way k_cb_fill (ctx_batch.hip) writes its arrays: a wave's store instruction covers 1 KiB of consecutive bytes whatever the row width, and a base that
 //   is not 16-byte aligned shifts the vector grid, so that only an array's first and last vector fall back to element stores.  Every cell
 //   is written exactly once (the host hands torch.empty).  The dataset's row of batch row b is order[start + b] (start + b without an
 //   order) CLAMPED into [0, N): the host validates an order where it enters, and the clamp keeps whatever it reads from ever becoming an
 //   address.  Sources are int8, int16 or int32 and are sign-extended to the output's 4 or 8 bytes.  Flat output indices are int32
 //   (recon_stage_b_supported refuses an output of 2^31 - 4096 cells or more); a source offset is 64-bit, the dataset may be larger.  No atomics.
+//   kPlanes adds one kind of segment, a bit-plane source with a float32 destination: the dataset row is `width / 3` bytes, and output cell
+//   j of a batch row is bit j / T of byte j % T as 0.0f or 1.0f (T = width / 3): the [3][T] mask of PCNN from one byte per token.
 // k_sb_collect: ONE workgroup of 1024 threads walks the M rows in chunks of 1024, in order.  Within a chunk a ballot gives a kept row its
 //   rank in its wave, a scan over the 16 wave counts its rank in the chunk: the compaction is stable.  The cursor is an int64 in the
 //   caller's device state, read at the start and stored once at the end with plain loads and stores — launches on one stream are ordered,
@@ -25,9 +29,11 @@ namespace {
 constexpr int kSbThreads = 256;
 constexpr int kSbCollectThreads = 1024;
 constexpr int kSbSegments = 7;
+constexpr int kPsSegments = 5;
 constexpr int64_t kSbMaxCells = (int64_t{1} << 31) - 4096;      // of the largest output: a last vector's past-the-end indices still fit an int32
 
 enum { SB_SRC_I8 = 1, SB_SRC_I16 = 2, SB_SRC_I32 = 4, SB_SRC_ROW = 0 };      // bytes of a source element; 0: the value is the dataset row itself
+enum { SB_SRC_PLANES = 3 };                                                  // k_sb_slice<., true> only: uint8 [N][width / 3], three bit planes
 
 struct SbSegment {
     void* dst;              // nullptr: the dataset has no such array
@@ -39,13 +45,17 @@ struct SbSegment {
     int32_t src_kind;
     int32_t block_end;      // first block behind this segment's
 };
-struct SbSlice {
-    SbSegment seg[kSbSegments];
+template <int kSegments>
+struct SbSliceT {
+    SbSegment seg[kSegments];
     const int64_t* order;   // nullptr: the identity
     int64_t start, N;
 };
+typedef SbSliceT<kSbSegments> SbSlice;
+typedef SbSliceT<kPsSegments> PsSlice;
 
-__device__ __forceinline__ int64_t sb_row(const SbSlice& s, int32_t b) {
+template <typename S>
+__device__ __forceinline__ int64_t sb_row(const S& s, int32_t b) {
     const int64_t r = s.order ? s.order[s.start + b] : s.start + b;
     return r < 0 ? 0 : (r >= s.N ? s.N - 1 : r);
 }
@@ -60,9 +70,9 @@ __device__ __forceinline__ int64_t sb_load(const SbSegment& g, int64_t row, int3
     }
 }
 
-// vector v of the segment's flat output: cells [v VE - shift, v VE - shift + VE)
-template <typename OT>
-__device__ __forceinline__ void sb_slice_vec(const SbSlice& s, const SbSegment& g, int32_t v) {
+// vector v of the segment's flat output: cells [v VE - shift, v VE - shift + VE); kPlanes: the segment is SB_SRC_PLANES
+template <typename OT, bool kPlanes, typename S>
+__device__ __forceinline__ void sb_slice_vec(const S& s, const SbSegment& g, int32_t v) {
     constexpr int VE = 16 / sizeof(OT);
     typedef OT vec_t __attribute__((ext_vector_type(VE)));
     OT* __restrict__ out = static_cast<OT*>(g.dst);
@@ -73,15 +83,27 @@ __device__ __forceinline__ void sb_slice_vec(const SbSlice& s, const SbSegment& 
     int32_t b = fa / g.width;
     int32_t j = fa - b * g.width;
     int64_t row = sb_row(s, b);
+    const int32_t T = kPlanes ? g.width / 3 : 1;                      // planes: bytes per dataset row,
+    int32_t p = kPlanes ? j / T : 0;                                  // the plane of cell j
+    int32_t t = kPlanes ? j - p * T : 0;                              // and its token
     OT val[VE];
 #pragma unroll
     for (int e = 0; e < VE; ++e) {
         const int32_t f = f0 + e;
         val[e] = 0;
         if (f < 0 || f >= g.total) continue;
-        val[e] = static_cast<OT>(sb_load(g, row, j));
+        if (kPlanes) {
+            val[e] = static_cast<OT>((static_cast<const uint8_t*>(g.src)[row * T + t] >> p) & 1);
+            if (++t == T) {
+                t = 0;
+                ++p;
+            }
+        } else {
+            val[e] = static_cast<OT>(sb_load(g, row, j));
+        }
         if (++j == g.width) {
             j = 0;
+            p = 0;
             ++b;
             if (f + 1 < g.total && e + 1 < VE) row = sb_row(s, b);
         }
@@ -98,16 +120,18 @@ __device__ __forceinline__ void sb_slice_vec(const SbSlice& s, const SbSegment& 
     }
 }
 
-__global__ void __launch_bounds__(kSbThreads) k_sb_slice(const SbSlice s) {
+template <int kSegments, bool kPlanes>
+__global__ void __launch_bounds__(kSbThreads) k_sb_slice(const SbSliceT<kSegments> s) {
     const int32_t blk = static_cast<int32_t>(blockIdx.x);
     int32_t first = 0;
 #pragma unroll
-    for (int i = 0; i < kSbSegments; ++i) {
+    for (int i = 0; i < kSegments; ++i) {
         const SbSegment& g = s.seg[i];
         if (blk < g.block_end) {
             const int32_t v = (blk - first) * kSbThreads + static_cast<int32_t>(threadIdx.x);
-            if (g.dst_bytes == 8) sb_slice_vec<int64_t>(s, g, v);
-            else sb_slice_vec<int32_t>(s, g, v);
+            if (kPlanes && g.src_kind == SB_SRC_PLANES) sb_slice_vec<float, true>(s, g, v);
+            else if (g.dst_bytes == 8) sb_slice_vec<int64_t, false>(s, g, v);
+            else sb_slice_vec<int32_t, false>(s, g, v);
             return;
         }
         first = g.block_end;
@@ -165,6 +189,11 @@ bool sb_shape_ok(int64_t count, int64_t C, int64_t T) {
     return count * (C * (T > 2 ? T : 2)) < kSbMaxCells;              // the widest rows: markers C T, the id pairs 2 C
 }
 
+bool ps_shape_ok(int64_t count, int64_t marker_rows, int64_t T) {
+    if (count < 1 || (marker_rows != 1 && marker_rows != 2) || T < 1 || T >= kSbMaxCells / 3 || count >= kSbMaxCells) return false;
+    return count * (3 * T) < kSbMaxCells;                            // the widest rows: the mask's 3 T
+}
+
 // one output of the slice; returns the segment's blocks
 int32_t sb_segment(SbSegment* g, void* dst, const void* src, int64_t width, int64_t count, int32_t dst_bytes, int32_t src_kind, int32_t first_block) {
     g->dst = dst;
@@ -216,7 +245,41 @@ extern "C" int recon_stage_b_slice(const int32_t* sentences, const int8_t* marke
     blocks += sb_segment(&s.seg[4], surface_ids_out, surface_ids, 2 * num_pairs, count, 4, SB_SRC_I32, blocks);
     blocks += sb_segment(&s.seg[5], num_entities_out, num_entities, 1, count, 4, SB_SRC_I32, blocks);
     blocks += sb_segment(&s.seg[6], rows_out, nullptr, 1, count, 8, SB_SRC_ROW, blocks);
-    hipLaunchKernelGGL(k_sb_slice, dim3(static_cast<unsigned>(blocks)), dim3(kSbThreads), 0, as_stream(stream), s);
+    hipLaunchKernelGGL((k_sb_slice<kSbSegments, false>), dim3(static_cast<unsigned>(blocks)), dim3(kSbThreads), 0, as_stream(stream), s);
+    RECON_CHECK_LAUNCH();
+    return RECON_OK;
+}
+
+extern "C" int recon_pair_slice_supported(int64_t count, int64_t marker_rows, int64_t sent_len) {
+    return recon::ps_shape_ok(count, marker_rows, sent_len) ? 1 : 0;
+}
+
+extern "C" int recon_pair_slice(const int32_t* sentences, const int8_t* markers, const int16_t* labels, const uint8_t* segment_bits, int64_t N,
+                                int64_t marker_rows, int64_t sent_len, const int64_t* order, int64_t order_len, int64_t start, int64_t count,
+                                int32_t index_bytes, void* sentence_input, void* entity_markers, float* pcnn_mask, int64_t* labels_out,
+                                int64_t* rows_out, recon_stream_t stream) {
+    using namespace recon;
+    if (!sentences || !markers || !labels || !sentence_input || !entity_markers || !labels_out || !rows_out) return RECON_ERR_INVALID;
+    if ((segment_bits == nullptr) != (pcnn_mask == nullptr)) return RECON_ERR_INVALID;
+    if (N < 1 || (marker_rows != 1 && marker_rows != 2) || sent_len < 1 || count < 1 || start < 0 || (index_bytes != 4 && index_bytes != 8))
+        return RECON_ERR_INVALID;
+    if (order ? (order_len < 0 || start > order_len || count > order_len - start) : (start > N || count > N - start)) return RECON_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(sentence_input) | reinterpret_cast<uintptr_t>(entity_markers)) % static_cast<uintptr_t>(index_bytes))
+        return RECON_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(labels_out) | reinterpret_cast<uintptr_t>(rows_out)) % 8u || reinterpret_cast<uintptr_t>(pcnn_mask) % 4u)
+        return RECON_ERR_INVALID;
+    if (!ps_shape_ok(count, marker_rows, sent_len)) return RECON_ERR_UNSUPPORTED;
+    PsSlice s;
+    s.order = order;
+    s.start = start;
+    s.N = N;
+    int32_t blocks = 0;
+    blocks += sb_segment(&s.seg[0], pcnn_mask, segment_bits, 3 * sent_len, count, 4, SB_SRC_PLANES, blocks);
+    blocks += sb_segment(&s.seg[1], entity_markers, markers, marker_rows * sent_len, count, index_bytes, SB_SRC_I8, blocks);
+    blocks += sb_segment(&s.seg[2], sentence_input, sentences, sent_len, count, index_bytes, SB_SRC_I32, blocks);
+    blocks += sb_segment(&s.seg[3], labels_out, labels, 1, count, 8, SB_SRC_I16, blocks);
+    blocks += sb_segment(&s.seg[4], rows_out, nullptr, 1, count, 8, SB_SRC_ROW, blocks);
+    hipLaunchKernelGGL((k_sb_slice<kPsSegments, true>), dim3(static_cast<unsigned>(blocks)), dim3(kSbThreads), 0, as_stream(stream), s);
     RECON_CHECK_LAUNCH();
     return RECON_OK;
 }

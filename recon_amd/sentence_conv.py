@@ -22,11 +22,13 @@ fp32 MFMA and pool), at most three backward, no atomics, bitwise reproducible.  
 masked copy is written: the op saves references to its inputs, out and one position byte per output (255: the maximum was the 0 of a
 zero-factor position).  Differentiable in both position tables, every weight and every bias; an input that does not require a
 gradient gets none and costs nothing.  The backward destroys nothing.  An id outside its table raises ValueError (one host read of a
-status word per forward, a synchronisation of the calling stream; the word is the stream's own).  Otherwise — CPU tensors, another
-dtype, a word_table that requires a gradient, a shape the library refuses, a backward under create_graph — the call runs `_chain`, the
-reference's lines as torch ops.  DESIGN.md section 31.
+status word per forward, a synchronisation of the calling stream; the word is the stream's own; inside `ids_prechecked()` one read where
+the context ends instead).  Otherwise — CPU tensors, another dtype, a word_table that requires a gradient, a shape the library refuses,
+a backward under create_graph — the call runs `_chain`, the reference's lines as torch ops.  DESIGN.md sections 31 and 32.
 """
+import contextlib
 import ctypes
+import threading
 
 import torch
 import torch.nn.functional as F
@@ -76,6 +78,48 @@ def _status(dev, stream):
     return s
 
 
+def _outside(V, P):
+    return ValueError("sentence_conv_pool: a word id outside [0, %d) or a position id outside [0, %d)" % (V, P))
+
+
+_PRECHECKED = threading.local()
+
+
+@contextlib.contextmanager
+def ids_prechecked():
+    """For a loop whose ids were checked on the host beforehand (`PairData.check_model`; `run_epoch` over a `PairData` enters it): inside,
+    `sentence_conv_pool` launches exactly as outside — an id outside its table still reads row 0 and still sets the stream's status word —
+    but the forward does not read the word, so it does not stall the host.  On leaving, the word of every (device, stream) the
+    context's forwards used is read once; a set word is cleared and raises the ValueError the forward would have raised.  Thread-local;
+    a context inside another leaves the reading to the outer one.  When an exception leaves the context, set words are cleared and the
+    exception goes on."""
+    if getattr(_PRECHECKED, "used", None) is not None:
+        yield
+        return
+    used = _PRECHECKED.used = {}
+    try:
+        yield
+    except BaseException:
+        _PRECHECKED.used = None
+        _read_words(used)
+        raise
+    _PRECHECKED.used = None
+    bad = _read_words(used)
+    if bad:
+        raise _outside(*bad[0])
+
+
+def _read_words(used):
+    """One read per word; clears the set ones and returns their (V, P)."""
+    bad = []
+    for status, stream, V, P in used.values():
+        with torch.cuda.stream(stream):                               # the read and the clear in the forwards' own order
+            if int(status):
+                status.zero_()
+                bad.append((V, P))
+    return bad
+
+
 def _ks(weights):
     return (ctypes.c_int32 * len(weights))(*[w.shape[2] for w in weights])
 
@@ -105,9 +149,14 @@ class _SentenceConvPool(torch.autograd.Function):
                                                _lib.ptr_array([b.detach() for b in biases]), ks, n, _lib.ptr(pool_keep), ACTIVATIONS[activation],
                                                B, T, Dw, Dp, E, out.data_ptr(), _lib.ptr(at), status.data_ptr(), ws.data_ptr(), ws.numel(),
                                                _lib.current_stream()), "recon_sent_conv_fwd")
-        if B and int(status):
+        used = getattr(_PRECHECKED, "used", None)
+        if used is not None:                                              # ids_prechecked(): the word is read where the context ends
+            key = (dev, _lib.current_stream())
+            if key not in used:
+                used[key] = (status, torch.cuda.current_stream(dev), V, P)
+        elif B and int(status):
             status.zero_()
-            raise ValueError("sentence_conv_pool: a word id outside [0, %d) or a position id outside [0, %d)" % (V, P))
+            raise _outside(V, P)
         ctx.set_materialize_grads(False)
         if wants:
             ctx.save_for_backward(sentence, positions, word_table, pos_table_0, pos_table_1, segments, keep_bits, keep_f, pool_keep, out, at, *params)

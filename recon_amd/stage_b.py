@@ -36,6 +36,7 @@ import torch
 
 from . import _lib
 from .objective import relation_objective
+from .sentence_conv import ids_prechecked
 
 _KERNELS = True                 # False: the torch path on every device
 _ARRAYS = ("sentences", "markers", "labels", "num_entities", "entity_indices", "surface_ids")
@@ -49,14 +50,14 @@ def _new(shape, dtype, device):
     return torch.empty(shape, dtype=dtype, device=device)
 
 
-def _compact(a, dtype, name):
+def _compact(a, dtype, name, owner="StageBData"):
     """`a` (numpy array or tensor of integers) as a CPU tensor of the compact dtype; ValueError for a value the dtype cannot hold."""
     t = a.detach().cpu() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
     if t.dtype == torch.bool or t.is_floating_point() or t.is_complex():
-        raise TypeError("StageBData: %s must be an integer array, got %s" % (name, t.dtype))
+        raise TypeError("%s: %s must be an integer array, got %s" % (owner, name, t.dtype))
     c = t.to(dtype)
     if c.dtype != t.dtype and not torch.equal(c.to(t.dtype), t):
-        raise ValueError("StageBData: %s holds a value that %s cannot hold" % (name, dtype))
+        raise ValueError("%s: %s holds a value that %s cannot hold" % (owner, name, dtype))
     return c.contiguous()
 
 
@@ -241,7 +242,11 @@ def run_epoch(model, data, batch_size, *, order=None, batcher=None, optimizer=No
     metrics=metrics)`; with an optimizer (any torch.optim.Optimizer) `zero_grad()` in front and `loss.backward()` / `step()` behind, in the
     reference's order (train.py:245, :313-315), without one everything under `torch.no_grad()`; with `rows` (an EpochRows)
     `rows.append`.  order: int64 on the data's device, at least (N // batch_size) * batch_size long, validated here with one min/max read.
-    The model's train / eval mode is the caller's.  Returns nothing: `metrics` and `rows` hold the results."""
+    The model's train / eval mode is the caller's.  Returns nothing: `metrics` and `rows` hold the results.
+
+    Over a `PairData` (recon_amd/pair_data.py: the per-pair baselines LSTM, CNN and PCNN) the model is called as
+    `model(*sl.model_args())`, there is no batcher (ValueError), and the ids are checked once, not once per forward: `data.check_model(model)`
+    on the host in front, and the loop inside `sentence_conv.ids_prechecked()`, whose one read of the status word comes behind the loop."""
     if not isinstance(batch_size, int) or batch_size < 1:
         raise ValueError("run_epoch: batch_size must be an integer >= 1, got %r" % (batch_size,))
     iterations = data.N // batch_size
@@ -251,18 +256,27 @@ def run_epoch(model, data, batch_size, *, order=None, batcher=None, optimizer=No
         if order.numel() < iterations * batch_size:
             raise ValueError("run_epoch: order holds %d rows, %d iterations of %d need %d" % (order.numel(), iterations, batch_size, iterations * batch_size))
         _check_order(order, data.N)
-    if batcher is not None and (data.entity_indices is None or data.surface_ids is None):
+    check_model = getattr(data, "check_model", None)                    # a PairData: one entity pair per row
+    if check_model is not None:
+        if batcher is not None:
+            raise ValueError("run_epoch: a batcher belongs to the per-sentence layout of a StageBData, not to a PairData")
+        check_model(model)
+    elif batcher is not None and (data.entity_indices is None or data.surface_ids is None):
         raise ValueError("run_epoch: a batcher needs a dataset with entity_indices and surface_ids")
-    for i in range(iterations):
-        sl = data.take(order, i * batch_size, batch_size, index_dtype)
-        with contextlib.nullcontext() if optimizer is not None else torch.no_grad():
-            if optimizer is not None:
-                optimizer.zero_grad()
-            extra = batcher.batch(sl.entity_indices, sl.surface_ids, index_dtype).model_args() if batcher is not None else ()
-            logits = model(sl.sentence_input, sl.entity_markers, sl.num_entities, *extra)
-            res = relation_objective(logits, sl.labels, ignore_index=0, empty_label=empty_label, metrics=metrics)
-            if optimizer is not None:
-                res.loss.backward()
-                optimizer.step()
-        if rows is not None:
-            rows.append(res, sl)
+    with ids_prechecked() if check_model is not None else contextlib.nullcontext():
+        for i in range(iterations):
+            sl = data.take(order, i * batch_size, batch_size, index_dtype)
+            with contextlib.nullcontext() if optimizer is not None else torch.no_grad():
+                if optimizer is not None:
+                    optimizer.zero_grad()
+                if hasattr(sl, "model_args"):
+                    logits = model(*sl.model_args())
+                else:
+                    extra = batcher.batch(sl.entity_indices, sl.surface_ids, index_dtype).model_args() if batcher is not None else ()
+                    logits = model(sl.sentence_input, sl.entity_markers, sl.num_entities, *extra)
+                res = relation_objective(logits, sl.labels, ignore_index=0, empty_label=empty_label, metrics=metrics)
+                if optimizer is not None:
+                    res.loss.backward()
+                    optimizer.step()
+            if rows is not None:
+                rows.append(res, sl)
