@@ -601,6 +601,38 @@ size_t recon_gcn_bwd_partial_floats(int32_t B, int32_t n, int32_t in_features, i
 int recon_gcn_bwd(const recon_gcn_bwd_args* args, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * P5 / K6 over a RAGGED batch in float32 (BASELINE.json configs[4]: graphs of up to 256 nodes, every one its own size): graph b owns
+ *     node rows node_ptr[b] .. node_ptr[b+1] of x / support / out (total_rows = node_ptr[B] rows in all, n_max the largest graph) and a
+ *     dense n_b x n_b adjacency at adj + adj_ptr[b] (elements).  The layer of models/layers.py:57-63 applied to every graph: x @ W over
+ *     all rows at once (the GEMMs of recon_gcn_fwd; w_split / gs_split as there, sized by recon_gcn_split_bytes(in, out) and
+ *     recon_gcn_bwd_split_bytes(1, total_rows, out), or NULL), the aggregate per graph on v_mfma_f32_16x16x4_f32.
+ *     x: rows of in_features floats at a stride of ldx >= in_features floats; adj, support, out, grad_out and the gradients are dense.
+ *     tiles [n_tiles][2] int32, device: the work list (graph b, row tile i) for b = 0 .. B-1, i = 0 .. ceil(n_b / 32) - 1, in any
+ *     order; a pair that names no graph or no rows of its graph is skipped.
+ *     Plain arguments, no struct.  All sizes, pointers and counts are checked before anything is launched: RECON_ERR_INVALID for a null
+ *     required pointer, in_features / out_features <= 0, ldx < in_features, sizes that no batch has (B == 0 with rows, n_max > total_rows,
+ *     total_rows > B * n_max) or an n_tiles outside B .. (total_rows + 31 B) / 32; RECON_ERR_UNSUPPORTED for B > 65535, total_rows beyond
+ *     int32 or n_max > 65535 * 32.  B == 0 launches nothing.  No atomics: results are bit-reproducible.
+ * ------------------------------------------------------------------------------------------*/
+/* The size checks alone (models/layers.py:57-63 per graph): RECON_OK where the two launchers below would take these sizes. */
+int recon_gcn_ragged_supported(int32_t B, int64_t total_rows, int32_t n_max, int32_t in_features, int32_t out_features);
+/* Forward, models/layers.py:57-63 per graph: support = x @ W (scratch / saved), out = relu(adj_b @ support_b + bias); bias may be NULL. */
+int recon_gcn_ragged_fwd(const float* x, int64_t ldx, const float* adj, const float* weight, const float* bias, const int32_t* node_ptr,
+                         const int64_t* adj_ptr, const int32_t* tiles, int32_t n_tiles, int32_t B, int64_t total_rows, int32_t n_max,
+                         int32_t in_features, int32_t out_features, float* support, float* out, void* w_split, recon_stream_t stream);
+/* Floats of the backward's `partial` (autograd's backward of models/layers.py:57-63): the weight gradient's split-K partials + [B, out]
+ * per-graph column sums for the bias gradient. */
+size_t recon_gcn_ragged_bwd_partial_floats(int32_t B, int64_t total_rows, int32_t in_features, int32_t out_features);
+/* Backward (what autograd derives from models/layers.py:57-63, per graph): g_support [total_rows, out] workspace = adj_b^T @ (grad_out *
+ * (out > 0)); g_x [total_rows, in], g_adj (laid out as adj; reads support), g_weight [in, out], g_bias [out]: each optional (NULL).
+ * g_bias is the per-graph column sums of the masked gradient added in graph order.  support, out, w_split: as the forward left them. */
+int recon_gcn_ragged_bwd(const float* x, int64_t ldx, const float* adj, const float* weight, const int32_t* node_ptr, const int64_t* adj_ptr,
+                         const int32_t* tiles, int32_t n_tiles, int32_t B, int64_t total_rows, int32_t n_max, int32_t in_features,
+                         int32_t out_features, const float* support, const float* out, const void* w_split, const float* grad_out,
+                         float* g_support, float* partial, float* g_x, float* g_adj, float* g_weight, float* g_bias, void* gs_split,
+                         recon_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * P5 / K6 in bfloat16 (BASELINE.json configs[2]: "bf16 + MFMA on W-projection"): the same layer on bfloat16 tensors — bf16
  *     storage, fp32 accumulation, x @ W / g_support @ W^T / x^T @ g_support on v_mfma_f32_16x16x32_bf16 (csrc/gemm_b16.hip).
  *     Activations carry a row stride that is a multiple of 8 elements (16 bytes) and at least the feature count rounded up

@@ -268,6 +268,13 @@ SYMBOLS = [
     ("recon_gcn_bwd_partial_floats", C.c_size_t, [C.c_int32] * 4),
     ("recon_gcn_bwd_split_bytes", C.c_size_t, [C.c_int32] * 3),
     ("recon_gcn_bwd", C.c_int, [C.POINTER(GcnBwdArgs), C.c_void_p]),
+    ("recon_gcn_ragged_supported", C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    ("recon_gcn_ragged_fwd", C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, c_i32p, c_i64p, c_i32p, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                                       C.c_int32, C.c_int32, c_f32p, c_f32p, C.c_void_p, C.c_void_p]),
+    ("recon_gcn_ragged_bwd_partial_floats", C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    ("recon_gcn_ragged_bwd", C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, c_i32p, c_i64p, c_i32p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                       C.c_int32, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p,
+                                       C.c_void_p]),
     ("recon_gcn_b16_planes_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
     ("recon_gcn_b16_fwd", C.c_int, [C.POINTER(GcnB16Args), C.c_void_p]),
     ("recon_gcn_b16_bwd_partial_floats", C.c_size_t, [C.c_int32] * 4),

@@ -9,7 +9,11 @@ bf16 storage, fp32 accumulation, what torch.mm does for bf16 operands.
 
 Extension over the reference: `forward` also accepts a batch, input [B,n,in] with adj [B,n,n]
 (the reference's torch.mm only takes the 2-D single-graph form).  Any n is accepted (the aggregate kernel tiles
-the adjacency in 32 x 32 blocks); B <= 65 535 graphs per call."""
+the adjacency in 32 x 32 blocks); B <= 65 535 graphs per call.
+
+Second extension: graphs of DIFFERENT sizes in one call, `forward(input [N, in], RaggedAdjacency(values, sizes))`, in bfloat16
+(csrc/gcn_b16.hip) and in float32 (csrc/gcn_ragged.hip: the dense layer's GEMMs over all N rows, the per-graph aggregate and g_adj on
+the exact-fp32 matrix cores); input and adjacency values share one dtype."""
 import ctypes as C
 import os
 import math
@@ -329,7 +333,8 @@ class RaggedAdjacency:
     """A batch of graphs of DIFFERENT sizes for GraphConvolution (BASELINE.json configs[4]: power-law graphs of up to 256 nodes each):
     graph b owns node rows node_ptr[b] .. node_ptr[b+1] of the layer's input [N, in] and a dense n_b x n_b adjacency stored at
     values[adj_ptr[b] : adj_ptr[b] + n_b^2] (row major).  Equivalent to the reference layer (models/layers.py:57-63) applied to each graph,
-    i.e. to one block-diagonal adjacency over all N nodes.  `values` is a bfloat16 GPU tensor and may require grad."""
+    i.e. to one block-diagonal adjacency over all N nodes.  `values` is a bfloat16 or a float32 GPU tensor — the dtype of the layer's input
+    and parameters — and may require grad."""
 
     def __init__(self, values, sizes):
         sizes = [int(v) for v in sizes]
@@ -355,6 +360,83 @@ class RaggedAdjacency:
     def block(self, b):
         o, n = int(self.adj_ptr[b]), self.sizes[b]
         return self.values[o:o + n * n].view(n, n)
+
+    def row_tiles(self):
+        """The float32 kernels' work list, built once from `sizes`: [tiles, 2] int32 on the values' device, one (graph, row tile) pair per
+        32 rows of every graph (include/recon_hip.h: recon_gcn_ragged_fwd's `tiles`)."""
+        t = self.__dict__.get("_row_tiles")
+        if t is None:
+            pairs = [(b, i) for b, n in enumerate(self.sizes) for i in range((n + 31) // 32)]
+            t = self._row_tiles = torch.tensor(pairs, dtype=torch.int32).reshape(-1, 2).to(self.values.device)
+        return t
+
+
+class _GcnRaggedFunction(torch.autograd.Function):
+    """GraphConvolution over a ragged batch in float32 (csrc/gcn_ragged.hip): x @ W, g_support @ W^T and x^T @ g_support over all node
+    rows at once on the dense layer's GEMMs (the same `_GEMM_BX3` switch), the aggregate and g_adj per graph on the exact-fp32 matrix
+    cores.  `x` is read in place through a row-strided view."""
+
+    @staticmethod
+    def forward(ctx, x, values, weight, bias, ragged):
+        _lib.require_gpu(x, values, weight, bias, dtype=torch.float32)
+        if x.dim() != 2 or x.shape[0] != ragged.total_rows or weight.shape[0] != x.shape[1]:
+            raise ValueError("GraphConvolution (ragged): input must be [total nodes, in_features]")
+        if ragged.B > _lib.MAX_BATCH:
+            raise NotImplementedError("GraphConvolution (ragged): more than %d graphs per call" % _lib.MAX_BATCH)
+        N, I, O, B, dev, L = x.shape[0], x.shape[1], weight.shape[1], ragged.B, x.device, _lib.lib()
+        # allocated and returned AS IS: the tensor saved for the backward (its sign is the ReLU mask) is the tensor the caller holds, so an
+        # in-place edit of the result is caught by autograd's version check (_GcnFunction's rule)
+        out = torch.empty(N, O, dtype=torch.float32, device=dev)
+        ctx.ragged = ragged
+        if N == 0 or B == 0:                                  # nothing to launch
+            ctx.save_for_backward(x, values, weight, bias, out, out, None)
+            ctx.ldx = I
+            return out
+        _lib.check(L.recon_gcn_ragged_supported(B, N, ragged.n_max, I, O), "recon_gcn_ragged_supported")
+        xr, ldx = _lib.rows_in_place(x, I)
+        values, weight = values.contiguous(), weight.contiguous()
+        sup = torch.empty(N, O, dtype=torch.float32, device=dev)
+        w_split = None
+        mode = _gl._GEMM_BX3                                  # the dense layer's switch and rule (_GcnFunction.forward), over all N rows
+        if mode == "1" or (mode != "0" and 2.0 * N * I * O >= 2.0e9):
+            w_split = _lib.workspace(L.recon_gcn_split_bytes(I, O), dev)
+        tiles = ragged.row_tiles()
+        with _lib.on_device(dev):
+            _lib.check(L.recon_gcn_ragged_fwd(xr.data_ptr(), ldx, values.data_ptr(), weight.data_ptr(), _lib.ptr(bias), ragged.node_ptr.data_ptr(),
+                                              ragged.adj_ptr.data_ptr(), tiles.data_ptr(), tiles.shape[0], B, N, ragged.n_max, I, O, sup.data_ptr(),
+                                              out.data_ptr(), _lib.ptr(w_split), _lib.current_stream()), "recon_gcn_ragged_fwd")
+        ctx.save_for_backward(xr, values, weight, bias, sup, out, w_split)
+        ctx.ldx = ldx
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        xr, values, weight, bias, sup, out, w_split = ctx.saved_tensors
+        ragged, ldx = ctx.ragged, ctx.ldx
+        N, I, O, B, dev, L = xr.shape[0], xr.shape[1], weight.shape[1], ragged.B, gout.device, _lib.lib()
+        f32 = dict(dtype=torch.float32, device=dev)
+        nx, nadj, nw, nb = ctx.needs_input_grad[:4]
+        g_x = torch.empty(N, I, **f32) if nx else None
+        g_adj = torch.empty(values.shape, **f32) if nadj else None
+        g_w = torch.empty(I, O, **f32) if nw else None
+        g_b = torch.empty(O, **f32) if (nb and bias is not None) else None
+        if N == 0 or B == 0:                                  # no rows: the parameters' gradients are sums over nothing
+            for g in (g_w, g_b):
+                if g is not None:
+                    g.zero_()
+            return g_x, g_adj, g_w, g_b, None
+        gout = gout.contiguous()
+        g_sup = torch.empty(N, O, **f32)
+        partial = torch.empty(L.recon_gcn_ragged_bwd_partial_floats(B, N, I, O), **f32)
+        gs_split = _lib.workspace(L.recon_gcn_bwd_split_bytes(1, N, O), dev) if (w_split is not None and g_w is not None) else None
+        tiles = ragged.row_tiles()
+        with _lib.on_device(dev):
+            _lib.check(L.recon_gcn_ragged_bwd(xr.data_ptr(), ldx, values.data_ptr(), weight.data_ptr(), ragged.node_ptr.data_ptr(),
+                                              ragged.adj_ptr.data_ptr(), tiles.data_ptr(), tiles.shape[0], B, N, ragged.n_max, I, O, sup.data_ptr(),
+                                              out.data_ptr(), _lib.ptr(w_split), gout.data_ptr(), g_sup.data_ptr(), partial.data_ptr(), _lib.ptr(g_x),
+                                              _lib.ptr(g_adj), _lib.ptr(g_w), _lib.ptr(g_b), _lib.ptr(gs_split), _lib.current_stream()),
+                       "recon_gcn_ragged_bwd")
+        return g_x, g_adj, g_w, g_b, None
 
 
 class _GcnB16RaggedFunction(torch.autograd.Function):
@@ -510,10 +592,12 @@ def gcn_stack(x, adj, layers):
     (csrc/gcn_b16.hip: k_gcn_b16_stack_fwd); with gradients (anything but `adj` requiring grad, in_features <= 320) the forward also keeps
     every layer's result and the backward is the mirror-image kernel + one weight-gradient GEMM per layer (_GcnB16StackFunction).  Results
     and gradients are bit-equal to the loop, which is also what runs for every other case.  Repacked weights are kept per weight tensor (identity + version); call
-    invalidate_stack_planes() after writing through `weight.data`."""
+    invalidate_stack_planes() after writing through `weight.data`.
+    A RaggedAdjacency (graphs of different sizes, x [total nodes, in]) runs layer by layer in bfloat16 and in float32 alike: the same
+    calls as the loop, hence the same bits."""
     layers = list(layers)
     if isinstance(adj, RaggedAdjacency):        # graphs of different sizes: layer by layer (GEMM over all rows + aggregate per graph;
-        return _layer_loop(x, adj, layers)      # the one-kernel form of a layer was measured and is no faster there, DESIGN 9)
+        return _layer_loop(x, adj, layers)      # the one-kernel form of a bf16 layer was measured and is no faster there, DESIGN 9)
     need_grad = torch.is_grad_enabled() and (x.requires_grad or adj.requires_grad or any(p.requires_grad for l in layers for p in l.parameters()))
     form = _stack_form(x, adj, layers, need_grad)
     if form is None:
@@ -580,8 +664,11 @@ class GraphConvolution(Module):
         return super()._apply(fn, *args, **kwargs)
 
     def forward(self, input, adj):
-        if isinstance(adj, RaggedAdjacency):                  # graphs of different sizes (bfloat16): input [total nodes, in]
-            return _GcnB16RaggedFunction.apply(input, adj.values, self.weight, self.bias, adj)
+        if isinstance(adj, RaggedAdjacency):                  # graphs of different sizes: input [total nodes, in], bfloat16 or float32
+            if input.dtype != adj.values.dtype and {input.dtype, adj.values.dtype} == {torch.float32, torch.bfloat16}:
+                raise TypeError("GraphConvolution (ragged): input is %s but the adjacency values are %s" % (input.dtype, adj.values.dtype))
+            fn = _GcnRaggedFunction if input.dtype == torch.float32 else _GcnB16RaggedFunction
+            return fn.apply(input, adj.values, self.weight, self.bias, adj)
         fn = _GcnB16Function if input.dtype == torch.bfloat16 else _GcnFunction     # bf16 storage / fp32 accumulate (module.to(torch.bfloat16))
         extra = (not self.training,) if fn is _GcnB16Function else ()              # eval(): the repacked weight planes are kept across calls
         if input.dim() == 3 and input.shape[0] > _lib.MAX_BATCH:   # 16-bit grid dimension over the graphs; graphs are independent: run slices
