@@ -1301,6 +1301,28 @@ int recon_line_pool_fwd(const float* states, int64_t ld, const float* weight, co
 int recon_line_pool_bwd(const float* states, int64_t ld, const float* weight, const float* g_out, const void* positions, int64_t U,
                         int32_t Ln, int32_t C, int32_t E, int32_t k, float* g_states, float* g_w, float* g_b, void* workspace,
                         size_t workspace_bytes, recon_stream_t stream);
+/* The ragged form of E12 (models/models.py:73-81 over the present lines alone): states is a flat list of L rows of C floats at one row
+ * stride ld >= C, and entity u owns the rows line_ptr[u] .. line_ptr[u + 1] (int32 [U + 1], ascending, line_ptr[0] = 0, line_ptr[U] = L;
+ * n_max = the longest entity's rows).  Every row is a present line, so no mask is read:
+ *     out[u][e] = max over p < n_u - k + 1 of  bias[e] + sum_{j < k} sum_c weight[e][c][j] states[line_ptr[u] + p + j][c]
+ * which is what the padded form gives for the same entity with the positions p >= n_u - k + 1 masked, bit for bit (a cell's sum is one
+ * fma chain whose order does not depend on the chunk sizes).  An entity with n_u < k rows (n_u = 0 included) gives -inf, position byte
+ * 255 and no gradient.  Shapes: 0 <= U <= 2^30, 0 <= n_max <= L <= U n_max, L < 2^31, n_max - k + 1 <= 255, C k <= 1024, 1 <= E <= 64,
+ * k >= 1; everything else answers RECON_ERR_UNSUPPORTED (negative sizes RECON_ERR_INVALID) before any launch. */
+int recon_line_pool_ragged_supported(int64_t U, int64_t L, int32_t n_max, int32_t C, int32_t E, int32_t k);
+/* Bytes of the ragged backward's workspace (models/models.py:73-81): the G slabs of recon_line_pool_workspace_bytes, G a function of U
+ * alone; 0 for a refused shape and for U == 0. */
+size_t recon_line_pool_ragged_workspace_bytes(int64_t U, int64_t L, int32_t n_max, int32_t C, int32_t E, int32_t k);
+/* Ragged forward (models/models.py:73-81): recon_line_pool_fwd's kernel instantiated with the row base and the position count taken from
+ * line_ptr; out [U][E], positions [U][E] bytes or NULL.  states may be NULL when L == 0.  One launch. */
+int recon_line_pool_ragged_fwd(const float* states, int64_t ld, const float* weight, const float* bias, const int32_t* line_ptr, int64_t U,
+                               int64_t L, int32_t n_max, int32_t C, int32_t E, int32_t k, float* out, void* positions, recon_stream_t stream);
+/* Ragged backward (models/models.py:73-81): recon_line_pool_bwd's kernels over the same entity groups.  g_states [L][C] contiguous or
+ * NULL, every cell written once; g_w, g_b, the workspace and the launches as there; no atomics, bitwise reproducible, any number of
+ * backwards per forward. */
+int recon_line_pool_ragged_bwd(const float* states, int64_t ld, const float* weight, const float* g_out, const void* positions,
+                               const int32_t* line_ptr, int64_t U, int64_t L, int32_t n_max, int32_t C, int32_t E, int32_t k, float* g_states,
+                               float* g_w, float* g_b, void* workspace, size_t workspace_bytes, recon_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * E13 The stage-B objective between the logits and the optimiser (csrc/objective.hip): CrossEntropyLoss(ignore_index) over [M][n_out],
@@ -1458,7 +1480,8 @@ int recon_ctx_batch_supported(int64_t n_ids, int64_t num_entities, int64_t num_s
  * occurrence; 0 for a -1 that does not occur); entities_position int64 [n_pairs][2]; with gat_mode 2 ('selected')
  * nonzero_entity_pos int64 [<= n_pairs], the pairs with a half other than -1 in row order, and pair_slot int32 [n_pairs], a pair's row
  * among them or -1 (all -1 for gat_mode 0, none, and 1, 'all'); header int32 [8] = U, T_b, P_b, Mnz, the position of the first maximum
- * of the occurrence counts, flags, 0, 0.  Flags: 1 an id outside [-1, Ne) or without an entity, 2 a surface id outside [0, S), 4 a pair with exactly one -1
+ * of the occurrence counts, flags, L = the sum over the unique entities of min(lines, max_num_contexts) (the rows of the ragged form,
+ * recon_ctx_batch_fill_ragged; the padded form does not read it), 0.  Flags: 1 an id outside [-1, Ne) or without an entity, 2 a surface id outside [0, S), 4 a pair with exactly one -1
  * half (gat_mode 2), 8 an entity whose gat_row is -2 (gat_mode 1, 2).  A flagged value is never used as an address; its outputs are
  * unspecified and the host must not launch the other two entries. */
 int recon_ctx_batch_index(const void* const* tables, const int64_t* dims, const int64_t* entity_indices, const int32_t* surface_ids,
@@ -1472,6 +1495,16 @@ int recon_ctx_batch_index(const void* const* tables, const int64_t* dims, const 
 int recon_ctx_batch_fill(const void* const* tables, const int64_t* dims, const int64_t* unique_entities, const int32_t* unique_info, int64_t U,
                          int32_t P_b, int32_t T_b, int32_t index_bytes, void* context_words, void* context_chars, void* context_mask,
                          recon_stream_t stream);
+/* get_context_indices without its padding lines (train.py:250-258; utils/context_utils.py:365-385 pads every entity to the batch's
+ * richest, :285-291 get_mask marks the first n_u lines present): context_words [L][T_b] and context_chars [L][cfs - 1 + T_b
+ * (max_char_len + cfs - 1)], entity u's n_u = min(lines, P_b) rows one after another in rank order, L = header[6] of
+ * recon_ctx_batch_index.  Writes line_ptr int32 [U + 1], the exclusive scan of the n_u (line_ptr[U] = L), and row_entity int32 [L], the
+ * owner of every row, which the fill reads to place a row; both stay valid for the caller (line_ptr is what recon_line_pool_ragged_*
+ * takes).  The cells of a row are those of the same line in recon_ctx_batch_fill's arrays; every cell of the L rows is written exactly
+ * once, as runs of 16-byte stores, and nothing behind row L.  RECON_ERR_INVALID unless U <= L <= U P_b.  Two launches. */
+int recon_ctx_batch_fill_ragged(const void* const* tables, const int64_t* dims, const int64_t* unique_entities, const int32_t* unique_info,
+                                int64_t U, int64_t L, int32_t P_b, int32_t T_b, int32_t index_bytes, void* context_words, void* context_chars,
+                                int32_t* line_ptr, int32_t* row_entity, recon_stream_t stream);
 /* get_gat_entity_embeddings / get_selected_gat_entity_embeddings (train.py:250-258; utils/context_utils.py:444-475):
  * gat_entity_embeddings fp32 [n_pairs][2 G] = (gat_emb[gat_row[head]] | gat_emb[gat_row[tail]]), a zero half for a row below 0; with
  * nonzero_gat_entity_embeddings [Mnz][2 G] (optional) the same row again at pair_slot[pair] >= 0.  Any G >= 1.  One launch. */

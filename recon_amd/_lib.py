@@ -255,6 +255,12 @@ SYMBOLS = [
     ("recon_line_pool_fwd", C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_void_p, C.c_int64] + [C.c_int32] * 4 + [c_f32p, C.c_void_p, C.c_void_p]),
     ("recon_line_pool_bwd", C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_void_p, C.c_int64] + [C.c_int32] * 4 + [c_f32p] * 3
                                      + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("recon_line_pool_ragged_supported", C.c_int, [C.c_int64] * 2 + [C.c_int32] * 4),
+    ("recon_line_pool_ragged_workspace_bytes", C.c_size_t, [C.c_int64] * 2 + [C.c_int32] * 4),
+    ("recon_line_pool_ragged_fwd", C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, c_i32p] + [C.c_int64] * 2 + [C.c_int32] * 4
+                                            + [c_f32p, C.c_void_p, C.c_void_p]),
+    ("recon_line_pool_ragged_bwd", C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_void_p, c_i32p] + [C.c_int64] * 2 + [C.c_int32] * 4
+                                            + [c_f32p] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("recon_relation_objective_supported", C.c_int, [C.c_int64, C.c_int32]),
     ("recon_relation_objective_workspace_bytes", C.c_size_t, [C.c_int64, C.c_int32]),
     ("recon_relation_objective_fwd", C.c_int, [c_f32p, C.c_int64, c_i64p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, c_f32p, c_i64p, c_f32p, c_f32p,
@@ -363,6 +369,8 @@ SYMBOLS = [
                                         c_i32p, c_i32p, C.c_void_p]),
     ("recon_ctx_batch_fill", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), c_i64p, c_i32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("recon_ctx_batch_fill_ragged", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), c_i64p, c_i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_void_p, c_i32p, c_i32p, C.c_void_p]),
     ("recon_ctx_batch_gat", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), c_i64p, C.c_int64, c_i32p, c_f32p, c_f32p, C.c_void_p]),
     ("recon_stage_b_supported", C.c_int, [C.c_int64] * 3),
     ("recon_stage_b_slice", C.c_int, [c_i32p, C.c_void_p, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_int64, C.c_int64, C.c_int64, c_i64p, C.c_int64,

@@ -16,7 +16,7 @@ and `.cuda()` on each result.  Here the text is tokenised ONCE per dataset into 
 Every result equals the reference's array exactly — integers to the value, floats to the bit: nothing is computed, only selected,
 ordered and copied (pinned by tests/golden/context_batch1.npz, recorded from the reference's own functions).
 
-Host reads: ONE per call — a header of eight int32 (U, T_b, P_b, Mnz, the most frequent entity's position, error flags): the
+Host reads: ONE per call — a header of eight int32 (U, T_b, P_b, Mnz, the most frequent entity's position, error flags, L): the
 output shapes depend on it, as `sampler.py`'s do.  It is read behind the first launch and before the model's forward is queued, so a
 caller's step waits once, on a kernel of a few microseconds, and the forward then runs without the host waiting again.
 
@@ -27,6 +27,11 @@ form -> tokens, all int32, plus with `gat=` an fp32 [Ng, G] matrix and a row map
 Two implementations of one result: csrc/ctx_batch.hip (k_cb_index, k_cb_fill, k_cb_gat) on the GPU for batches up to
 `MAX_IDS` ids, and the same assembled from torch primitives (`unique`, `scatter_reduce`, a sort, ragged gathers), which is the CPU
 path, the path beyond the kernels' limit and what the randomised GPU test compares with; `_KERNELS = False` forces it.
+
+`batch(..., ragged_lines=True)` leaves the padding lines out: context_words [L, T_b] and context_chars [L, W] hold the
+entities' present lines one after another, L = the sum of their line counts (the header's seventh word: still one host read), and
+context_mask is a `RaggedLines` (line_ptr int32 [U + 1]) in the mask's place, which `EntityEmbedding.forward` takes as its third argument.
+The default, False, is the reference's padded form.
 """
 import ctypes as C
 import re
@@ -35,6 +40,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ragged_lines import RaggedLines
 
 ALL_ZERO, UNKNOWN = "ALL_ZERO", "_UNKNOWN"
 # embedding_utils.get_idx (utils/embedding_utils.py:13-16, :87-88): three spellings mapped onto a vocabulary entry
@@ -225,7 +231,8 @@ class ContextTables:
 
 
 class StageBBatch:
-    """The inputs of one stage-B forward; the fields carry the names of the arguments of RECON.forward."""
+    """The inputs of one stage-B forward; the fields carry the names of the arguments of RECON.forward.  With `ragged_lines=True`
+    context_words and context_chars are [L, .] and context_mask is a `RaggedLines`, in the same three positions."""
     __slots__ = ("unique_entities", "entity_indices", "context_words", "context_chars", "context_mask", "entities_position",
                  "max_occurred_entity_in_batch_pos", "gat_entity_embeddings", "nonzero_gat_entity_embeddings", "nonzero_entity_pos", "gat_mode")
 
@@ -261,11 +268,12 @@ class ContextBatcher:
     def __init__(self, tables):
         self.tables = tables
 
-    def batch(self, entity_indices, surface_ids, index_dtype=torch.int64):
+    def batch(self, entity_indices, surface_ids, index_dtype=torch.int64, ragged_lines=False):
         """entity_indices int64 [B, C, 2] (values -1 .. Ne - 1) and surface_ids [B, C, 2] (of `ContextTables.build`), both on the tables'
         device -> StageBBatch.  One host read per call (the header: sizes, the most frequent entity's position, error flags), made
         before the model's forward is queued.  index_dtype: of context_words and context_chars (torch.int64, the reference's, or
         torch.int32: the char-CNN and line-LSTM ops take both, and the char block is half the bytes).
+        ragged_lines: context_words [L, T_b] and context_chars [L, W] without the padding lines and a `RaggedLines` as context_mask.
         IndexError for an id or a surface id outside its table, KeyError for an entity the GAT table lacks, ValueError for a pair with
         exactly one ALL_ZERO half in 'selected' mode — raised from the header's flags; such a value is never used as an address."""
         t = self.tables
@@ -281,11 +289,11 @@ class ContextBatcher:
                 and _lib.lib().recon_ctx_batch_supported(n, t.dims["Ne"], t.dims["S"])):
             if surface_ids.dtype != torch.int32:                       # (a value beyond int32 stays outside the table instead of wrapping into it)
                 surface_ids = surface_ids.clamp(-1, 2 ** 31 - 1).to(torch.int32)
-            return self._batch_kernels(ids, surface_ids.contiguous(), index_dtype)
-        return self._batch_torch(ids, surface_ids.to(torch.int64).contiguous(), index_dtype)
+            return self._batch_kernels(ids, surface_ids.contiguous(), index_dtype, ragged_lines)
+        return self._batch_torch(ids, surface_ids.to(torch.int64).contiguous(), index_dtype, ragged_lines)
 
     # ------------------------------------------------------------------------------------------------------------- the kernels
-    def _batch_kernels(self, ids, surf, index_dtype):
+    def _batch_kernels(self, ids, surf, index_dtype, ragged_lines=False):
         t, L, dev = self.tables, _lib.lib(), ids.device
         B, Cn = ids.shape[0], ids.shape[1]
         npairs, d = B * Cn, t.dims
@@ -301,16 +309,27 @@ class ContextBatcher:
             st = _lib.current_stream()
             _lib.check(L.recon_ctx_batch_index(t._ptrs_c, t._dims_c, ids.data_ptr(), surf.data_ptr(), npairs, mode, uniq.data_ptr(), uinfo.data_ptr(),
                                                pos.data_ptr(), nzpos.data_ptr(), slot.data_ptr(), hdr.data_ptr(), st), "recon_ctx_batch_index")
-            U, T, P, Mnz, max_pos, err = hdr.tolist()[:6]                  # the one host read
+            U, T, P, Mnz, max_pos, err, Lr = hdr.tolist()[:7]              # the one host read
             _raise_flags(err, t)
             W = d["conv_filter_size"] - 1 + T * (d["max_char_len"] + d["conv_filter_size"] - 1)
             if U * P * W >= MAX_CELLS:                                 # (beyond the defaults' reach: 8193 entities of 32 x 386 are 1e8 cells)
-                return self._batch_torch(ids, surf.to(torch.int64), index_dtype)
-            words = _new((U, P, T), index_dtype, dev)
-            chars = _new((U, P, W), index_dtype, dev)
-            mask = _new((U, P), torch.bool, dev)
-            _lib.check(L.recon_ctx_batch_fill(t._ptrs_c, t._dims_c, uniq.data_ptr(), uinfo.data_ptr(), U, P, T, 8 if index_dtype == torch.int64 else 4,
-                                              words.data_ptr() if T else None, chars.data_ptr(), mask.data_ptr(), st), "recon_ctx_batch_fill")
+                return self._batch_torch(ids, surf.to(torch.int64), index_dtype, ragged_lines)
+            ib = 8 if index_dtype == torch.int64 else 4
+            if ragged_lines:                                           # the present lines alone: Lr rows, a RaggedLines in the mask's place
+                words = _new((Lr, T), index_dtype, dev)
+                chars = _new((Lr, W), index_dtype, dev)
+                line_ptr = _new((U + 1,), torch.int32, dev)
+                row_ent = _new((Lr,), torch.int32, dev)
+                _lib.check(L.recon_ctx_batch_fill_ragged(t._ptrs_c, t._dims_c, uniq.data_ptr(), uinfo.data_ptr(), U, Lr, P, T, ib,
+                                                         words.data_ptr() if T else None, chars.data_ptr(), line_ptr.data_ptr(), row_ent.data_ptr(),
+                                                         st), "recon_ctx_batch_fill_ragged")
+                mask = RaggedLines(line_ptr, U, Lr, P)
+            else:
+                words = _new((U, P, T), index_dtype, dev)
+                chars = _new((U, P, W), index_dtype, dev)
+                mask = _new((U, P), torch.bool, dev)
+                _lib.check(L.recon_ctx_batch_fill(t._ptrs_c, t._dims_c, uniq.data_ptr(), uinfo.data_ptr(), U, P, T, ib,
+                                                  words.data_ptr() if T else None, chars.data_ptr(), mask.data_ptr(), st), "recon_ctx_batch_fill")
             gat = nz = None
             if mode:
                 gat = _new((B, Cn, 2 * d["G"]), torch.float32, dev)
@@ -327,7 +346,7 @@ class ContextBatcher:
         return out
 
     # ------------------------------------------------------------------------------------------------------------- torch primitives
-    def _batch_torch(self, ids, surf, index_dtype):
+    def _batch_torch(self, ids, surf, index_dtype, ragged_lines=False):
         t, dev, d, a = self.tables, ids.device, self.tables.dims, self.tables.arrays
         B, Cn = ids.shape[0], ids.shape[1]
         n, Ne, S, G = ids.numel(), d["Ne"], d["S"], d["G"]
@@ -390,6 +409,9 @@ class ContextBatcher:
         out = StageBBatch()
         out.unique_entities, out.entity_indices, out.entities_position = unique_entities, ids, entities_position
         out.context_words, out.context_chars, out.context_mask = words, chars, ~live
+        if ragged_lines:                                               # the rows under ~mask, entity by entity (boolean indexing: a host read on a GPU)
+            out.context_words, out.context_chars = words[live], chars[live]
+            out.context_mask = RaggedLines.from_counts(live.sum(1), dev)
         out.max_occurred_entity_in_batch_pos = int(max_pos)
         out.gat_entity_embeddings = out.nonzero_gat_entity_embeddings = out.nonzero_entity_pos = None
         out.gat_mode = mode

@@ -23,6 +23,11 @@
 // k_cb_fill: the three context arrays as flat runs of 16-byte vectors — a wave's store instruction covers 1 KiB of consecutive bytes —
 //   whatever the row width; a base that is not 16-byte aligned shifts the vector grid, so that only the first and last vector of an
 //   array fall back to element stores.  Every cell is written exactly once (the host hands torch.empty).
+// k_cb_scan + k_cb_fill over CbRaggedRows (recon_ctx_batch_fill_ragged): the same two arrays without the padding lines, [L][T_b] and [L][W] with
+//   L = header[6] = the sum of the entities' line counts, which k_cb_index adds up in LDS (an integer add: any order, one result).  One workgroup
+//   scans the counts in rank order into line_ptr [U + 1] and writes the owner of every row into row_ent [L]; the fill's vectors then find
+//   (entity, line) of a row by two loads, row_ent[row] and line_ptr[u], where a search of line_ptr would be 13 dependent loads for the 8193
+//   entities a batch can hold.  The map is L int32, at most 1/386 of the char block at the reference's widths.  No mask is written: every row is present.
 // k_cb_gat: a wave per (b, c) pair writes both halves of gat_entity_embeddings and, for a present pair, the row of the compacted block.
 #include "recon_common.h"
 
@@ -98,7 +103,8 @@ __global__ void __launch_bounds__(kCbThreads) k_cb_index(const CbTables t, const
     uint32_t* cnt = maxp + H;
     uint32_t* bits = cnt + H;
     uint32_t* wpre = bits + kCbWords;
-    uint32_t* misc = wpre + kCbWords;          // 0 err, 1 -1 occurs, 2 longest line, 3 most lines, 4 count key, 5 first occurrences, 6 present pairs
+    uint32_t* misc = wpre + kCbWords;          // 0 err, 1 -1 occurs, 2 longest line, 3 most lines, 4 count key, 5 first occurrences, 6 present pairs,
+                                               // 7 the lines of all entities (each cut at max_P): the rows of the ragged form
     const int tid = threadIdx.x;
     for (uint32_t s = tid; s < H; s += kCbThreads) { keys[s] = kCbEmpty; minp[s] = 0xffffffffu; maxp[s] = 0; cnt[s] = 0; }
     if (tid < kCbWords) bits[tid] = 0;
@@ -147,6 +153,7 @@ __global__ void __launch_bounds__(kCbThreads) k_cb_index(const CbTables t, const
         uinfo[2 * r] = nl;
         uinfo[2 * r + 1] = sid;
         atomicMax(&misc[3], static_cast<uint32_t>(nl));
+        atomicAdd(&misc[7], static_cast<uint32_t>(min(nl, t.max_P)));
         atomicMax(&misc[2], static_cast<uint32_t>(max(t.ent_max_len[key], t.sf_len[sid])));
         atomicMax(&misc[4], (cnt[s] << 16) | (0xffffu - r));
         if (key == 0u) misc[1] = 1u;
@@ -158,6 +165,7 @@ __global__ void __launch_bounds__(kCbThreads) k_cb_index(const CbTables t, const
         uinfo[0] = nl;
         uinfo[1] = 0;
         atomicMax(&misc[3], static_cast<uint32_t>(nl));
+        atomicAdd(&misc[7], static_cast<uint32_t>(min(nl, t.max_P)));
         atomicMax(&misc[2], static_cast<uint32_t>(max(t.ent_max_len[0], t.sf_len[0])));
     }
     // 4. positions
@@ -197,16 +205,30 @@ __global__ void __launch_bounds__(kCbThreads) k_cb_index(const CbTables t, const
         hdr[3] = static_cast<int32_t>(misc[6]);
         hdr[4] = static_cast<int32_t>(0xffffu - (misc[4] & 0xffffu));
         hdr[5] = static_cast<int32_t>(misc[0]);
-        hdr[6] = 0;
+        hdr[6] = static_cast<int32_t>(misc[7]);
         hdr[7] = 0;
     }
 }
 
 // tokens of line p of unique entity u: the surface form of its last occurrence, then the entity's table lines; nothing from its line count on
 struct CbLine { int32_t start, len; };
-__device__ __forceinline__ CbLine cb_line(const CbTables& t, const int64_t* __restrict__ uniq, const int32_t* __restrict__ uinfo, int32_t row, int32_t P, int32_t T) {
-    const int32_t u = row / P;
-    const int32_t p = row - u * P;
+// where row `row` of the context arrays lies: P rows per entity (the padded form), or the entity's own rows one after another (the ragged
+// form: entity u owns the rows line_ptr[u] .. line_ptr[u + 1], and row_ent[row], written by k_cb_scan, names the owner of a row)
+struct CbPaddedRows {
+    static constexpr bool kMask = true;
+    int32_t P;
+    __device__ __forceinline__ void at(int32_t row, int32_t& u, int32_t& p) const { u = row / P; p = row - u * P; }
+};
+struct CbRaggedRows {
+    static constexpr bool kMask = false;
+    const int32_t* line_ptr;
+    const int32_t* row_ent;
+    __device__ __forceinline__ void at(int32_t row, int32_t& u, int32_t& p) const { u = row_ent[row]; p = row - line_ptr[u]; }
+};
+template <typename ROWS>
+__device__ __forceinline__ CbLine cb_line(const CbTables& t, const int64_t* __restrict__ uniq, const int32_t* __restrict__ uinfo, int32_t row, const ROWS& rows, int32_t T) {
+    int32_t u, p;
+    rows.at(row, u, p);
     CbLine ln{0, 0};
     if (p == 0) {
         const int32_t sid = uinfo[2 * u + 1];
@@ -224,8 +246,8 @@ __device__ __forceinline__ CbLine cb_line(const CbTables& t, const int64_t* __re
 // vector v of the flat array out[total] (rows of width W): elements [v VE - shift, v VE - shift + VE), shift = elements from the last
 // 16-byte boundary to out.  Flat indices are int32 (recon_ctx_batch_fill refuses an array of 2^31 cells: a 64-bit division costs as much as the
 // rest of a vector).  One division finds the vector's row and column, one more the word slot w and the char c of a char column; from there they count up.
-template <typename IT, int VE, bool CHARS>
-__device__ __forceinline__ void cb_fill_vec(const CbTables& t, const int64_t* __restrict__ uniq, const int32_t* __restrict__ uinfo, int32_t P, int32_t T,
+template <typename IT, int VE, bool CHARS, typename ROWS>
+__device__ __forceinline__ void cb_fill_vec(const CbTables& t, const int64_t* __restrict__ uniq, const int32_t* __restrict__ uinfo, const ROWS& P, int32_t T,
                                             int32_t W, IT* __restrict__ out, int32_t total, int32_t shift, int32_t v) {
     typedef IT vec_t __attribute__((ext_vector_type(VE)));
     const int32_t f0 = v * VE - shift;
@@ -271,23 +293,58 @@ __device__ __forceinline__ void cb_fill_vec(const CbTables& t, const int64_t* __
     }
 }
 
-template <typename IT>
-__global__ void __launch_bounds__(kCbFillThreads) k_cb_fill(const CbTables t, const int64_t* __restrict__ uniq, const int32_t* __restrict__ uinfo, int64_t U,
-                                                            int32_t P, int32_t T, IT* __restrict__ words, IT* __restrict__ chars,
+// `rows` rows of either form; the mask blocks (the padded form alone) follow the word blocks
+template <typename IT, typename ROWS>
+__global__ void __launch_bounds__(kCbFillThreads) k_cb_fill(const CbTables t, const int64_t* __restrict__ uniq, const int32_t* __restrict__ uinfo, int32_t rows,
+                                                            const ROWS P, int32_t T, IT* __restrict__ words, IT* __restrict__ chars,
                                                             uint8_t* __restrict__ mask, int64_t char_blocks, int64_t word_blocks, int32_t char_shift,
                                                             int32_t word_shift) {
     constexpr int VE = 16 / sizeof(IT);
     const int64_t blk = blockIdx.x;
-    const int32_t rows = static_cast<int32_t>(U * P);
     if (blk < char_blocks) {
         const int32_t W = t.cfs - 1 + T * (t.mcl + t.cfs - 1);
         cb_fill_vec<IT, VE, true>(t, uniq, uinfo, P, T, W, chars, rows * W, char_shift, static_cast<int32_t>(blk * kCbFillThreads + threadIdx.x));
     } else if (blk < char_blocks + word_blocks) {
         cb_fill_vec<IT, VE, false>(t, uniq, uinfo, P, T, T, words, rows * T, word_shift, static_cast<int32_t>((blk - char_blocks) * kCbFillThreads + threadIdx.x));
-    } else {
+    } else if constexpr (ROWS::kMask) {
         const int32_t i = static_cast<int32_t>((blk - char_blocks - word_blocks) * kCbFillThreads + threadIdx.x);
-        if (i < rows) mask[i] = i % P >= uinfo[2 * (i / P)] ? 1 : 0;
+        if (i < rows) mask[i] = i % P.P >= uinfo[2 * (i / P.P)] ? 1 : 0;
     }
+}
+
+// line_ptr [U + 1] = the exclusive scan, in rank order, of the entities' line counts (each cut at P), and row_ent [L]: the entity of every
+// row.  One workgroup: thread i takes the entities [i per, (i + 1) per), per = ceil(U / 1024) <= 9; a wave scans its lanes' sums by
+// __shfl_up, thread 0 the 16 wave totals.  Nothing is written behind row L.
+__global__ void __launch_bounds__(kCbThreads) k_cb_scan(const int32_t* __restrict__ uinfo, int32_t U, int32_t P, int32_t L, int32_t* __restrict__ line_ptr,
+                                                        int32_t* __restrict__ row_ent) {
+    __shared__ uint32_t wsum[kCbThreads / kWave];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    const int per = (U + kCbThreads - 1) / kCbThreads;
+    const int u0 = min(U, tid * per), u1 = min(U, u0 + per);
+    uint32_t sum = 0;
+    for (int u = u0; u < u1; ++u) sum += static_cast<uint32_t>(min(max(uinfo[2 * u], 0), P));
+    uint32_t incl = sum;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const uint32_t o = __shfl_up(incl, off, kWave);
+        if (lane >= off) incl += o;
+    }
+    if (lane == kWave - 1) wsum[wv] = incl;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t run = 0;
+        for (int w = 0; w < kCbThreads / kWave; ++w) { const uint32_t s = wsum[w]; wsum[w] = run; run += s; }
+    }
+    __syncthreads();
+    int32_t base = static_cast<int32_t>(wsum[wv] + incl - sum);
+    for (int u = u0; u < u1; ++u) {
+        const int32_t nl = min(max(uinfo[2 * u], 0), P);
+        line_ptr[u] = base;
+        for (int32_t i = 0; i < nl; ++i)
+            if (base + i < L) row_ent[base + i] = u;
+        base += nl;
+    }
+    if (tid == kCbThreads - 1) line_ptr[U] = base;
 }
 
 __global__ void __launch_bounds__(kCbFillThreads) k_cb_gat(const CbTables t, const int64_t* __restrict__ ids, int64_t npairs, const int32_t* __restrict__ pair_slot,
@@ -346,18 +403,35 @@ bool cb_tables(const void* const* tables, const int64_t* dims, bool want_gat, Cb
     return true;
 }
 
-template <typename IT>
-void cb_launch_fill(hipStream_t st, const CbTables& t, const int64_t* uniq, const int32_t* uinfo, int64_t U, int32_t P, int32_t T, void* words, void* chars,
-                    void* mask) {
+// `n_rows` rows of either form (the padded form: U P_b, with the mask behind them)
+template <typename IT, typename ROWS>
+void cb_launch_fill(hipStream_t st, const CbTables& t, const int64_t* uniq, const int32_t* uinfo, int64_t n_rows, const ROWS& rows, int32_t T, void* words,
+                    void* chars, void* mask) {
     constexpr int VE = 16 / sizeof(IT);
     const int64_t W = t.cfs - 1 + static_cast<int64_t>(T) * (t.mcl + t.cfs - 1);
     const int32_t cs = static_cast<int32_t>((reinterpret_cast<uintptr_t>(chars) & 15u) / sizeof(IT));
     const int32_t ws = static_cast<int32_t>((reinterpret_cast<uintptr_t>(words) & 15u) / sizeof(IT));
-    const int64_t cb = ceil_div64(ceil_div64(U * P * W + cs, VE), kCbFillThreads);
-    const int64_t wb = ceil_div64(ceil_div64(U * P * T + ws, VE), kCbFillThreads);
-    const int64_t mb = ceil_div64(U * P, kCbFillThreads);
-    hipLaunchKernelGGL(k_cb_fill<IT>, dim3(static_cast<unsigned>(cb + wb + mb)), dim3(kCbFillThreads), 0, st, t, uniq, uinfo, U, P, T,
-                       static_cast<IT*>(words), static_cast<IT*>(chars), static_cast<uint8_t*>(mask), cb, wb, cs, ws);
+    const int64_t cb = ceil_div64(ceil_div64(n_rows * W + cs, VE), kCbFillThreads);
+    const int64_t wb = ceil_div64(ceil_div64(n_rows * T + ws, VE), kCbFillThreads);
+    const int64_t mb = ROWS::kMask ? ceil_div64(n_rows, kCbFillThreads) : 0;
+    hipLaunchKernelGGL((k_cb_fill<IT, ROWS>), dim3(static_cast<unsigned>(cb + wb + mb)), dim3(kCbFillThreads), 0, st, t, uniq, uinfo,
+                       static_cast<int32_t>(n_rows), rows, T, static_cast<IT*>(words), static_cast<IT*>(chars), static_cast<uint8_t*>(mask), cb, wb, cs, ws);
+}
+
+// what recon_ctx_batch_fill and recon_ctx_batch_fill_ragged check alike, over n_rows rows
+int cb_fill_args(const void* const* tables, const int64_t* dims, const int64_t* uniq, const int32_t* uinfo, int64_t U, int64_t n_rows, int32_t P_b, int32_t T_b,
+                 int32_t index_bytes, const void* words, const void* chars, CbTables* t) {
+    if (U < 1 || P_b < 1 || T_b < 0 || (index_bytes != 4 && index_bytes != 8)) return RECON_ERR_INVALID;
+    if (!cb_tables(tables, dims, false, t)) return RECON_ERR_INVALID;
+    if (!uniq || !uinfo || !chars || (T_b > 0 && !words)) return RECON_ERR_INVALID;
+    if (P_b > t->max_P || T_b > t->max_T) return RECON_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(chars) | reinterpret_cast<uintptr_t>(words)) % static_cast<uintptr_t>(index_bytes)) return RECON_ERR_INVALID;
+    if (U > kCbMaxIds + 1) return RECON_ERR_UNSUPPORTED;
+    // every flat index of the char block, the last workgroup's past-the-end ones included, fits an int32
+    if (static_cast<int64_t>(T_b) * (t->mcl + t->cfs - 1) > (int64_t{1} << 24) ||
+        n_rows * (t->cfs - 1 + static_cast<int64_t>(T_b) * (t->mcl + t->cfs - 1)) >= kCbMaxCells)
+        return RECON_ERR_UNSUPPORTED;
+    return RECON_OK;
 }
 
 }  // namespace
@@ -393,19 +467,31 @@ extern "C" int recon_ctx_batch_fill(const void* const* tables, const int64_t* di
                                     int32_t P_b, int32_t T_b, int32_t index_bytes, void* context_words, void* context_chars, void* context_mask,
                                     recon_stream_t stream) {
     using namespace recon;
-    if (U < 1 || P_b < 1 || T_b < 0 || (index_bytes != 4 && index_bytes != 8)) return RECON_ERR_INVALID;
     CbTables t;
-    if (!cb_tables(tables, dims, false, &t)) return RECON_ERR_INVALID;
-    if (!unique_entities || !unique_info || !context_chars || !context_mask || (T_b > 0 && !context_words)) return RECON_ERR_INVALID;
-    if (P_b > t.max_P || T_b > t.max_T) return RECON_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(context_chars) | reinterpret_cast<uintptr_t>(context_words)) % static_cast<uintptr_t>(index_bytes)) return RECON_ERR_INVALID;
-    if (U > kCbMaxIds + 1) return RECON_ERR_UNSUPPORTED;
-    // every flat index of the char block, the last workgroup's past-the-end ones included, fits an int32
-    if (static_cast<int64_t>(T_b) * (t.mcl + t.cfs - 1) > (int64_t{1} << 24) ||
-        U * P_b * (t.cfs - 1 + static_cast<int64_t>(T_b) * (t.mcl + t.cfs - 1)) >= kCbMaxCells)
-        return RECON_ERR_UNSUPPORTED;
-    if (index_bytes == 8) cb_launch_fill<int64_t>(as_stream(stream), t, unique_entities, unique_info, U, P_b, T_b, context_words, context_chars, context_mask);
-    else cb_launch_fill<int32_t>(as_stream(stream), t, unique_entities, unique_info, U, P_b, T_b, context_words, context_chars, context_mask);
+    if (U >= 1 && P_b >= 1 && !context_mask) return RECON_ERR_INVALID;
+    const int rc = cb_fill_args(tables, dims, unique_entities, unique_info, U, U * P_b, P_b, T_b, index_bytes, context_words, context_chars, &t);
+    if (rc != RECON_OK) return rc;
+    const CbPaddedRows rows{P_b};
+    if (index_bytes == 8) cb_launch_fill<int64_t>(as_stream(stream), t, unique_entities, unique_info, U * P_b, rows, T_b, context_words, context_chars, context_mask);
+    else cb_launch_fill<int32_t>(as_stream(stream), t, unique_entities, unique_info, U * P_b, rows, T_b, context_words, context_chars, context_mask);
+    RECON_CHECK_LAUNCH();
+    return RECON_OK;
+}
+
+extern "C" int recon_ctx_batch_fill_ragged(const void* const* tables, const int64_t* dims, const int64_t* unique_entities, const int32_t* unique_info,
+                                           int64_t U, int64_t L, int32_t P_b, int32_t T_b, int32_t index_bytes, void* context_words, void* context_chars,
+                                           int32_t* line_ptr, int32_t* row_entity, recon_stream_t stream) {
+    using namespace recon;
+    CbTables t;
+    if (L < U || (U >= 1 && P_b >= 1 && L > U * P_b) || !line_ptr || !row_entity) return RECON_ERR_INVALID;
+    const int rc = cb_fill_args(tables, dims, unique_entities, unique_info, U, L, P_b, T_b, index_bytes, context_words, context_chars, &t);
+    if (rc != RECON_OK) return rc;
+    hipLaunchKernelGGL(k_cb_scan, dim3(1), dim3(kCbThreads), 0, as_stream(stream), unique_info, static_cast<int32_t>(U), P_b, static_cast<int32_t>(L),
+                       line_ptr, row_entity);
+    RECON_CHECK_LAUNCH();
+    const CbRaggedRows rows{line_ptr, row_entity};
+    if (index_bytes == 8) cb_launch_fill<int64_t>(as_stream(stream), t, unique_entities, unique_info, L, rows, T_b, context_words, context_chars, nullptr);
+    else cb_launch_fill<int32_t>(as_stream(stream), t, unique_entities, unique_info, L, rows, T_b, context_words, context_chars, nullptr);
     RECON_CHECK_LAUNCH();
     return RECON_OK;
 }

@@ -25,6 +25,12 @@
 //   so the loads of the winning line states do not wait for one another.  A slab of more than 1024 cells takes further passes over
 //   the group's entities.  The slab goes to the workspace.  Either half is skipped when its result is not wanted.
 // k_lp_reduce: adds the slabs in group order.
+//
+// The ragged form (recon_line_pool_ragged_*): the states are a flat [L][C] list and entity u owns the rows line_ptr[u] .. line_ptr[u + 1]
+//   (recon_amd.RaggedLines), every one of them present: P_u = n_u - k + 1 positions, none masked, -inf and byte 255 where n_u < k.  The
+//   same two kernel bodies, instantiated with RAGGED: the row base and the position count come from line_ptr instead of u Ln and the
+//   mask; chunk sizes come from the longest entity, and a sum's order does not depend on them (one fma chain in r order per cell), so an
+//   entity gives the bits the padded form gives for it.  The entity groups of the backward are those of the padded form.
 #include "recon_common.h"
 
 #include <cmath>
@@ -54,8 +60,10 @@ inline LpTiles lp_tiles(int P, int R, int E) {
 inline int64_t lp_per(int64_t U) { return ceil_div64(U, U < kLpMaxGroups ? U : kLpMaxGroups); }
 inline int64_t lp_groups(int64_t U) { return ceil_div64(U, lp_per(U)); }
 
+// RAGGED: `rows` is line_ptr [U + 1] and every position of an entity is unmasked; otherwise `rows` is the mask [U][P] and Ln the line count
+template <bool RAGGED>
 __global__ void __launch_bounds__(kLpThreads) k_lp_fwd(const float* __restrict__ states, int64_t ld, const float* __restrict__ weight,
-                                                       const float* __restrict__ bias, const uint8_t* __restrict__ mask, int32_t Ln, int32_t C,
+                                                       const float* __restrict__ bias, const void* __restrict__ rows, int32_t Ln, int32_t C,
                                                        int32_t E, int32_t k, int32_t PC, int32_t RC, float* __restrict__ out,
                                                        uint8_t* __restrict__ pos) {
     extern __shared__ __align__(16) float lp_lds[];
@@ -63,11 +71,21 @@ __global__ void __launch_bounds__(kLpThreads) k_lp_fwd(const float* __restrict__
     __shared__ uint8_t masked[kLpMaxP + 1];
     const int t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
     const int64_t u = blockIdx.x;
-    const int P = Ln - k + 1, R = C * k, pitch = RC + 1;
+    const int R = C * k, pitch = RC + 1;
+    int P;
+    int64_t row0;
+    if constexpr (RAGGED) {
+        const int32_t* line_ptr = static_cast<const int32_t*>(rows);
+        row0 = line_ptr[u];
+        P = min(line_ptr[u + 1] - static_cast<int32_t>(row0) - k + 1, kLpMaxP);      // <= 0: an entity shorter than the filter
+    } else {
+        row0 = u * Ln;
+        P = Ln - k + 1;
+        if (t < P) masked[t] = static_cast<const uint8_t*>(rows)[u * P + t];
+    }
     float* Ws = lp_lds;
     float* Xs = lp_lds + E * pitch;
-    const float* srow = states + u * Ln * ld;
-    if (t < P) masked[t] = mask[u * P + t];
+    const float* srow = states + row0 * ld;
     float best = -INFINITY;                                              // thread e < E: the maximum so far and where
     int at = kLpNone;
     for (int p0 = 0; p0 < P; p0 += PC) {
@@ -123,7 +141,7 @@ __global__ void __launch_bounds__(kLpThreads) k_lp_fwd(const float* __restrict__
 #pragma unroll 4
             for (int pi = 0; pi < pcn; ++pi) {                           // (selects, not branches: the reads of the next positions go ahead)
                 const float v = vals[pi * E + t];
-                const bool take = !masked[p0 + pi] && (at == kLpNone || v > best || (v != v && best == best));
+                const bool take = (RAGGED || !masked[p0 + pi]) && (at == kLpNone || v > best || (v != v && best == best));
                 best = take ? v : best;
                 at = take ? p0 + pi : at;
             }
@@ -136,11 +154,12 @@ __global__ void __launch_bounds__(kLpThreads) k_lp_fwd(const float* __restrict__
 }
 
 // WLDS: the weight (E C k <= kLpBwdWeightFloats) is staged in LDS for the d_states pass; otherwise it is read where it lies
-template <bool WLDS>
+// RAGGED: entity u's rows of states and g_states are line_ptr[u] .. line_ptr[u + 1] (g_states is [L][C]); otherwise u Ln .. (u + 1) Ln
+template <bool WLDS, bool RAGGED>
 __global__ void __launch_bounds__(kLpThreads) k_lp_bwd(const float* __restrict__ states, int64_t ld, const float* __restrict__ weight,
                                                        const float* __restrict__ g_out, const uint8_t* __restrict__ pos, int64_t U, int64_t per,
-                                                       int32_t Ln, int32_t C, int32_t E, int32_t k, float* __restrict__ g_states,
-                                                       float* __restrict__ slabs) {
+                                                       int32_t Ln, int32_t C, int32_t E, int32_t k, const int32_t* __restrict__ line_ptr,
+                                                       float* __restrict__ g_states, float* __restrict__ slabs) {
     extern __shared__ __align__(16) float lp_w[];
     __shared__ float gs[kLpBwdChunk * kLpMaxE];                          // g_out and the positions of a chunk of entities
     __shared__ int ps[kLpBwdChunk * kLpMaxE];
@@ -179,10 +198,12 @@ __global__ void __launch_bounds__(kLpThreads) k_lp_bwd(const float* __restrict__
             __syncthreads();
             if (g_states && q0 == 0) {
                 for (int uu = 0; uu < n; ++uu) {
-                    float* drow = g_states + (uc + uu) * Ln * C;
+                    const int64_t row0 = RAGGED ? line_ptr[uc + uu] : (uc + uu) * Ln;
+                    const int cells = (RAGGED ? line_ptr[uc + uu + 1] - static_cast<int32_t>(row0) : Ln) * C;
+                    float* drow = g_states + row0 * C;
                     const float* gu = gs + uu * E;
                     const int* pu = ps + uu * E;
-                    for (int i = t; i < Ln * C; i += kLpThreads) {
+                    for (int i = t; i < cells; i += kLpThreads) {
                         const int l = i / C, c = i - l * C;
                         float s = 0.f;
                         if constexpr (WLDS) {                            // selects: the LDS reads of the channels e go out together
@@ -205,11 +226,14 @@ __global__ void __launch_bounds__(kLpThreads) k_lp_bwd(const float* __restrict__
             }
             if (slabs) {
                 for (int uu = 0; uu < n; ++uu) {
+                    const int64_t row0 = RAGGED ? line_ptr[uc + uu] : (uc + uu) * Ln;
 #pragma unroll
                     for (int a = 0; a < kLpAcc; ++a) {
                         const int p = ps[uu * E + ee[a]];
                         const bool valid = ok[a] && p != kLpNone;        // (an absent position reads line 0 and is not added)
-                        const float x = states[((uc + uu) * Ln + (valid ? p : 0) + jj[a]) * ld + cc[a]];
+                        float x;
+                        if constexpr (RAGGED) x = valid ? states[(row0 + p + jj[a]) * ld + cc[a]] : 0.f;      // (an entity may own no line: no read)
+                        else x = states[(row0 + (valid ? p : 0) + jj[a]) * ld + cc[a]];
                         acc[a] = valid ? fmaf(gs[uu * E + ee[a]], isb[a] ? 1.f : x, acc[a]) : acc[a];
                     }
                 }
@@ -241,6 +265,58 @@ bool lp_shape_ok(int64_t U, int32_t Ln, int32_t C, int32_t E, int32_t k) {
     return Ln - k + 1 <= kLpMaxP && static_cast<int64_t>(C) * k <= kLpMaxR;
 }
 
+
+// the ragged form: U entities over L rows, the longest of n_max; an entity may own no row and may be shorter than the filter
+bool lp_ragged_ok(int64_t U, int64_t L, int32_t n_max, int32_t C, int32_t E, int32_t k) {
+    if (U < 0 || U > (int64_t{1} << 30) || L < 0 || L >= (int64_t{1} << 31) || n_max < 0 || n_max > L || L > U * n_max) return false;
+    if (C < 1 || E < 1 || E > kLpMaxE || k < 1) return false;
+    return n_max - k + 1 <= kLpMaxP && static_cast<int64_t>(C) * k <= kLpMaxR;
+}
+
+// the forward of either form: `rows` is the mask [U][P] of Ln lines per entity, or line_ptr [U + 1] with Ln = the longest entity's lines
+template <bool RAGGED>
+int lp_run_fwd(const float* states, int64_t ld, const float* weight, const float* bias, const void* rows, int64_t U, int32_t Ln, int32_t C, int32_t E,
+               int32_t k, float* out, void* positions, recon_stream_t stream) {
+    const LpTiles tl = lp_tiles(Ln - k + 1 > 1 ? Ln - k + 1 : 1, C * k, E);
+    const size_t lds = static_cast<size_t>(E + tl.PC) * (tl.RC + 1) * sizeof(float);
+    hipLaunchKernelGGL(k_lp_fwd<RAGGED>, dim3(static_cast<unsigned>(U)), dim3(kLpThreads), lds, as_stream(stream), states, ld, weight, bias, rows, Ln, C,
+                       E, k, tl.PC, tl.RC, out, static_cast<uint8_t*>(positions));
+    RECON_CHECK_LAUNCH();
+    return RECON_OK;
+}
+
+// the backward of either form behind the argument checks; workspace: lp_groups(U) slabs
+template <bool RAGGED>
+int lp_run_bwd(const float* states, int64_t ld, const float* weight, const float* g_out, const void* positions, const int32_t* line_ptr, int64_t U,
+               int32_t Ln, int32_t C, int32_t E, int32_t k, float* g_states, float* g_w, float* g_b, void* workspace, recon_stream_t stream) {
+    hipStream_t st = as_stream(stream);
+    const bool params = g_w || g_b;
+    const int R = C * k, slab = E * (R + 1);
+    const int64_t G = lp_groups(U);
+    float* slabs = params ? static_cast<float*>(workspace) : nullptr;
+    const uint8_t* pb = static_cast<const uint8_t*>(positions);
+    if (g_states && E * R <= kLpBwdWeightFloats)
+        hipLaunchKernelGGL((k_lp_bwd<true, RAGGED>), dim3(static_cast<unsigned>(G)), dim3(kLpThreads), sizeof(float) * E * R, st, states, ld, weight, g_out,
+                           pb, U, lp_per(U), Ln, C, E, k, line_ptr, g_states, slabs);
+    else
+        hipLaunchKernelGGL((k_lp_bwd<false, RAGGED>), dim3(static_cast<unsigned>(G)), dim3(kLpThreads), 0, st, states, ld, weight, g_out, pb, U, lp_per(U),
+                           Ln, C, E, k, line_ptr, g_states, slabs);
+    RECON_CHECK_LAUNCH();
+    if (params) {
+        hipLaunchKernelGGL(k_lp_reduce, dim3(static_cast<unsigned>((slab + kLpThreads - 1) / kLpThreads)), dim3(kLpThreads), 0, st, slabs,
+                           static_cast<int32_t>(G), slab, R, g_w, g_b);
+        RECON_CHECK_LAUNCH();
+    }
+    return RECON_OK;
+}
+
+// zeros in every wanted parameter gradient of a call without an entity, no kernel
+int lp_zero_params(float* g_w, float* g_b, int32_t E, int32_t R, hipStream_t st) {
+    if (g_w && hipMemsetAsync(g_w, 0, sizeof(float) * E * R, st) != hipSuccess) return RECON_ERR_LAUNCH;
+    if (g_b && hipMemsetAsync(g_b, 0, sizeof(float) * E, st) != hipSuccess) return RECON_ERR_LAUNCH;
+    return RECON_OK;
+}
+
 }  // namespace
 }  // namespace recon
 
@@ -259,12 +335,7 @@ extern "C" int recon_line_pool_fwd(const float* states, int64_t ld, const float*
     if (!lp_shape_ok(U, Ln, C, E, k)) return RECON_ERR_UNSUPPORTED;
     if (U == 0) return RECON_OK;
     if (!states || !weight || !bias || !mask || !out || ld < C) return RECON_ERR_INVALID;
-    const LpTiles tl = lp_tiles(Ln - k + 1, C * k, E);
-    const size_t lds = static_cast<size_t>(E + tl.PC) * (tl.RC + 1) * sizeof(float);
-    hipLaunchKernelGGL(k_lp_fwd, dim3(static_cast<unsigned>(U)), dim3(kLpThreads), lds, as_stream(stream), states, ld, weight, bias,
-                       static_cast<const uint8_t*>(mask), Ln, C, E, k, tl.PC, tl.RC, out, static_cast<uint8_t*>(positions));
-    RECON_CHECK_LAUNCH();
-    return RECON_OK;
+    return lp_run_fwd<false>(states, ld, weight, bias, mask, U, Ln, C, E, k, out, positions, stream);
 }
 
 extern "C" int recon_line_pool_bwd(const float* states, int64_t ld, const float* weight, const float* g_out, const void* positions, int64_t U,
@@ -273,34 +344,52 @@ extern "C" int recon_line_pool_bwd(const float* states, int64_t ld, const float*
     using namespace recon;
     if (U < 0 || Ln < 1 || C < 1 || E < 1 || k < 1 || k > Ln) return RECON_ERR_INVALID;
     if (!lp_shape_ok(U, Ln, C, E, k)) return RECON_ERR_UNSUPPORTED;
-    hipStream_t st = as_stream(stream);
     const bool params = g_w || g_b;
-    const int R = C * k, slab = E * (R + 1);
-    if (U == 0) {                                                        // zeros in every wanted parameter gradient, no kernel
-        if (g_w && hipMemsetAsync(g_w, 0, sizeof(float) * E * R, st) != hipSuccess) return RECON_ERR_LAUNCH;
-        if (g_b && hipMemsetAsync(g_b, 0, sizeof(float) * E, st) != hipSuccess) return RECON_ERR_LAUNCH;
-        return RECON_OK;
-    }
+    if (U == 0) return lp_zero_params(g_w, g_b, E, C * k, as_stream(stream));
     if (!g_states && !params) return RECON_OK;
     if (!states || !weight || !g_out || !positions || ld < C) return RECON_ERR_INVALID;
     if (params) {
         if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15)) return RECON_ERR_INVALID;
         if (workspace_bytes < recon_line_pool_workspace_bytes(U, Ln, C, E, k)) return RECON_ERR_WORKSPACE;
     }
-    const int64_t G = lp_groups(U);
-    float* slabs = params ? static_cast<float*>(workspace) : nullptr;
-    const uint8_t* pb = static_cast<const uint8_t*>(positions);
-    if (g_states && E * R <= kLpBwdWeightFloats)
-        hipLaunchKernelGGL(k_lp_bwd<true>, dim3(static_cast<unsigned>(G)), dim3(kLpThreads), sizeof(float) * E * R, st, states, ld, weight, g_out, pb,
-                           U, lp_per(U), Ln, C, E, k, g_states, slabs);
-    else
-        hipLaunchKernelGGL(k_lp_bwd<false>, dim3(static_cast<unsigned>(G)), dim3(kLpThreads), 0, st, states, ld, weight, g_out, pb, U, lp_per(U), Ln,
-                           C, E, k, g_states, slabs);
-    RECON_CHECK_LAUNCH();
+    return lp_run_bwd<false>(states, ld, weight, g_out, positions, nullptr, U, Ln, C, E, k, g_states, g_w, g_b, workspace, stream);
+}
+
+extern "C" int recon_line_pool_ragged_supported(int64_t U, int64_t L, int32_t n_max, int32_t C, int32_t E, int32_t k) {
+    return recon::lp_ragged_ok(U, L, n_max, C, E, k) ? 1 : 0;
+}
+
+extern "C" size_t recon_line_pool_ragged_workspace_bytes(int64_t U, int64_t L, int32_t n_max, int32_t C, int32_t E, int32_t k) {
+    using namespace recon;
+    if (!lp_ragged_ok(U, L, n_max, C, E, k) || U == 0) return 0;
+    return align_up(static_cast<size_t>(lp_groups(U)) * E * (C * k + 1) * sizeof(float), 16);
+}
+
+extern "C" int recon_line_pool_ragged_fwd(const float* states, int64_t ld, const float* weight, const float* bias, const int32_t* line_ptr, int64_t U,
+                                          int64_t L, int32_t n_max, int32_t C, int32_t E, int32_t k, float* out, void* positions,
+                                          recon_stream_t stream) {
+    using namespace recon;
+    if (U < 0 || L < 0 || n_max < 0 || C < 1 || E < 1 || k < 1) return RECON_ERR_INVALID;
+    if (!lp_ragged_ok(U, L, n_max, C, E, k)) return RECON_ERR_UNSUPPORTED;
+    if (U == 0) return RECON_OK;
+    if ((!states && L > 0) || !weight || !bias || !line_ptr || !out || ld < C) return RECON_ERR_INVALID;
+    return lp_run_fwd<true>(states, ld, weight, bias, line_ptr, U, n_max, C, E, k, out, positions, stream);
+}
+
+extern "C" int recon_line_pool_ragged_bwd(const float* states, int64_t ld, const float* weight, const float* g_out, const void* positions,
+                                          const int32_t* line_ptr, int64_t U, int64_t L, int32_t n_max, int32_t C, int32_t E, int32_t k,
+                                          float* g_states, float* g_w, float* g_b, void* workspace, size_t workspace_bytes, recon_stream_t stream) {
+    using namespace recon;
+    if (U < 0 || L < 0 || n_max < 0 || C < 1 || E < 1 || k < 1) return RECON_ERR_INVALID;
+    if (!lp_ragged_ok(U, L, n_max, C, E, k)) return RECON_ERR_UNSUPPORTED;
+    const bool params = g_w || g_b;
+    if (U == 0) return lp_zero_params(g_w, g_b, E, C * k, as_stream(stream));
+    if (L == 0) g_states = nullptr;                                      // no row: nothing to write
+    if (!g_states && !params) return RECON_OK;
+    if ((!states && L > 0) || !weight || !g_out || !positions || !line_ptr || ld < C) return RECON_ERR_INVALID;
     if (params) {
-        hipLaunchKernelGGL(k_lp_reduce, dim3(static_cast<unsigned>((slab + kLpThreads - 1) / kLpThreads)), dim3(kLpThreads), 0, st, slabs,
-                           static_cast<int32_t>(G), slab, R, g_w, g_b);
-        RECON_CHECK_LAUNCH();
+        if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15)) return RECON_ERR_INVALID;
+        if (workspace_bytes < recon_line_pool_ragged_workspace_bytes(U, L, n_max, C, E, k)) return RECON_ERR_WORKSPACE;
     }
-    return RECON_OK;
+    return lp_run_bwd<true>(states, ld, weight, g_out, positions, line_ptr, U, n_max, C, E, k, g_states, g_w, g_b, workspace, stream);
 }

@@ -19,7 +19,8 @@ from .context_lstm import context_line_states
 from .sentence_lstm import pair_sentence_states
 from .transitions import pair_transitions
 from .relation_head import relation_logits
-from .line_pool import entity_line_pool
+from .line_pool import entity_line_pool, entity_line_pool_ragged
+from .ragged_lines import RaggedLines
 
 
 def _fused_encode_applies(m, sentence_input, entity_markers, active):
@@ -216,7 +217,10 @@ class EntityEmbedding(nn.Module):
 
     def forward(self, words, chars, conv_mask):
         """words [U, lines, len], chars [U, lines, cfs-1 + len*(max_char+cfs-1)], conv_mask bool [U, lines-ecfs+1] (True = padding
-        line) -> [U, entity_embed_dim]."""
+        line) -> [U, entity_embed_dim].  With a `RaggedLines` as the third argument: words [L, len], chars [L, .], the entities'
+        present lines alone (`forward_ragged`)."""
+        if isinstance(conv_mask, RaggedLines):
+            return self.forward_ragged(words, chars, conv_mask)
         U, lines = words.shape[0], words.shape[1]
         words = words.reshape(U * lines, words.shape[2])
         chars = chars.reshape(U * lines, chars.shape[2])
@@ -240,6 +244,39 @@ class EntityEmbedding(nn.Module):
             return entity_line_pool(h_n, ce.weight, ce.bias, conv_mask)
         conv = self.conv1d_entity(h_n.permute(0, 2, 1))
         conv = conv.masked_fill(conv_mask.unsqueeze(1), -float('inf'))
+        return conv.max(dim=2).values
+
+    def forward_ragged(self, words, chars, lines):
+        """words [L, len], chars [L, cfs-1 + len*(max_char+cfs-1)], lines a RaggedLines over the L rows -> [U, entity_embed_dim]: `forward`
+        without the padding lines.  The char-CNN and the line LSTM run over the L present lines, and
+        `entity_line_pool_ragged` finds an entity's states by offset; where conv1d_entity is not plain (or `fused_line_pool` is off) the
+        states are padded for the stock pool.  A padding line never reaches `forward`'s output (its position is masked to -inf in front
+        of the max) and gets a zero gradient, so the results are those of the padded call.  Dropout: the char embedding's factors are
+        drawn for L rows — the same distribution on another random stream than a padded batch draws from, the standing of
+        `packed_char_dropout`."""
+        if words.dim() != 2 or chars.dim() != 2 or words.shape[0] != lines.total or chars.shape[0] != lines.total:
+            raise ValueError("EntityEmbedding: with a RaggedLines, words and chars must be [L, .] with L = %d rows, got %s and %s"
+                             % (lines.total, tuple(words.shape), tuple(chars.shape)))
+        we = self.word_embeddings
+        plain = type(we) is nn.Embedding and we.max_norm is None and not we.sparse and not we.scale_grad_by_freq
+        emb = self.char_embeddings
+        draw = emb.draw_packed_keep if self.packed_char_dropout else emb.draw_keep
+        keep = draw(chars.shape[0], chars.shape[1], emb.embeddings.embedding_dim, chars.device)
+        char_feat = char_word_features(chars, emb.embeddings.weight, self.conv1d.weight, self.conv1d.bias, self.word_span, keep=keep,
+                                       padding_idx=emb.embeddings.padding_idx)
+        if plain:
+            h_n = context_line_states(self.lstm, char_feat, words, we.weight, padding_idx=we.padding_idx)
+        else:
+            _, (h_n, _) = self.lstm(torch.cat((we(words), char_feat), -1))
+            h_n = h_n.view(self.layers, 2, lines.total, self.hidden_dim)[-1].permute(1, 0, 2)
+        h_n = h_n.reshape(lines.total, 2 * self.hidden_dim)
+        ce = self.conv1d_entity
+        if (self.fused_line_pool and type(ce) is nn.Conv1d and ce.bias is not None and ce.stride == (1,) and ce.padding == (0,)
+                and ce.dilation == (1,) and ce.groups == 1):
+            return entity_line_pool_ragged(h_n, lines, ce.weight, ce.bias)
+        Ln = max(lines.n_max, ce.kernel_size[0] if isinstance(ce, nn.Conv1d) else 1)
+        conv = ce(lines.pad(h_n, Ln).permute(0, 2, 1))
+        conv = conv.masked_fill(lines.to_mask(Ln, Ln - conv.shape[2] + 1).unsqueeze(1), -float('inf'))
         return conv.max(dim=2).values
 
 
