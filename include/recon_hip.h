@@ -1651,6 +1651,51 @@ int recon_sent_conv_bwd(const void* sentence, int32_t sentence_bytes, const void
                         const void* max_at, const float* g_out, int32_t pos_padding_idx, float* g_pos_table_0, float* g_pos_table_1,
                         void* const* g_weights, void* const* g_biases, void* workspace, size_t workspace_bytes, recon_stream_t stream);
 
+/* --------------------------------------------------------------------------------------------
+ * E18 The distinct (sentence, pair markers) sequences of a stage-B batch (csrc/pair_groups.hip; recon_amd/pair_groups.py).
+ *     to_indices_with_real_entities_and_entity_nums_with_vertex_padding (parsing/legacy_sp_models.py:294-326) fills
+ *     entity_matrix[index, new_j] only for the edges a sentence has, every other pair slot keeps an all-zero marker row, and GPGNN.encode
+ *     (models/models.py:160-184) copies the sentence once per slot: the slots of a sentence whose marker rows are equal are one LSTM
+ *     input.  Grouping rule: two pair slots of the SAME sentence share a sequence exactly when their marker rows are equal element by
+ *     element (not "all zero"); slots of different sentences never share.  The representative of a group is its lowest c, and the S_d
+ *     distinct sequences are numbered in (b, lowest c) order.  Selection, ordering and copying only; no global atomics, no hash, bitwise
+ *     reproducible; every index read back from memory is clamped before it is used as an address.  Status codes are those of the
+ *     E8 - E17 entries; nothing is allocated inside the library.
+ * ------------------------------------------------------------------------------------------*/
+/* 1 when markers [B][C][T] (parsing/legacy_sp_models.py:294-326) are grouped by the kernels: 1 <= B <= 8192 sentences per call,
+ * 1 <= C <= 256 pair slots, T >= 1 and B C T below 2^31 - 4096.  The reference's batch is 50 x 72 x 36. */
+int recon_pair_groups_supported(int64_t B, int64_t C, int64_t T);
+/* Bytes of recon_pair_groups_build's workspace (parsing/legacy_sp_models.py:294-326): first and local_rank int32 [B C] and counts
+ * int32 [B]; 16-byte aligned, any contents; 0 for a refused shape. */
+size_t recon_pair_groups_workspace_bytes(int64_t B, int64_t C, int64_t T);
+/* The grouping inside each sentence (parsing/legacy_sp_models.py:294-326; models/models.py:160-184), one launch, one workgroup per
+ * sentence: markers [B][C][T] contiguous, of marker_bytes 1, 4 or 8 (int8 as the resident dataset stores them, int32, int64), compared
+ * exactly, word-wise, every row against the rows in front of it.  Writes first int32 [B C] (the lowest c' of the sentence whose row
+ * equals slot c's), local_rank int32 [B C] (the number of the slot's group among the sentence's groups, in lowest-c order) and counts
+ * int32 [B] (the sentence's distinct rows). */
+int recon_pair_groups_local(const void* markers, int32_t marker_bytes, int64_t B, int64_t C, int64_t T, int32_t* first, int32_t* local_rank,
+                            int32_t* counts, recon_stream_t stream);
+/* The maps of a batch (parsing/legacy_sp_models.py:294-326; models/models.py:160-184), two launches: recon_pair_groups_local into the
+ * workspace, then ONE workgroup scans counts in b order into seq_ptr int32 [B + 1] and writes pair_seq int32 [B C] (the sequence of every
+ * pair), seq_pair int32 [total] (the flat pair index b C + c of every sequence's representative) and the rows the encoder reads,
+ * sentence_d [total][T] and markers_d [total][T] of index_bytes 4 or 8: the representatives' rows of sentence [B][T] (index_bytes wide)
+ * and of markers.  `total` is the caller's S_d (B <= total <= B C, else RECON_ERR_INVALID): when the scan finds another one, status[0]
+ * (device int32, zeroed by the caller) is set to 1, pair_seq is clamped below total, rows between the two totals are zeros and nothing
+ * is written at or behind row total.  total < 0: seq_ptr and pair_seq alone (seq_ptr[B] is S_d; the other outputs may be NULL). */
+int recon_pair_groups_build(const void* sentence, int32_t index_bytes, const void* markers, int32_t marker_bytes, int64_t B, int64_t C, int64_t T,
+                            int64_t total, int32_t* seq_pair, int32_t* pair_seq, int32_t* seq_ptr, void* sentence_d, void* markers_d, int32_t* status,
+                            void* workspace, size_t workspace_bytes, recon_stream_t stream);
+/* out [n_pairs][F] = rows[pair_seq[p]][:] (models/models.py:160-184: every pair slot's state from its sequence's), fp32, one launch of
+ * 16-byte stores (element stores where F is no multiple of 4 or a base is not 16-byte aligned).  pair_seq is clamped into [0, S_d).
+ * n_pairs F and S_d F below 2^31 - 4096.  n_pairs == 0: nothing is launched. */
+int recon_pair_groups_expand(const float* rows, const int32_t* pair_seq, int64_t n_pairs, int64_t S_d, int32_t F, float* out, recon_stream_t stream);
+/* The backward of recon_pair_groups_expand (models/models.py:160-184), one launch: g_rows[j][:] = the sum of g_out[b C + c][:] over the
+ * slots c of sequence j's sentence b = seq_pair[j] / C with pair_seq[b C + c] == j, c ascending: one fp32 chain per element, one wave per
+ * (sequence, chunk of columns), no atomics; it destroys nothing (any number of backwards per forward, the same bits each time).
+ * S_d == 0: nothing is launched. */
+int recon_pair_groups_reduce(const float* g_out, const int32_t* pair_seq, const int32_t* seq_pair, int64_t B, int64_t C, int64_t S_d, int32_t F,
+                             float* g_rows, recon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -397,6 +397,13 @@ SYMBOLS = [
                                      C.c_int64] + [C.c_int32] * 4 + [c_f32p, C.c_void_p, c_f32p, C.c_int32, c_f32p, c_f32p,
                                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t,
                                                                      C.c_void_p]),
+    ("recon_pair_groups_supported", C.c_int, [C.c_int64] * 3),
+    ("recon_pair_groups_workspace_bytes", C.c_size_t, [C.c_int64] * 3),
+    ("recon_pair_groups_local", C.c_int, [C.c_void_p, C.c_int32] + [C.c_int64] * 3 + [c_i32p] * 3 + [C.c_void_p]),
+    ("recon_pair_groups_build", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_int64] * 4 + [c_i32p] * 3 + [C.c_void_p] * 2
+                                         + [c_i32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("recon_pair_groups_expand", C.c_int, [c_f32p, c_i32p, C.c_int64, C.c_int64, C.c_int32, c_f32p, C.c_void_p]),
+    ("recon_pair_groups_reduce", C.c_int, [c_f32p, c_i32p, c_i32p] + [C.c_int64] * 3 + [C.c_int32, c_f32p, C.c_void_p]),
 ]
 
 _lib = None

@@ -41,9 +41,11 @@ class ContextAware(nn.Module):
         self.linear2 = nn.Linear(in_features=p['units1'] * 4, out_features=n_out)                     # :49-51
         nn.init.xavier_uniform_(self.linear2.weight)
 
-    # fused_sentence_encoder, packed_word_dropout: GPGNN's switches of the same names (`gpgnn.pair_states` reads them).
+    # fused_sentence_encoder, packed_word_dropout, distinct_pair_sequences: GPGNN's switches of the same names (`gpgnn.pair_states` reads
+    # them).  distinct_pair_sequences is an opt-in for GPGNN's reason: under packed dropout the pair slots that share a sequence share one draw.
     fused_sentence_encoder = True
     packed_word_dropout = False
+    distinct_pair_sequences = False
     # fused_ghost_attention: run the attention over ghosts as `pair_context_attention` (csrc/pair_attn.hip) whenever linear1 is a plain
     # bias-free nn.Linear; DESIGN.md section 30 has the measurement behind the default.
     fused_ghost_attention = True

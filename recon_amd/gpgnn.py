@@ -21,6 +21,7 @@ from .transitions import pair_transitions
 from .relation_head import relation_logits
 from .line_pool import entity_line_pool, entity_line_pool_ragged
 from .ragged_lines import RaggedLines
+from .pair_groups import PairGroups
 
 
 def _fused_encode_applies(m, sentence_input, entity_markers, active):
@@ -35,14 +36,17 @@ def pair_states(m, sentence_input, entity_markers):
     """models/models.py:160-183 (and models/baselines.py:62-84, the same lines): one LSTM pass per (sentence, ordered entity pair) of a model
     with word_embedding, pos_embedding, dropout1 and rnn1; returns [B, C, 2*units1], what `GPGNN.encode` hands to its dropout2 and
     `ContextAware` to its attention.  `pair_sentence_states` where `fused_sentence_encoder` / `packed_word_dropout` allow, the stock ops
-    otherwise."""
+    otherwise; there, with `distinct_pair_sequences`, over the `PairGroups` of the batch's markers."""
     B, C = sentence_input.size(0), m.MAX_EDGES_PER_GRAPH
     active = m.training and m.dropout1.p > 0
     if _fused_encode_applies(m, sentence_input, entity_markers, active):
         we = m.word_embedding
-        keep = draw_packed_keep(B * C, m.max_sent_len, we.embedding_dim, m.dropout1.p, sentence_input.device) if active else None
+        # distinct_pair_sequences: the distinct (sentence, marker row) sequences alone run, one dropout draw each (DESIGN.md section 35)
+        groups = PairGroups.from_markers(sentence_input, entity_markers) if getattr(m, "distinct_pair_sequences", False) and B * C else None
+        rows = B * C if groups is None else groups.total
+        keep = draw_packed_keep(rows, m.max_sent_len, we.embedding_dim, m.dropout1.p, sentence_input.device) if active else None
         return pair_sentence_states(m.rnn1, sentence_input, entity_markers, we.weight, m.pos_embedding.weight, keep,
-                                    pos_padding_idx=m.pos_embedding.padding_idx)
+                                    pos_padding_idx=m.pos_embedding.padding_idx, groups=groups)
     expanded = torch.transpose(sentence_input.expand(C, B, m.max_sent_len), 0, 1)
     word = m.word_embedding(expanded.contiguous().view(-1, m.max_sent_len)).view(B, C, m.max_sent_len, -1)
     word = m.dropout1(word)
@@ -93,8 +97,14 @@ class GPGNN(nn.Module):
     # is frozen and dropout1 is inactive or drawn as packed bits; DESIGN.md section 21 says why this is the default it is.
     # packed_word_dropout (default False): draw dropout1 as packed bits (`draw_packed_keep`), so that training batches run the kernels too.
     # Same distribution, another random stream than the reference's nn.Dropout call: an opt-in, like EntityEmbedding.packed_char_dropout.
+    # distinct_pair_sequences (default False): wherever the fused encoder applies, encode each distinct (sentence, marker row) sequence of
+    # the batch once (`PairGroups.from_markers`, csrc/pair_groups.hip) and copy its state to the pair slots that share it.  In eval mode
+    # and at p = 0 the values are the dense call's.  Under `packed_word_dropout` the slots that share a sequence share ONE draw: each
+    # pair's factors still have dropout's distribution, but the joint distribution over a sentence's copies is another one (the dense
+    # call draws every copy independently).  That is why it is an opt-in.  DESIGN.md section 35.
     fused_sentence_encoder = True
     packed_word_dropout = False
+    distinct_pair_sequences = False
 
     def encode(self, sentence_input, entity_markers):
         """models/models.py:160-184: one LSTM pass per (sentence, ordered entity pair); returns [B, C, 2*units1]."""

@@ -1,14 +1,15 @@
 """The sentence encoder's pair LSTM (`GPGNN.encode`, models/models.py:160-184) as one device op:
 
     from recon_amd import pair_sentence_states
-    states = pair_sentence_states(rnn, sentence, markers, word_table, pos_table, keep=None, pos_padding_idx=0)   # [B, C, 2H]
+    states = pair_sentence_states(rnn, sentence, markers, word_table, pos_table, keep=None, pos_padding_idx=0, groups=None)   # [B, C, 2H]
     x[b, c, t]   = (word_table[sentence[b, t]] * keep[b C + c, t] | pos_table[markers[b, c, t]])                # never written
     states[b, c] = (h of the forward direction after t = T - 1 | h of the reverse direction after t = 0)
 
 rnn an nn.LSTM, sentence [B, T] and markers [B, C, T] int64 or int32 (strided views with unit last stride are read in place), word_table
 [Vw, Dw], pos_table [Vp, P]; keep None, a `PackedKeep` over [B C, T, Dw] (`char_features.draw_packed_keep` / `pack_keep`) or an fp32
-[B, C, T, Dw] tensor of factors.  With fp32 GPU tensors, a one-layer bidirectional batch_first nn.LSTM with bias, without projection and
-with dropout 0, a word_table that requires no gradient, keep None or packed, at most MAX_POS_ROWS rows in pos_table and a shape
+[B, C, T, Dw] tensor of factors; groups None or a `PairGroups` (pair_groups.py: only the batch's distinct sequences run, at B' = S_d and
+C' = 1, and `groups.expand` gives every pair its sequence's state).  With fp32 GPU tensors, a one-layer
+bidirectional batch_first nn.LSTM with bias, without projection and with dropout 0, a word_table that requires no gradient, keep None or packed, at most MAX_POS_ROWS rows in pos_table and a shape
 `recon_sent_lstm_supported` takes (H up to 256), the kernels of csrc/sent_lstm.hip run: two launches forward, five backward, all fp32 on the
 fp32 MFMA, bitwise reproducible.  Neither the C copies of the sentence, nor the gathered rows, their product with keep, the concatenation
 or the [B C, T, 2H] outputs are written; for the backward the forward keeps gates and cell state (5 H floats per direction, sequence and
@@ -123,13 +124,33 @@ def _fused(rnn, sentence, markers, word_table, pos_table, keep):
     return bool(_lib.lib().recon_sent_lstm_supported(B, C, T, word_table.shape[1], pos_table.shape[1], rnn.hidden_size))
 
 
-def pair_sentence_states(rnn, sentence, markers, word_table, pos_table, keep=None, pos_padding_idx=0):
+def _grouped(rnn, sentence, markers, word_table, pos_table, keep, pos_padding_idx, groups):
+    """The call over the distinct sequences of `groups`: the op itself at B' = S_d, C' = 1 over the compact copies —
+    the kernels or `_chain`, by the same rules — and `groups.expand` behind it."""
+    from .pair_groups import PairGroups
+    if not isinstance(groups, PairGroups):
+        raise ValueError("pair_sentence_states: groups must be a PairGroups or None, got %s" % type(groups).__name__)
+    sentence_d, markers_d = groups.compact(sentence, markers)
+    S_d, T, Dw = groups.total, sentence.shape[1], word_table.shape[1]
+    if keep is not None and not isinstance(keep, PackedKeep):
+        if not torch.is_tensor(keep) or tuple(keep.shape) != (S_d, 1, T, Dw):
+            raise ValueError("pair_sentence_states: with groups, keep must be [S_d, 1, T, Dw] = [%d, 1, %d, %d] (sequence j has one draw), got %s"
+                             % (S_d, T, Dw, tuple(getattr(keep, "shape", ()))))
+    rows = pair_sentence_states(rnn, sentence_d, markers_d, word_table, pos_table, keep, pos_padding_idx)
+    return groups.expand(rows.reshape(S_d, rows.shape[-1]))
+
+
+def pair_sentence_states(rnn, sentence, markers, word_table, pos_table, keep=None, pos_padding_idx=0, groups=None):
     """nn.LSTM, [B, T] ids, [B, C, T] ids, [Vw, Dw], [Vp, P] -> [B, C, 2H]: the final hidden states of both directions of every (sentence,
     entity pair) sequence (models/models.py:160-184; for the LSTMs only the stock ops take, whatever those lines give), differentiable in
     pos_table and the LSTM's parameters (and, through the stock ops, in a word_table that requires a gradient: a plain table, no padding
     row).  keep: None, a `PackedKeep` over [B C, T, Dw] or fp32 [B, C, T, Dw] factors multiplied onto the gathered word rows.
     pos_padding_idx: that row of pos_table's gradient is zero, as with nn.Embedding; its values are read as they are.  B C == 0 gives an
-    empty [B, C, 2H] without a launch."""
+    empty [B, C, 2H] without a launch.  groups: a `PairGroups` over the [B, C] pairs: the S_d distinct sequences alone are encoded (the same
+    op over the compact copies at B' = S_d, C' = 1) and `groups.expand` gives every pair its sequence's state; keep then has S_d rows (a
+    `PackedKeep` over [S_d, T, Dw], or fp32 [S_d, 1, T, Dw]): sequence j has one draw."""
+    if groups is not None and sentence.dim() == 2 and markers.dim() == 3 and sentence.shape[0] * markers.shape[1] > 0:
+        return _grouped(rnn, sentence, markers, word_table, pos_table, keep, pos_padding_idx, groups)
     if not isinstance(rnn, nn.LSTM):
         raise ValueError("pair_sentence_states: rnn must be an nn.LSTM, got %s" % type(rnn).__name__)
     if sentence.dim() != 2 or sentence.dtype not in (torch.int64, torch.int32):

@@ -26,7 +26,9 @@ forces the torch path.  A batch beyond `recon_stage_b_supported` goes to the tor
 
 Host reads: none in `take` and `append`.  `run_epoch` validates an `order` once where it enters (one min/max read per epoch,
 IndexError outside [0, N)); the kernel also clamps what it reads from `order` into [0, N), so that a value never becomes an address.
-`EpochRows.result()` is one read of 16 bytes.  With a `ContextBatcher` the batcher's header read stays (one per iteration).
+`EpochRows.result()` is one read of 16 bytes.  With a `ContextBatcher` the batcher's header read stays (one per iteration).  For a model with
+`distinct_pair_sequences` set, `run_epoch` reads the batches' distinct-sequence totals once per epoch and the status word of
+`pair_groups` once behind the loop.
 """
 import collections
 import contextlib
@@ -34,7 +36,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, pair_groups
 from .objective import relation_objective
 from .sentence_conv import ids_prechecked
 
@@ -80,6 +82,7 @@ class StageBData:
             setattr(self, name, self.arrays.get(name))
         self.device = self.sentences.device
         self.N, self.C, self.T = self.markers.shape
+        self._distinct_counts = None
 
     @classmethod
     def from_indices(cls, as_indices, surface_ids=None):
@@ -113,6 +116,13 @@ class StageBData:
     def to(self, device):
         device = torch.device(device)
         return StageBData({k: v.to(device) for k, v in self.arrays.items()}, self.kept_pairs)
+
+    def distinct_counts(self):
+        """int32 [N] on the data's device: every sentence's distinct marker rows (`pair_groups.distinct_counts` over the resident int8
+        markers, in chunks), computed once and kept: what `run_epoch` sums per batch for a model with `distinct_pair_sequences`."""
+        if self._distinct_counts is None:
+            self._distinct_counts = pair_groups.distinct_counts(self.markers)
+        return self._distinct_counts
 
     # ------------------------------------------------------------------------------------------------------------- take
     def take(self, order, start, count, index_dtype=torch.int64):
@@ -246,7 +256,11 @@ def run_epoch(model, data, batch_size, *, order=None, batcher=None, optimizer=No
 
     Over a `PairData` (recon_amd/pair_data.py: the per-pair baselines LSTM, CNN and PCNN) the model is called as
     `model(*sl.model_args())`, there is no batcher (ValueError), and the ids are checked once, not once per forward: `data.check_model(model)`
-    on the host in front, and the loop inside `sentence_conv.ids_prechecked()`, whose one read of the status word comes behind the loop."""
+    on the host in front, and the loop inside `sentence_conv.ids_prechecked()`, whose one read of the status word comes behind the loop.
+
+    A model with `distinct_pair_sequences` set: the dataset's per-sentence distinct counts are computed once
+    (`data.distinct_counts()`), the per-batch totals are read once per epoch, and every batch runs inside `pair_groups.known_total`, so
+    that `PairGroups.from_markers` reads nothing; the status word is read once behind the loop (ValueError at a mismatch)."""
     if not isinstance(batch_size, int) or batch_size < 1:
         raise ValueError("run_epoch: batch_size must be an integer >= 1, got %r" % (batch_size,))
     iterations = data.N // batch_size
@@ -263,10 +277,18 @@ def run_epoch(model, data, batch_size, *, order=None, batcher=None, optimizer=No
         check_model(model)
     elif batcher is not None and (data.entity_indices is None or data.surface_ids is None):
         raise ValueError("run_epoch: a batcher needs a dataset with entity_indices and surface_ids")
-    with ids_prechecked() if check_model is not None else contextlib.nullcontext():
+    totals = None
+    if check_model is None and getattr(model, "distinct_pair_sequences", False) and iterations:
+        # the batches' distinct sequences from the dataset's cached per-sentence counts: the epoch's one host read for `PairGroups`
+        counts = data.distinct_counts()
+        used = counts[:iterations * batch_size] if order is None else counts[order[:iterations * batch_size]]
+        totals = used.view(iterations, batch_size).sum(1).tolist()
+    outer = ids_prechecked() if check_model is not None else (pair_groups.known_total(None) if totals is not None else contextlib.nullcontext())
+    with outer:
         for i in range(iterations):
             sl = data.take(order, i * batch_size, batch_size, index_dtype)
-            with contextlib.nullcontext() if optimizer is not None else torch.no_grad():
+            with contextlib.nullcontext() if optimizer is not None else torch.no_grad(), \
+                    pair_groups.known_total(int(totals[i])) if totals is not None else contextlib.nullcontext():
                 if optimizer is not None:
                     optimizer.zero_grad()
                 if hasattr(sl, "model_args"):
