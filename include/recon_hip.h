@@ -1696,6 +1696,44 @@ int recon_pair_groups_expand(const float* rows, const int32_t* pair_seq, int64_t
 int recon_pair_groups_reduce(const float* g_out, const int32_t* pair_seq, const int32_t* seq_pair, int64_t B, int64_t C, int64_t S_d, int32_t F,
                              float* g_rows, recon_stream_t stream);
 
+/* ---- E19: the distinct word forms of an entity-context batch (recon_amd/word_forms.py, csrc/word_forms.hip, csrc/ctx_batch.hip) ----------
+ * `get_char_indices` (utils/context_utils.py:265-283) lays every word slot of a context line out as [cfs - 1 pads][max_char_len ids]
+ * [cfs - 1 pads], and the char-CNN (models/models.py:57-61) computes a slot's feature from that window alone: it is run once per distinct
+ * window (a form) and the feature rows are copied to the forms' slots (recon_pair_groups_expand with slot_form as the map). */
+/* Slots per piece of the backward below (models/models.py:57-61; a constant of the build). */
+int32_t recon_word_forms_piece(void);
+/* Scratch of recon_word_forms_reduce (models/models.py:57-61): (n_slots / piece + S_d + 1) F floats; 0 for a shape it refuses. */
+size_t recon_word_forms_reduce_workspace_bytes(int64_t n_slots, int64_t S_d, int32_t F);
+/* The backward of the copy (models/models.py:57-61: the gradient of a form's feature row is the sum of its slots'), two launches:
+ * g_rows[f][:] = the sum of g_out[s][:] over s = form_slots[form_ptr[f] .. form_ptr[f + 1]) in list order, fp32.  form_ptr int32
+ * [S_d + 1], form_slots int32 [n_slots] (the slots of form 0, then of form 1, ...).  A segment is cut into pieces of
+ * recon_word_forms_piece() slots from ITS start; a piece is one fp32 chain per element, and a form's pieces are added in piece order: the
+ * result depends on a form's own list alone, is the same bits from run to run, and nothing is destroyed.  A form without a slot gets
+ * zeros.  form_ptr and form_slots are clamped into [0, n_slots] and [0, n_slots) before use.  n_slots F, S_d F and the scratch below
+ * 2^31 - 4096 floats.  S_d == 0: nothing is launched. */
+int recon_word_forms_reduce(const float* g_out, const int32_t* form_ptr, const int32_t* form_slots, int64_t n_slots, int64_t S_d, int32_t F, float* g_rows,
+                            void* workspace, size_t workspace_bytes, recon_stream_t stream);
+/* Scratch of the two entries below (utils/context_utils.py:265-283): 3 num_forms int32 (flags, ranks, the list of present forms); 0 for a num_forms they refuse. */
+size_t recon_ctx_batch_forms_scratch_bytes(int64_t num_forms);
+/* Between recon_ctx_batch_index and the host's read of the header (utils/context_utils.py:265-283 under :365-385): which of the tables'
+ * num_forms word forms the batch holds.  tok_form int32 [V] is every token's form (form 0: the all-pad window of an empty word slot),
+ * form_chars int32 [num_forms][max_char_len] the forms' char ids.  Three launches on `stream`: the flags are cleared, every token of
+ * every line of the batch stores 1 into its form's flag (and a line shorter than T_b into form 0's; the sizes are read from the header
+ * on the device; ragged = 1: the padding lines do not exist), and one workgroup scans the flags: the batch numbers its forms by ascending
+ * table form.  header[7] = S_d.  tables and dims are recon_ctx_batch_index's; n_pairs bounds the entities walked. */
+int recon_ctx_batch_forms_count(const void* const* tables, const int64_t* dims, const int32_t* tok_form, const int32_t* form_chars, int64_t num_forms,
+                                const int64_t* unique_entities, const int32_t* unique_info, int64_t n_pairs, int32_t ragged, int32_t* scratch,
+                                int32_t* header, recon_stream_t stream);
+/* recon_ctx_batch_fill (ragged = 0: n_rows = U P_b and context_mask; line_ptr and row_entity unused) or recon_ctx_batch_fill_ragged
+ * (ragged = 1: n_rows = L, line_ptr and row_entity; context_mask unused) with the char block as its distinct windows
+ * (utils/context_utils.py:265-283): form_rows [S_d][2 (cfs - 1) + max_char_len] of index_bytes, one `W = 1` row of
+ * recon_char_features_fwd per form, and slot_form int32 [n_rows T_b], the form of every word slot.  The dense [n_rows][W] block is not
+ * written.  scratch is what recon_ctx_batch_forms_count left for this batch, S_d the header's eighth word. */
+int recon_ctx_batch_fill_forms(const void* const* tables, const int64_t* dims, const int32_t* tok_form, const int32_t* form_chars, int64_t num_forms,
+                               const int32_t* scratch, const int64_t* unique_entities, const int32_t* unique_info, int64_t U, int64_t n_rows, int32_t P_b,
+                               int32_t T_b, int64_t S_d, int32_t ragged, int32_t index_bytes, void* context_words, void* context_mask, int32_t* line_ptr,
+                               int32_t* row_entity, void* form_rows, int32_t* slot_form, recon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ from .relation_head import relation_logits  # noqa: E402,F401
 from .line_pool import entity_line_pool, entity_line_pool_ragged  # noqa: E402,F401
 from .ragged_lines import RaggedLines  # noqa: E402,F401
 from .pair_groups import PairGroups  # noqa: E402,F401
+from .word_forms import WordForms, word_form_features  # noqa: E402,F401
 from .objective import RelationMetrics, relation_objective  # noqa: E402,F401
 from .context_batch import ContextBatcher, ContextTables, StageBBatch  # noqa: E402,F401
 from .stage_b import EpochRows, StageBData, StageBSlice, run_epoch  # noqa: E402,F401

@@ -404,6 +404,15 @@ SYMBOLS = [
                                          + [c_i32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("recon_pair_groups_expand", C.c_int, [c_f32p, c_i32p, C.c_int64, C.c_int64, C.c_int32, c_f32p, C.c_void_p]),
     ("recon_pair_groups_reduce", C.c_int, [c_f32p, c_i32p, c_i32p] + [C.c_int64] * 3 + [C.c_int32, c_f32p, C.c_void_p]),
+    ("recon_word_forms_piece", C.c_int32, []),
+    ("recon_word_forms_reduce_workspace_bytes", C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    ("recon_word_forms_reduce", C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int64, C.c_int64, C.c_int32, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("recon_ctx_batch_forms_scratch_bytes", C.c_size_t, [C.c_int64]),
+    ("recon_ctx_batch_forms_count", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), c_i32p, c_i32p, C.c_int64, c_i64p, c_i32p, C.c_int64, C.c_int32,
+                                              c_i32p, c_i32p, C.c_void_p]),
+    ("recon_ctx_batch_fill_forms", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), c_i32p, c_i32p, C.c_int64, c_i32p, c_i64p, c_i32p, C.c_int64,
+                                             C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, c_i32p, c_i32p,
+                                             C.c_void_p, c_i32p, C.c_void_p]),
 ]
 
 _lib = None

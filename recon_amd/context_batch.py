@@ -32,6 +32,15 @@ path, the path beyond the kernels' limit and what the randomised GPU test compar
 entities' present lines one after another, L = the sum of their line counts (the header's seventh word: still one host read), and
 context_mask is a `RaggedLines` (line_ptr int32 [U + 1]) in the mask's place, which `EntityEmbedding.forward` takes as its third argument.
 The default, False, is the reference's padded form.
+
+`batch(..., word_forms=True)` hands the char block over as its distinct word windows: context_chars is a `WordForms` —
+chars [S_d, cfs - 1 + word_span], one row per distinct window of the batch, and slot_form [rows T_b] with its occurrence lists — in the
+padded form (rows = U P_b) and in the ragged one (rows = L).  The tables carry a form id per token (`tok_form`; two tokens that agree in
+their first `max_char_len` characters share a form, form 0 is the all-pad row of an empty slot) and the forms' rows (`form_chars`); the
+batch numbers the forms it holds by ascending table form id.  S_d travels in the header's eighth word: still one host read, and the
+dense [rows, W] block is never written.  `EntityEmbedding.forward` takes the `WordForms` where it takes the block.  Under dropout every
+occurrence of a form then shares one draw, which is why the default is False.  `ContextBatcher(tables, ragged_lines=, word_forms=)` sets
+what `batch` falls back to.
 """
 import ctypes as C
 import re
@@ -41,6 +50,7 @@ import torch
 
 from . import _lib
 from .ragged_lines import RaggedLines
+from .word_forms import WordForms, occurrence_lists
 
 ALL_ZERO, UNKNOWN = "ALL_ZERO", "_UNKNOWN"
 # embedding_utils.get_idx (utils/embedding_utils.py:13-16, :87-88): three spellings mapped onto a vocabulary entry
@@ -106,9 +116,14 @@ class ContextTables:
     """What a dataset's batches are cut from; built by `ContextTables.build`, moved by `.to(device)`."""
 
     def __init__(self, arrays, dims, gat_mode):
+        arrays = dict(arrays)                                          # (the caller's dict stays as it is)
         self.arrays, self.dims, self.gat_mode = arrays, dict(dims), gat_mode
         self.device = arrays["tok_flat"].device
         d = self.dims
+        if "tok_form" not in arrays:                                   # arrays from before the forms: derived once, on the host, where the tables are made
+            tok_form, form_chars = _forms_of(arrays["tok_chars"].cpu().numpy(), d["pad_char"])
+            arrays["tok_form"], arrays["form_chars"] = torch.from_numpy(tok_form).to(self.device), torch.from_numpy(form_chars).to(self.device)
+        d["NFm"] = int(arrays["form_chars"].shape[0])
         self._dims_c = (C.c_int64 * 12)(d["Ne"], d["S"], d["V"], d["L"], d["NF"], d["max_sent_len"], d["max_num_contexts"], d["max_char_len"],
                                         d["conv_filter_size"], d["pad_char"], d["G"], d["Ng"])
         self._ptrs_c = _lib.ptr_array([arrays.get(k) for k in _TABLES]) if self.device.type == "cuda" else None
@@ -188,7 +203,8 @@ class ContextTables:
                 for k in range(2):
                     surface_ids[i, j, k] = surface(list(sf[i, j, k]))
         i32 = lambda a, shape=None: torch.from_numpy(np.asarray(a if len(a) else [0], dtype=np.int32).reshape(shape or -1))
-        arrays = {"ent_line_ptr": i32(ent_line_ptr), "ent_max_len": i32(ent_max_len), "line_start": i32(line_start), "line_len": i32(line_len),
+        tok_form, form_chars = _forms_of(np.asarray(tok_chars, dtype=np.int32).reshape(-1, max_char_len), pad)
+        arrays = {"tok_form": torch.from_numpy(tok_form), "form_chars": torch.from_numpy(form_chars), "ent_line_ptr": i32(ent_line_ptr), "ent_max_len": i32(ent_max_len), "line_start": i32(line_start), "line_len": i32(line_len),
                   "sf_start": i32(sf_start), "sf_len": i32(sf_len), "tok_flat": i32(flat), "tok_word": i32(tok_word),
                   "tok_chars": i32(tok_chars, (-1, max_char_len))}
         dims = {"Ne": Ne, "S": len(sf_start), "V": len(tok_word), "L": L, "NF": len(flat), "max_sent_len": max_sent_len,
@@ -230,9 +246,21 @@ class ContextTables:
         return ContextTables({k: v.to(device) for k, v in self.arrays.items()}, self.dims, self.gat_mode)
 
 
+def _forms_of(tok_chars, pad):
+    """(tok_form int32 [V], form_chars int32 [NFm, mcl]) of tok_chars [V, mcl]: the distinct rows numbered from 1 in first-occurrence
+    order behind form 0, the all-pad row of an empty word slot (a token whose row is all pad takes form 0: no two forms are equal)."""
+    mcl = tok_chars.shape[1]
+    ids = {(pad,) * mcl: 0}
+    tok_form = np.empty(tok_chars.shape[0], dtype=np.int32)
+    for i, row in enumerate(tok_chars.tolist()):
+        tok_form[i] = ids.setdefault(tuple(row), len(ids))
+    return (tok_form if len(tok_form) else np.zeros(1, np.int32)), np.asarray(list(ids), dtype=np.int32).reshape(len(ids), mcl)
+
+
 class StageBBatch:
     """The inputs of one stage-B forward; the fields carry the names of the arguments of RECON.forward.  With `ragged_lines=True`
-    context_words and context_chars are [L, .] and context_mask is a `RaggedLines`, in the same three positions."""
+    context_words and context_chars are [L, .] and context_mask is a `RaggedLines`, in the same three positions; with `word_forms=True`
+    context_chars is a `WordForms`."""
     __slots__ = ("unique_entities", "entity_indices", "context_words", "context_chars", "context_mask", "entities_position",
                  "max_occurred_entity_in_batch_pos", "gat_entity_embeddings", "nonzero_gat_entity_embeddings", "nonzero_entity_pos", "gat_mode")
 
@@ -265,18 +293,23 @@ def _raise_flags(err, tables):
 
 
 class ContextBatcher:
-    def __init__(self, tables):
-        self.tables = tables
+    def __init__(self, tables, ragged_lines=False, word_forms=False):
+        """ragged_lines, word_forms: what `batch` does where its arguments of these names are left at None."""
+        self.tables, self.ragged_lines, self.word_forms = tables, bool(ragged_lines), bool(word_forms)
 
-    def batch(self, entity_indices, surface_ids, index_dtype=torch.int64, ragged_lines=False):
+    def batch(self, entity_indices, surface_ids, index_dtype=torch.int64, ragged_lines=None, word_forms=None):
         """entity_indices int64 [B, C, 2] (values -1 .. Ne - 1) and surface_ids [B, C, 2] (of `ContextTables.build`), both on the tables'
         device -> StageBBatch.  One host read per call (the header: sizes, the most frequent entity's position, error flags), made
         before the model's forward is queued.  index_dtype: of context_words and context_chars (torch.int64, the reference's, or
         torch.int32: the char-CNN and line-LSTM ops take both, and the char block is half the bytes).
         ragged_lines: context_words [L, T_b] and context_chars [L, W] without the padding lines and a `RaggedLines` as context_mask.
+        word_forms: context_chars as a `WordForms` over the rows of either form (S_d in the header: still one read).  None for either:
+        the constructor's value.
         IndexError for an id or a surface id outside its table, KeyError for an entity the GAT table lacks, ValueError for a pair with
         exactly one ALL_ZERO half in 'selected' mode — raised from the header's flags; such a value is never used as an address."""
         t = self.tables
+        ragged_lines = self.ragged_lines if ragged_lines is None else bool(ragged_lines)
+        word_forms = self.word_forms if word_forms is None else bool(word_forms)
         if index_dtype not in (torch.int64, torch.int32):
             raise TypeError("index_dtype must be torch.int64 or torch.int32")
         if entity_indices.dim() != 3 or entity_indices.shape[2] != 2 or surface_ids.shape != entity_indices.shape:
@@ -289,11 +322,11 @@ class ContextBatcher:
                 and _lib.lib().recon_ctx_batch_supported(n, t.dims["Ne"], t.dims["S"])):
             if surface_ids.dtype != torch.int32:                       # (a value beyond int32 stays outside the table instead of wrapping into it)
                 surface_ids = surface_ids.clamp(-1, 2 ** 31 - 1).to(torch.int32)
-            return self._batch_kernels(ids, surface_ids.contiguous(), index_dtype, ragged_lines)
-        return self._batch_torch(ids, surface_ids.to(torch.int64).contiguous(), index_dtype, ragged_lines)
+            return self._batch_kernels(ids, surface_ids.contiguous(), index_dtype, ragged_lines, word_forms)
+        return self._batch_torch(ids, surface_ids.to(torch.int64).contiguous(), index_dtype, ragged_lines, word_forms)
 
     # ------------------------------------------------------------------------------------------------------------- the kernels
-    def _batch_kernels(self, ids, surf, index_dtype, ragged_lines=False):
+    def _batch_kernels(self, ids, surf, index_dtype, ragged_lines=False, word_forms=False):
         t, L, dev = self.tables, _lib.lib(), ids.device
         B, Cn = ids.shape[0], ids.shape[1]
         npairs, d = B * Cn, t.dims
@@ -309,13 +342,42 @@ class ContextBatcher:
             st = _lib.current_stream()
             _lib.check(L.recon_ctx_batch_index(t._ptrs_c, t._dims_c, ids.data_ptr(), surf.data_ptr(), npairs, mode, uniq.data_ptr(), uinfo.data_ptr(),
                                                pos.data_ptr(), nzpos.data_ptr(), slot.data_ptr(), hdr.data_ptr(), st), "recon_ctx_batch_index")
-            U, T, P, Mnz, max_pos, err, Lr = hdr.tolist()[:7]              # the one host read
+            if word_forms:                                             # marked and counted in front of the read: S_d is the header's eighth word
+                NFm, tok_form, form_chars = d["NFm"], t.arrays["tok_form"], t.arrays["form_chars"]
+                nbytes = L.recon_ctx_batch_forms_scratch_bytes(NFm)
+                if nbytes == 0:                                        # more table forms than the scan takes
+                    return self._batch_torch(ids, surf.to(torch.int64), index_dtype, ragged_lines, word_forms)
+                scratch = _new((nbytes // 4,), torch.int32, dev)       # flags, ranks and the list of present forms
+                _lib.check(L.recon_ctx_batch_forms_count(t._ptrs_c, t._dims_c, tok_form.data_ptr(), form_chars.data_ptr(), NFm, uniq.data_ptr(),
+                                                         uinfo.data_ptr(), npairs, int(ragged_lines), scratch.data_ptr(), hdr.data_ptr(), st),
+                           "recon_ctx_batch_forms_count")
+            U, T, P, Mnz, max_pos, err, Lr, S_d = hdr.tolist()             # the one host read
             _raise_flags(err, t)
             W = d["conv_filter_size"] - 1 + T * (d["max_char_len"] + d["conv_filter_size"] - 1)
             if U * P * W >= MAX_CELLS:                                 # (beyond the defaults' reach: 8193 entities of 32 x 386 are 1e8 cells)
-                return self._batch_torch(ids, surf.to(torch.int64), index_dtype, ragged_lines)
+                return self._batch_torch(ids, surf.to(torch.int64), index_dtype, ragged_lines, word_forms)
             ib = 8 if index_dtype == torch.int64 else 4
-            if ragged_lines:                                           # the present lines alone: Lr rows, a RaggedLines in the mask's place
+            if word_forms:                                             # the words (and the mask or the line map) as below; no char block
+                n_rows = Lr if ragged_lines else U * P
+                span = d["max_char_len"] + d["conv_filter_size"] - 1
+                words = _new((n_rows, T) if ragged_lines else (U, P, T), index_dtype, dev)
+                form_rows = _new((S_d, d["conv_filter_size"] - 1 + span), index_dtype, dev)
+                slot_form = _new((n_rows * T,), torch.int32, dev)
+                line_ptr = row_ent = mask = None
+                if ragged_lines:
+                    line_ptr, row_ent = _new((U + 1,), torch.int32, dev), _new((Lr,), torch.int32, dev)
+                else:
+                    mask = _new((U, P), torch.bool, dev)
+                _lib.check(L.recon_ctx_batch_fill_forms(t._ptrs_c, t._dims_c, tok_form.data_ptr(), form_chars.data_ptr(), NFm, scratch.data_ptr(),
+                                                        uniq.data_ptr(), uinfo.data_ptr(), U, n_rows, P, T, S_d, int(ragged_lines), ib,
+                                                        words.data_ptr() if T else None, _lib.ptr(mask), _lib.ptr(line_ptr), _lib.ptr(row_ent),
+                                                        form_rows.data_ptr() if S_d else None, slot_form.data_ptr() if n_rows * T else None, st),
+                           "recon_ctx_batch_fill_forms")
+                if ragged_lines:
+                    mask = RaggedLines(line_ptr, U, Lr, P)
+                form_ptr, form_slots = occurrence_lists(slot_form, S_d)
+                chars = WordForms(form_rows, slot_form, form_ptr, form_slots, n_rows, T, S_d, span, d["conv_filter_size"])
+            elif ragged_lines:                                           # the present lines alone: Lr rows, a RaggedLines in the mask's place
                 words = _new((Lr, T), index_dtype, dev)
                 chars = _new((Lr, W), index_dtype, dev)
                 line_ptr = _new((U + 1,), torch.int32, dev)
@@ -346,7 +408,7 @@ class ContextBatcher:
         return out
 
     # ------------------------------------------------------------------------------------------------------------- torch primitives
-    def _batch_torch(self, ids, surf, index_dtype, ragged_lines=False):
+    def _batch_torch(self, ids, surf, index_dtype, ragged_lines=False, word_forms=False):
         t, dev, d, a = self.tables, ids.device, self.tables.dims, self.tables.arrays
         B, Cn = ids.shape[0], ids.shape[1]
         n, Ne, S, G = ids.numel(), d["Ne"], d["S"], d["G"]
@@ -406,12 +468,24 @@ class ContextBatcher:
         cells = torch.full((U, P, T, mcl + cfs - 1), pad, **i64)
         cells[..., :mcl] = torch.where(has[..., None], a["tok_chars"].to(torch.int64)[tok], torch.full((), pad, **i64))
         chars = torch.cat((torch.full((U, P, cfs - 1), pad, **i64), cells.view(U, P, T * (mcl + cfs - 1))), dim=2).to(index_dtype)
+        table_form = torch.where(has, a["tok_form"].to(torch.int64)[tok], torch.zeros((), **i64)) if word_forms else None       # [U, P, T]; 0: an empty slot
         out = StageBBatch()
         out.unique_entities, out.entity_indices, out.entities_position = unique_entities, ids, entities_position
         out.context_words, out.context_chars, out.context_mask = words, chars, ~live
         if ragged_lines:                                               # the rows under ~mask, entity by entity (boolean indexing: a host read on a GPU)
             out.context_words, out.context_chars = words[live], chars[live]
             out.context_mask = RaggedLines.from_counts(live.sum(1), dev)
+            table_form = table_form[live] if word_forms else None
+        if word_forms:                                                 # the kernels' numbering: the present table forms, ascending
+            present = torch.zeros(d["NFm"], **i64).index_fill_(0, table_form.reshape(-1), 1)
+            rank = present.cumsum(0) - 1
+            form_of = torch.nonzero(present).squeeze(1)                # (a host read on a GPU)
+            lead = torch.full((form_of.numel(), cfs - 1), pad, **i64)
+            form_rows = torch.cat((lead, a["form_chars"].to(torch.int64)[form_of], lead), dim=1).to(index_dtype).contiguous()
+            slot_form = rank[table_form.reshape(-1)].to(torch.int32).contiguous()
+            form_ptr, form_slots = occurrence_lists(slot_form, form_of.numel())
+            out.context_chars = WordForms(form_rows, slot_form, form_ptr, form_slots, table_form.shape[0] * (1 if ragged_lines else P), T, form_of.numel(),
+                                          mcl + cfs - 1, cfs)
         out.max_occurred_entity_in_batch_pos = int(max_pos)
         out.gat_entity_embeddings = out.nonzero_gat_entity_embeddings = out.nonzero_entity_pos = None
         out.gat_mode = mode

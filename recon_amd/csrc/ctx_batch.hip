@@ -28,6 +28,13 @@
 //   scans the counts in rank order into line_ptr [U + 1] and writes the owner of every row into row_ent [L]; the fill's vectors then find
 //   (entity, line) of a row by two loads, row_ent[row] and line_ptr[u], where a search of line_ptr would be 13 dependent loads for the 8193
 //   entities a batch can hold.  The map is L int32, at most 1/386 of the char block at the reference's widths.  No mask is written: every row is present.
+// k_cb_forms_mark, k_cb_forms_scan, k_cb_forms_fill (recon_ctx_batch_forms_count, recon_ctx_batch_fill_forms): the char block
+//   as its distinct word windows.  The tables carry a form id per token (tok_form; form 0 = the empty slot's all-pad row) and the forms' char
+//   rows (form_chars).  Behind k_cb_index and in front of the host's read, k_cb_forms_mark walks the batch's lines by the sizes the header holds ON THE
+//   DEVICE and stores 1 into flags[form] for every token's form, and into flags[0] where a line ends in front of T_b (same-value stores: any
+//   order, one result); ONE workgroup then scans the flags in tiles of 4096 into rank[form] = the present forms below it, lists the present
+//   forms and writes their number S_d into the header's eighth word.  After the read k_cb_forms_fill writes slot_form [rows T_b] = rank[form of the
+//   slot's token] and chars [S_d][cfs - 1 + mcl + cfs - 1]; the dense [rows][W] block is never written.
 // k_cb_gat: a wave per (b, c) pair writes both halves of gat_entity_embeddings and, for a present pair, the row of the compacted block.
 #include "recon_common.h"
 
@@ -368,6 +375,119 @@ __global__ void __launch_bounds__(kCbFillThreads) k_cb_gat(const CbTables t, con
     }
 }
 
+// ---- the char block as its distinct word windows
+struct CbForms {
+    const int32_t* tok_form;       // [V]: the form of every token, 1 .. NFm - 1 (0: a token whose char row is all pad)
+    const int32_t* form_chars;     // [NFm][mcl]; row 0 is all pad
+    int32_t NFm, V, NF;
+};
+constexpr int kCbFormTile = 4 * kCbThreads;           // flags per scan step
+
+// the table form in word slot w of a line (0 behind the line's end), clamped into the tables whatever memory holds
+__device__ __forceinline__ int32_t cb_slot_form(const CbTables& t, const CbForms& fm, const CbLine& ln, int32_t w) {
+    if (w >= ln.len) return 0;
+    const int32_t tok = min(max(t.tok_flat[min(max(ln.start + w, 0), fm.NF - 1)], 0), fm.V - 1);
+    return min(max(fm.tok_form[tok], 0), fm.NFm - 1);
+}
+
+// One thread per (entity, line) of the padded grid, by the sizes k_cb_index left in the header (the host has not read them yet): the
+// forms of the line's tokens, and form 0 where the line is shorter than T_b.  ragged: the lines at and behind an entity's count do not exist.
+__global__ void __launch_bounds__(kCbFillThreads) k_cb_forms_mark(const CbTables t, const CbForms fm, const int64_t* __restrict__ uniq,
+                                                                  const int32_t* __restrict__ uinfo, const int32_t* __restrict__ hdr, int32_t max_U,
+                                                                  int32_t ragged, int32_t* __restrict__ flags) {
+    const int32_t U = min(max(hdr[0], 0), max_U), T = min(max(hdr[1], 0), t.max_T), P = min(max(hdr[2], 0), t.max_P);
+    const int64_t items = static_cast<int64_t>(U) * P;
+    const CbPaddedRows rows{max(P, 1)};
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kCbFillThreads + threadIdx.x; i < items; i += static_cast<int64_t>(gridDim.x) * kCbFillThreads) {
+        const int32_t row = static_cast<int32_t>(i);
+        if (ragged && row % P >= uinfo[2 * (row / P)]) continue;
+        const CbLine ln = cb_line(t, uniq, uinfo, row, rows, T);
+        for (int32_t w = 0; w < ln.len; ++w) flags[cb_slot_form(t, fm, ln, w)] = 1;
+        if (ln.len < T) flags[0] = 1;
+    }
+}
+
+// rank[f] = the set flags below f, form_of[r] = the r-th present form, hdr[7] = their number.  ONE workgroup, tiles of 4096 flags: a
+// thread's four, a wave's sums by __shfl_up, the 16 wave totals by every thread, the carry in a register.
+__global__ void __launch_bounds__(kCbThreads) k_cb_forms_scan(const int32_t* __restrict__ flags, int32_t NFm, int32_t* __restrict__ rank,
+                                                              int32_t* __restrict__ form_of, int32_t* __restrict__ hdr) {
+    __shared__ uint32_t wsum[kCbThreads / kWave];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    uint32_t carry = 0;
+    for (int32_t base = 0; base < NFm; base += kCbFormTile) {
+        const int32_t i0 = base + 4 * tid;
+        uint32_t c[4], sum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { c[j] = (i0 + j < NFm && flags[i0 + j] != 0) ? 1u : 0u; sum += c[j]; }
+        uint32_t incl = sum;
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) {
+            const uint32_t o = __shfl_up(incl, off, kWave);
+            if (lane >= off) incl += o;
+        }
+        if (lane == kWave - 1) wsum[wv] = incl;
+        __syncthreads();
+        uint32_t below = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < kCbThreads / kWave; ++w) { const uint32_t s = wsum[w]; below += w < wv ? s : 0u; all += s; }
+        uint32_t run = carry + below + incl - sum;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (i0 + j < NFm) {
+                rank[i0 + j] = static_cast<int32_t>(run);
+                if (c[j]) form_of[run] = i0 + j;
+                run += c[j];
+            }
+        carry += all;
+        __syncthreads();                                                  // wsum is written again in the next tile
+    }
+    if (tid == 0) hdr[7] = static_cast<int32_t>(carry);
+}
+
+// blocks [0, slot_blocks): slot_form[row T + w] = rank[the slot's form]; behind them chars [S_d][Wf]: the present forms' windows
+template <typename IT, typename ROWS>
+__global__ void __launch_bounds__(kCbFillThreads) k_cb_forms_fill(const CbTables t, const CbForms fm, const int64_t* __restrict__ uniq,
+                                                                  const int32_t* __restrict__ uinfo, int32_t n_rows, const ROWS P, int32_t T, int32_t S_d,
+                                                                  const int32_t* __restrict__ rank, const int32_t* __restrict__ form_of,
+                                                                  int64_t slot_blocks, int32_t* __restrict__ slot_form, IT* __restrict__ chars) {
+    const int64_t blk = blockIdx.x;
+    if (blk < slot_blocks) {
+        const int64_t i = blk * kCbFillThreads + threadIdx.x;
+        if (i >= static_cast<int64_t>(n_rows) * T) return;
+        const int32_t row = static_cast<int32_t>(i / T), w = static_cast<int32_t>(i - static_cast<int64_t>(row) * T);
+        const CbLine ln = cb_line(t, uniq, uinfo, row, P, T);
+        slot_form[i] = min(max(rank[cb_slot_form(t, fm, ln, w)], 0), S_d - 1);
+    } else {
+        const int32_t Wf = 2 * (t.cfs - 1) + t.mcl;
+        const int64_t i = (blk - slot_blocks) * kCbFillThreads + threadIdx.x;
+        if (i >= static_cast<int64_t>(S_d) * Wf) return;
+        const int32_t r = static_cast<int32_t>(i / Wf), c = static_cast<int32_t>(i - static_cast<int64_t>(r) * Wf) - (t.cfs - 1);
+        const int32_t f = min(max(form_of[r], 0), fm.NFm - 1);
+        chars[i] = static_cast<IT>((c >= 0 && c < t.mcl) ? fm.form_chars[static_cast<int64_t>(f) * t.mcl + c] : t.pad);
+    }
+}
+
+bool cb_forms(const int64_t* dims, const int32_t* tok_form, const int32_t* form_chars, int64_t NFm, CbForms* fm) {
+    if (!dims || !tok_form || !form_chars || NFm < 1 || NFm >= (int64_t{1} << 31) - kCbFormTile) return false;
+    if (dims[CB_D_V] < 1 || dims[CB_D_V] >= (int64_t{1} << 31) || dims[CB_D_NF] < 1 || dims[CB_D_NF] >= (int64_t{1} << 31)) return false;
+    fm->tok_form = tok_form;
+    fm->form_chars = form_chars;
+    fm->NFm = static_cast<int32_t>(NFm);
+    fm->V = static_cast<int32_t>(dims[CB_D_V]);
+    fm->NF = static_cast<int32_t>(dims[CB_D_NF]);
+    return true;
+}
+
+template <typename IT, typename ROWS>
+void cb_launch_forms_fill(hipStream_t st, const CbTables& t, const CbForms& fm, const int64_t* uniq, const int32_t* uinfo, int64_t n_rows, const ROWS& rows,
+                          int32_t T, int32_t S_d, const int32_t* rank, const int32_t* form_of, int32_t* slot_form, void* chars) {
+    const int64_t sb = ceil_div64(n_rows * T, kCbFillThreads);
+    const int64_t cb = ceil_div64(static_cast<int64_t>(S_d) * (2 * (t.cfs - 1) + t.mcl), kCbFillThreads);
+    if (sb + cb == 0) return;
+    hipLaunchKernelGGL((k_cb_forms_fill<IT, ROWS>), dim3(static_cast<unsigned>(sb + cb)), dim3(kCbFillThreads), 0, st, t, fm, uniq, uinfo,
+                       static_cast<int32_t>(n_rows), rows, T, S_d, rank, form_of, sb, slot_form, static_cast<IT*>(chars));
+}
+
 bool cb_ids_ok(int64_t n_ids, int64_t Ne, int64_t S) {
     return n_ids >= 2 && n_ids <= kCbMaxIds && n_ids % 2 == 0 && Ne >= 0 && Ne < (int64_t{1} << 31) - 1 && S >= 1 && S < (int64_t{1} << 31);
 }
@@ -406,12 +526,12 @@ bool cb_tables(const void* const* tables, const int64_t* dims, bool want_gat, Cb
 // `n_rows` rows of either form (the padded form: U P_b, with the mask behind them)
 template <typename IT, typename ROWS>
 void cb_launch_fill(hipStream_t st, const CbTables& t, const int64_t* uniq, const int32_t* uinfo, int64_t n_rows, const ROWS& rows, int32_t T, void* words,
-                    void* chars, void* mask) {
+                    void* chars, void* mask, bool with_chars = true) {
     constexpr int VE = 16 / sizeof(IT);
     const int64_t W = t.cfs - 1 + static_cast<int64_t>(T) * (t.mcl + t.cfs - 1);
     const int32_t cs = static_cast<int32_t>((reinterpret_cast<uintptr_t>(chars) & 15u) / sizeof(IT));
     const int32_t ws = static_cast<int32_t>((reinterpret_cast<uintptr_t>(words) & 15u) / sizeof(IT));
-    const int64_t cb = ceil_div64(ceil_div64(n_rows * W + cs, VE), kCbFillThreads);
+    const int64_t cb = with_chars ? ceil_div64(ceil_div64(n_rows * W + cs, VE), kCbFillThreads) : 0;       // (the forms' batch has no char block)
     const int64_t wb = ceil_div64(ceil_div64(n_rows * T + ws, VE), kCbFillThreads);
     const int64_t mb = ROWS::kMask ? ceil_div64(n_rows, kCbFillThreads) : 0;
     hipLaunchKernelGGL((k_cb_fill<IT, ROWS>), dim3(static_cast<unsigned>(cb + wb + mb)), dim3(kCbFillThreads), 0, st, t, uniq, uinfo,
@@ -420,10 +540,10 @@ void cb_launch_fill(hipStream_t st, const CbTables& t, const int64_t* uniq, cons
 
 // what recon_ctx_batch_fill and recon_ctx_batch_fill_ragged check alike, over n_rows rows
 int cb_fill_args(const void* const* tables, const int64_t* dims, const int64_t* uniq, const int32_t* uinfo, int64_t U, int64_t n_rows, int32_t P_b, int32_t T_b,
-                 int32_t index_bytes, const void* words, const void* chars, CbTables* t) {
+                 int32_t index_bytes, const void* words, const void* chars, CbTables* t, bool with_chars = true) {
     if (U < 1 || P_b < 1 || T_b < 0 || (index_bytes != 4 && index_bytes != 8)) return RECON_ERR_INVALID;
     if (!cb_tables(tables, dims, false, t)) return RECON_ERR_INVALID;
-    if (!uniq || !uinfo || !chars || (T_b > 0 && !words)) return RECON_ERR_INVALID;
+    if (!uniq || !uinfo || (with_chars && !chars) || (T_b > 0 && !words)) return RECON_ERR_INVALID;
     if (P_b > t->max_P || T_b > t->max_T) return RECON_ERR_INVALID;
     if ((reinterpret_cast<uintptr_t>(chars) | reinterpret_cast<uintptr_t>(words)) % static_cast<uintptr_t>(index_bytes)) return RECON_ERR_INVALID;
     if (U > kCbMaxIds + 1) return RECON_ERR_UNSUPPORTED;
@@ -506,6 +626,80 @@ extern "C" int recon_ctx_batch_gat(const void* const* tables, const int64_t* dim
     if (n_pairs > kCbMaxIds / 2 || !cb_ids_ok(2 * n_pairs, t.Ne, t.S)) return RECON_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_cb_gat, dim3(static_cast<unsigned>(ceil_div64(n_pairs, kCbFillThreads / kWave))), dim3(kCbFillThreads), 0, as_stream(stream), t,
                        entity_indices, n_pairs, pair_slot, gat_entity_embeddings, nonzero_gat_entity_embeddings);
+    RECON_CHECK_LAUNCH();
+    return RECON_OK;
+}
+
+extern "C" size_t recon_ctx_batch_forms_scratch_bytes(int64_t num_forms) {
+    if (num_forms < 1 || num_forms >= (int64_t{1} << 31) - recon::kCbFormTile) return 0;
+    return static_cast<size_t>(3 * num_forms) * sizeof(int32_t);
+}
+
+extern "C" int recon_ctx_batch_forms_count(const void* const* tables, const int64_t* dims, const int32_t* tok_form, const int32_t* form_chars, int64_t num_forms,
+                                           const int64_t* unique_entities, const int32_t* unique_info, int64_t n_pairs, int32_t ragged, int32_t* scratch,
+                                           int32_t* header, recon_stream_t stream) {
+    using namespace recon;
+    if (n_pairs < 1 || n_pairs > kCbMaxIds / 2 || (ragged != 0 && ragged != 1)) return RECON_ERR_INVALID;
+    CbTables t;
+    CbForms fm;
+    if (!cb_tables(tables, dims, false, &t) || !cb_forms(dims, tok_form, form_chars, num_forms, &fm)) return RECON_ERR_INVALID;
+    if (!unique_entities || !unique_info || !scratch || !header) return RECON_ERR_INVALID;
+    int32_t* flags = scratch;
+    int32_t* rank = scratch + num_forms;
+    int32_t* form_of = rank + num_forms;
+    const hipStream_t st = as_stream(stream);
+    if (hipMemsetAsync(flags, 0, static_cast<size_t>(num_forms) * sizeof(int32_t), st) != hipSuccess) return RECON_ERR_LAUNCH;
+    const int32_t max_U = static_cast<int32_t>(2 * n_pairs + 1);
+    const int64_t blocks = std::min<int64_t>(1024, ceil_div64(static_cast<int64_t>(max_U) * t.max_P, kCbFillThreads));
+    hipLaunchKernelGGL(k_cb_forms_mark, dim3(static_cast<unsigned>(blocks)), dim3(kCbFillThreads), 0, st, t, fm, unique_entities, unique_info, header, max_U,
+                       ragged, flags);
+    RECON_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_cb_forms_scan, dim3(1), dim3(kCbThreads), 0, st, flags, fm.NFm, rank, form_of, header);
+    RECON_CHECK_LAUNCH();
+    return RECON_OK;
+}
+
+extern "C" int recon_ctx_batch_fill_forms(const void* const* tables, const int64_t* dims, const int32_t* tok_form, const int32_t* form_chars, int64_t num_forms,
+                                          const int32_t* scratch, const int64_t* unique_entities, const int32_t* unique_info, int64_t U, int64_t n_rows,
+                                          int32_t P_b, int32_t T_b, int64_t S_d, int32_t ragged, int32_t index_bytes, void* context_words, void* context_mask,
+                                          int32_t* line_ptr, int32_t* row_entity, void* form_rows, int32_t* slot_form, recon_stream_t stream) {
+    using namespace recon;
+    CbTables t;
+    CbForms fm;
+    if (ragged != 0 && ragged != 1) return RECON_ERR_INVALID;
+    if (ragged ? (n_rows < U || (U >= 1 && P_b >= 1 && n_rows > U * P_b) || !line_ptr || !row_entity) : (n_rows != U * P_b || !context_mask)) return RECON_ERR_INVALID;
+    const int rc = cb_fill_args(tables, dims, unique_entities, unique_info, U, n_rows, P_b, T_b, index_bytes, context_words, nullptr, &t, false);
+    if (rc != RECON_OK) return rc;
+    if (!cb_forms(dims, tok_form, form_chars, num_forms, &fm) || !scratch) return RECON_ERR_INVALID;
+    const int64_t n_slots = n_rows * T_b;
+    if (S_d < 0 || S_d > num_forms || S_d > n_slots || (n_slots > 0 && S_d < 1)) return RECON_ERR_INVALID;
+    if ((n_slots > 0 && !slot_form) || (S_d > 0 && !form_rows)) return RECON_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(form_rows) % static_cast<uintptr_t>(index_bytes)) return RECON_ERR_INVALID;
+    const int32_t* rank = scratch + num_forms;
+    const int32_t* form_of = rank + num_forms;
+    const hipStream_t st = as_stream(stream);
+    const int32_t s_d = static_cast<int32_t>(S_d);
+    if (ragged) {
+        hipLaunchKernelGGL(k_cb_scan, dim3(1), dim3(kCbThreads), 0, st, unique_info, static_cast<int32_t>(U), P_b, static_cast<int32_t>(n_rows), line_ptr, row_entity);
+        RECON_CHECK_LAUNCH();
+        const CbRaggedRows rows{line_ptr, row_entity};
+        if (index_bytes == 8) {
+            cb_launch_fill<int64_t>(st, t, unique_entities, unique_info, n_rows, rows, T_b, context_words, nullptr, nullptr, false);
+            cb_launch_forms_fill<int64_t>(st, t, fm, unique_entities, unique_info, n_rows, rows, T_b, s_d, rank, form_of, slot_form, form_rows);
+        } else {
+            cb_launch_fill<int32_t>(st, t, unique_entities, unique_info, n_rows, rows, T_b, context_words, nullptr, nullptr, false);
+            cb_launch_forms_fill<int32_t>(st, t, fm, unique_entities, unique_info, n_rows, rows, T_b, s_d, rank, form_of, slot_form, form_rows);
+        }
+    } else {
+        const CbPaddedRows rows{P_b};
+        if (index_bytes == 8) {
+            cb_launch_fill<int64_t>(st, t, unique_entities, unique_info, n_rows, rows, T_b, context_words, nullptr, context_mask, false);
+            cb_launch_forms_fill<int64_t>(st, t, fm, unique_entities, unique_info, n_rows, rows, T_b, s_d, rank, form_of, slot_form, form_rows);
+        } else {
+            cb_launch_fill<int32_t>(st, t, unique_entities, unique_info, n_rows, rows, T_b, context_words, nullptr, context_mask, false);
+            cb_launch_forms_fill<int32_t>(st, t, fm, unique_entities, unique_info, n_rows, rows, T_b, s_d, rank, form_of, slot_form, form_rows);
+        }
+    }
     RECON_CHECK_LAUNCH();
     return RECON_OK;
 }

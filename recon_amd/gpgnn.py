@@ -21,6 +21,7 @@ from .transitions import pair_transitions
 from .relation_head import relation_logits
 from .line_pool import entity_line_pool, entity_line_pool_ragged
 from .ragged_lines import RaggedLines
+from .word_forms import WordForms, word_form_features
 from .pair_groups import PairGroups
 
 
@@ -228,20 +229,15 @@ class EntityEmbedding(nn.Module):
     def forward(self, words, chars, conv_mask):
         """words [U, lines, len], chars [U, lines, cfs-1 + len*(max_char+cfs-1)], conv_mask bool [U, lines-ecfs+1] (True = padding
         line) -> [U, entity_embed_dim].  With a `RaggedLines` as the third argument: words [L, len], chars [L, .], the entities'
-        present lines alone (`forward_ragged`)."""
+        present lines alone (`forward_ragged`).  chars may be a `WordForms` over the U lines (or L) rows in either form (`_char_features`)."""
         if isinstance(conv_mask, RaggedLines):
             return self.forward_ragged(words, chars, conv_mask)
         U, lines = words.shape[0], words.shape[1]
         words = words.reshape(U * lines, words.shape[2])
-        chars = chars.reshape(U * lines, chars.shape[2])
         we = self.word_embeddings
         plain = type(we) is nn.Embedding and we.max_norm is None and not we.sparse and not we.scale_grad_by_freq
         word_vec = None if plain else we(words)
-        emb = self.char_embeddings
-        draw = emb.draw_packed_keep if self.packed_char_dropout else emb.draw_keep
-        keep = draw(chars.shape[0], chars.shape[1], emb.embeddings.embedding_dim, chars.device)
-        char_feat = char_word_features(chars, emb.embeddings.weight, self.conv1d.weight, self.conv1d.bias, self.word_span, keep=keep,
-                                       padding_idx=emb.embeddings.padding_idx)                                              # :57-61
+        char_feat = self._char_features(chars if isinstance(chars, WordForms) else chars.reshape(U * lines, chars.shape[2]), words)   # :57-61
         if plain:        # gather, cat, LSTM and the h_n reshape as one op (csrc/ctx_lstm.hip; the stock ops where its kernels do not apply)   # :62-70
             h_n = context_line_states(self.lstm, char_feat, words, we.weight, padding_idx=we.padding_idx).reshape(U, lines, 2 * self.hidden_dim)
         else:
@@ -256,6 +252,23 @@ class EntityEmbedding(nn.Module):
         conv = conv.masked_fill(conv_mask.unsqueeze(1), -float('inf'))
         return conv.max(dim=2).values
 
+    def _char_features(self, chars, words):
+        """[rows, len, char_feature_size] of chars [rows, .] or of a `WordForms` over the rows of words [rows, len] (models/models.py:57-61).
+        With a `WordForms` the char-CNN runs over the S_d distinct windows and the dropout factors are drawn for them: every occurrence
+        of a form in the batch shares one draw, where the dense block draws per slot — another distribution, hence an opt-in of the
+        batcher (`word_forms=True`).  In eval mode or at p = 0 the result is the dense call's."""
+        emb = self.char_embeddings
+        draw = emb.draw_packed_keep if self.packed_char_dropout else emb.draw_keep
+        weights = (emb.embeddings.weight, self.conv1d.weight, self.conv1d.bias)
+        if isinstance(chars, WordForms):
+            if (chars.rows, chars.T) != tuple(words.shape) or chars.word_span != self.word_span or chars.cfs != self.conv1d.kernel_size[0]:
+                raise ValueError("EntityEmbedding: %r does not fit words %s with word_span = %d, cfs = %d"
+                                 % (chars, tuple(words.shape), self.word_span, self.conv1d.kernel_size[0]))
+            keep = draw(chars.total, chars.chars.shape[1], emb.embeddings.embedding_dim, chars.device)
+            return word_form_features(chars, *weights, keep=keep, padding_idx=emb.embeddings.padding_idx)
+        keep = draw(chars.shape[0], chars.shape[1], emb.embeddings.embedding_dim, chars.device)
+        return char_word_features(chars, *weights, self.word_span, keep=keep, padding_idx=emb.embeddings.padding_idx)
+
     def forward_ragged(self, words, chars, lines):
         """words [L, len], chars [L, cfs-1 + len*(max_char+cfs-1)], lines a RaggedLines over the L rows -> [U, entity_embed_dim]: `forward`
         without the padding lines.  The char-CNN and the line LSTM run over the L present lines, and
@@ -264,16 +277,15 @@ class EntityEmbedding(nn.Module):
         of the max) and gets a zero gradient, so the results are those of the padded call.  Dropout: the char embedding's factors are
         drawn for L rows — the same distribution on another random stream than a padded batch draws from, the standing of
         `packed_char_dropout`."""
-        if words.dim() != 2 or chars.dim() != 2 or words.shape[0] != lines.total or chars.shape[0] != lines.total:
+        forms = isinstance(chars, WordForms)
+        shapes_fit = words.dim() == 2 and (forms or chars.dim() == 2)
+        rows_fit = shapes_fit and words.shape[0] == lines.total and (chars.rows if forms else chars.shape[0]) == lines.total
+        if not rows_fit:
             raise ValueError("EntityEmbedding: with a RaggedLines, words and chars must be [L, .] with L = %d rows, got %s and %s"
-                             % (lines.total, tuple(words.shape), tuple(chars.shape)))
+                             % (lines.total, tuple(words.shape), chars if forms else tuple(chars.shape)))
         we = self.word_embeddings
         plain = type(we) is nn.Embedding and we.max_norm is None and not we.sparse and not we.scale_grad_by_freq
-        emb = self.char_embeddings
-        draw = emb.draw_packed_keep if self.packed_char_dropout else emb.draw_keep
-        keep = draw(chars.shape[0], chars.shape[1], emb.embeddings.embedding_dim, chars.device)
-        char_feat = char_word_features(chars, emb.embeddings.weight, self.conv1d.weight, self.conv1d.bias, self.word_span, keep=keep,
-                                       padding_idx=emb.embeddings.padding_idx)
+        char_feat = self._char_features(chars, words)
         if plain:
             h_n = context_line_states(self.lstm, char_feat, words, we.weight, padding_idx=we.padding_idx)
         else:

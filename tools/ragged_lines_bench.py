@@ -59,11 +59,12 @@ def set_line_counts(ds, rng, lo, hi):
     ds["context_wikidata"] = ctx
 
 
-def make_dataset(N, n, T, seed, lo, hi, zipf=1.33):       # about 450 unique entities per batch of 50, as section 28 measured
+def make_dataset(N, n, T, seed, lo, hi, zipf=1.33, fill=None):       # about 450 unique entities per batch of 50, as section 28 measured
+    """fill: what writes the entities' context in place of `set_line_counts` (tools/word_forms_bench.py's adverse table)."""
     C = n * (n - 1)
     rng = np.random.default_rng(seed)
     ds = random_dataset(rng, 1500, PARAMS["gat_entity_embedding_dim"])
-    set_line_counts(ds, rng, lo, hi)
+    (fill or set_line_counts)(ds, rng, lo, hi)
     ids, sf = random_batch(np.random.default_rng(seed + 1), ds, N, C, zipf=zipf)
     tables, surface_ids = build(ds, "wikidata", sf, "selected")
     rng = np.random.default_rng(seed + 2)
